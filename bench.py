@@ -1,15 +1,22 @@
 """Headline benchmark: sampled conformations / second, 256-residue chain, 100 denoise steps.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config cfg2|cfg3|cfg4|cfg5]   (N > 1: torch.distributed.run)
+    python bench.py [--gpus N --steps K --warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full]
+    (N > 1: torch.distributed.run)
 
 One "step" = one replica chunk sampled end to end on every GPU: forward marginal, 1 self-conditioning forward +
 S x (score-network forward + fused SE(3) step), backbone projection, RCCL gather of the coordinates to rank 0 and
 copy to the host.  Replicas are independent, so the work is sharded with no data-path collective except that final
-gather (weak scaling: the same replicas per GPU at every N).  Prints ONE JSON line (see README "bench contract"); adds
+gather (weak scaling: the same replicas per GPU at every N).  Prints ONE JSON line (see README "bench contract").
+A plain run sets up, warms up, times K steps and prints the headline (metric, value, unit, ms_per_step, dtype, ...).
+--dump-outputs DIR writes what the last timed step returned (rank 0) as DIR/<name>.npy in float32 (at most 64 MB:
+a fixed, seeded sample of rows beyond that), so that two builds can be compared output for output.
+--full adds what the headline does not need (the --no-* switches trim it):
   roofline     the dominant kernel (s2s_edge_transition, MFMA bound) timed per launch with HIP events on the launch
                stream inside the timed region (+ `ipa_kernel`: the HBM-bound IPA core the north star names)
-  cpu_baseline the CPU oracle (a port of the reference path, bit-equal to it on CPU) timed on this box's host cores on
+  kernel_times one more (untimed) step with per-launch events per kernel family (+ edge_embed / node rooflines)
+  cpu_baseline the CPU oracle (a port of the reference path, bit-equal to it on CPU) timed on the host cores on
                a bounded sample of the same workload (rank 0, N=1 only)
+  other_configs one step each of cfg3 / cfg4 / cfg5 / ref_default in processes of their own (default cfg2, N=1 only)
 --config selects the BASELINE.json workload (default cfg2 = configs[1], the one the metric is quoted on):
   cfg3  configs[2]: the 12 Science2011 fast folders (tests/golden/pdb), 1000 replicas each, PDB text written natively
   cfg4  configs[3]: 512-residue chain, 128 replicas per GPU (1024 over 8), 200 steps
@@ -154,6 +161,30 @@ def traffic_from_profiles(pairs, mode):
     return None, None
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_NAMES = {"cfg2": "backbone", "cfg4": "backbone", "cfg3": "atom37_last_target", "cfg5": "backbone_residues",
+              "ref_default": "backbone_last_target"}
+
+
+def dump_outputs(out_dir, config, res):
+    """--dump-outputs: what the last timed step returned on rank 0, in float32 (cfg2 / cfg4: the gathered backbone [(world,) B, N, 5, 3];
+    cfg3: atom37 of the last target [B * world, N, 37, 3]; cfg5: the flat gather as residues [R, 5, 3]; ref_default: the backbone of the
+    last target's last t_delta).  Beyond 64 MB a fixed, seeded sample of rows (one residue's atoms each) is written, with the row indices
+    as <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    name = DUMP_NAMES[config]
+    arr = res.detach().float().cpu().numpy()
+    if config == "cfg5":
+        arr = arr.reshape(-1, 5, 3)
+    if arr.nbytes > DUMP_MAX_BYTES:
+        rows = arr.reshape(-1, *arr.shape[-2:])
+        keep = DUMP_MAX_BYTES // (rows[0].nbytes + 8)   # (+ the float64 row index)
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=keep, replace=False))
+        arr = rows[idx]
+        np.save(os.path.join(out_dir, f"{name}_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -169,7 +200,14 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true", help="default cfg2 line at 1 GPU: do not append one step each of cfg3 / cfg4 / cfg5")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-table", action="store_true", help="skip the extra (untimed) step that times the kernel families")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel rooflines inside the timed region, the kernel-family "
+                         "table, the CPU-oracle baseline and the other configs (the --no-* switches trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy (float32, <= 64 MB)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch.distributed as dist
 
@@ -386,7 +424,7 @@ def main():
     extra = {k: (0.0 if k == "pdb_write_s" else v) for k, v in extra.items()}
     barrier()
     t0 = time.perf_counter()
-    timed = ("s2s_edge_transition", "s2s_ipa_attention") if a.config in ("cfg2", "cfg4") else ()  # (timers disable HIP graphs)
+    timed = ("s2s_edge_transition", "s2s_ipa_attention") if a.full and a.config in ("cfg2", "cfg4") else ()  # (timers disable HIP graphs)
     with ops.KernelTimer(*timed) as kt:
         for k in range(a.steps):
             res = one_step(100 + k)
@@ -402,11 +440,13 @@ def main():
     elapsed = float(el.item())
     et_ms, et_n = kt.mean_ms("s2s_edge_transition") if timed else (float("nan"), 0)
     ipa_ms, ipa_n = kt.mean_ms("s2s_ipa_attention") if timed else (float("nan"), 0)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, a.config, res)
     # Kernel-family time table: ONE more step, outside the timed region (per-launch HIP events on the launch stream; they switch the
     # HIP-graph replay of tiny chunks off, which is why cfg3 / cfg5 do not carry them inside the timed region)
     fam = ("s2s_edge_transition", "s2s_edge_embed", "s2s_ipa_attention", "s2s_encoder_attention", "s2s_node_linear")
     table = None
-    if not a.no_kernel_table:   # (every rank runs the step: it contains the job's collectives; rank 0's table is reported)
+    if a.full and not a.no_kernel_table:   # (every rank runs the step: it contains the job's collectives; rank 0's table is reported)
         torch.cuda.synchronize()
         tp0 = time.perf_counter()
         with ops.KernelTimer(*fam) as kp:
@@ -493,9 +533,10 @@ def main():
                                                  nl["total_ms"] * 1e-3, mode, launches_timed=nl["launches"], total_ms=nl["total_ms"], source=src,
                                                  note="flops = sum over launches of 2 M K N as launched; ~11 launches of 0.1 ms each per IPA block at cfg2: "
                                                       "launch- and latency-bound, the fraction is reported for completeness")
-        if world == 1 and not a.no_cpu_baseline and a.config == "cfg2":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.config == "cfg2":
             line["cpu_baseline"] = cpu_baseline(N, S, steps_sampled=a.cpu_steps, replicas=a.cpu_replicas)
-        if world == 1 and a.config == "cfg2" and not a.no_other_configs and a.n_res is None and a.replicas is None and a.denoise_steps is None:
+        if (a.full and world == 1 and a.config == "cfg2" and not a.no_other_configs and a.n_res is None and a.replicas is None
+                and a.denoise_steps is None):
             # the other single-GPU workloads of BASELINE.json and the reference's default inference block (configs/model/diffusion.yaml:88-100
             # there: the workload its users run), ONE step each (their own processes, after the timed region and the CPU baseline):
             # driver-visible numbers for cfg3 / cfg4 / cfg5 / ref_default beside the headline
@@ -509,7 +550,7 @@ def main():
                     # (cfg4 times its kernels inside the timed region like cfg2; cfg3 / cfg5 run under HIP graphs, so their kernel
                     #  fractions come from one more step with per-launch events: the kernel table)
                     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "1", "--warmup", "0",
-                                        "--no-cpu-baseline"] + ([] if cfg in ("cfg3", "cfg5") else ["--no-kernel-table"]), capture_output=True, text=True, timeout=900, cwd=ROOT,
+                                        "--full", "--no-cpu-baseline"] + ([] if cfg in ("cfg3", "cfg5") else ["--no-kernel-table"]), capture_output=True, text=True, timeout=900, cwd=ROOT,
                                        env={k: v for k, v in os.environ.items() if k not in   # (side runs are plain 1-GPU processes)
                                             ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "GROUP_RANK", "LOCAL_WORLD_SIZE", "TORCHELASTIC_RUN_ID")})
                     sub = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1674,6 +1674,39 @@ def test_rccl_one_rank_job_runs_the_device_collectives(tmp_path):
         assert files["plain"] and files["plain"] == files["rccl"], tag
 
 
+def test_bench_plain_run_dumps_what_the_full_run_computes(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` (the plain run) times K steps and prints the headline fields only; --dump-outputs
+    writes the last timed step's backbone in float32, the same from run to run and the same as under --full, whose per-launch
+    timers and extra kernel-table step leave the sampled coordinates alone."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+
+    bare = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "PYTEST_CURRENT_TEST")}
+    shape = ["--gpus", "1", "--n-res", "32", "--replicas", "4", "--denoise-steps", "4", "--steps", "3", "--warmup", "1"]
+    lines, dumps = {}, {}
+    for tag, extra in (("a", []), ("b", []), ("full", ["--full", "--no-cpu-baseline"])):
+        out = tmp_path / tag
+        r = subprocess.run([sys.executable, "bench.py"] + shape + extra + ["--dump-outputs", str(out)], cwd=ROOT, env=bare,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        got = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(got) == 1, r.stdout[-2000:]
+        lines[tag] = json.loads(got[0])
+        assert os.listdir(out) == ["backbone.npy"]
+        dumps[tag] = np.load(out / "backbone.npy")
+    d = lines["a"]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "conformations/s" and d["dtype"].startswith("f32")
+    assert not {"roofline", "ipa_kernel", "kernel_times", "cpu_baseline", "other_configs"} & set(d)
+    assert {"roofline", "ipa_kernel", "kernel_times"} <= set(lines["full"])
+    assert dumps["a"].dtype == np.float32 and dumps["a"].shape == (4, 32, 5, 3) and np.isfinite(dumps["a"]).all()
+    assert np.array_equal(dumps["a"], dumps["b"]) and np.array_equal(dumps["a"], dumps["full"])
+
+
 def test_full_size_batch_is_invariant_at_the_headline_shape(net_smooth, diffuser):
     """BASELINE configs[1] at its FULL batch: 128 replicas of the 256-residue chain as ONE trajectory (n_replica 128 in the reference's
     chunks of replica_per_batch 2, merged: 8 388 608 pairs per launch, the persistent workgroups walk many tiles each) for the 5 + 1

@@ -507,3 +507,29 @@ def test_t_delta_merging_groups(monkeypatch):
         assert all(len(g) == 1 or len(g) * b * n * n <= 8 << 20 for g in groups)
     monkeypatch.setenv("S2S_MERGE_DELTAS", "0")
     assert merge_delta_groups(steps, 100, 35) == [[i] for i in range(10)]
+
+
+def test_bench_dump_outputs_writes_float32_within_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's array as <name>.npy in float32, whole while it fits the cap; beyond it a fixed, seeded
+    sample of rows (one residue's atoms each) plus their indices, the two files together within the cap and the same from run to run."""
+    import bench
+
+    x = torch.arange(2 * 50 * 5 * 3, dtype=torch.float32).reshape(2, 50, 5, 3)
+    bench.dump_outputs(str(tmp_path / "whole"), "cfg2", x)
+    got = np.load(tmp_path / "whole" / "backbone.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    bench.dump_outputs(str(tmp_path / "flat"), "cfg5", x.reshape(-1))
+    assert np.array_equal(np.load(tmp_path / "flat" / "backbone_residues.npy"), x.numpy().reshape(-1, 5, 3))
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1024)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), "cfg4", x)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["backbone.npy", "backbone_rows.npy"]
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= 1024
+    rows = np.load(tmp_path / "a" / "backbone_rows.npy")
+    sample = np.load(tmp_path / "a" / "backbone.npy")
+    assert rows.dtype == np.float64 and len(rows) == len(sample) > 0 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(sample, x.numpy().reshape(-1, 5, 3)[rows.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -5,10 +5,10 @@ T=${1:-r03}
 O=gpurun_out/$T; mkdir -p $O
 python tools/et_only.py --B 128 --N 256 --iters 20 --proj --layout tiled 2>/dev/null | tail -1 > $O/box_calibration.txt
 python -m pytest tests -m gpu -q 2>&1 | tail -4 > $O/pytest.log
-python bench.py > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python bench.py --config cfg3 --steps 1 --warmup 1 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
-python bench.py --config cfg4 --steps 1 --warmup 0 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
-python bench.py --config cfg5 --steps 1 --warmup 0 > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+python bench.py --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python bench.py --full --config cfg3 --steps 1 --warmup 1 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+python bench.py --full --config cfg4 --steps 1 --warmup 0 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+python bench.py --full --config cfg5 --steps 1 --warmup 0 > $O/bench_cfg5.json 2> $O/bench_cfg5.err
 bash tools/prof_bench.sh $T > $O/prof.log 2>&1
 cat $O/box_calibration.txt $O/pytest.log
 for c in cfg2 cfg3 cfg4 cfg5; do python - <<PY

@@ -7,7 +7,7 @@ O=gpurun_out/$T; mkdir -p $O
 python tools/et_only.py --B 128 --N 256 --iters 20 --proj --layout tiled 2>/dev/null | tail -1 > $O/box_calibration.txt
 python -m pytest tests -m gpu -q 2>&1 | tail -4 > $O/pytest.log
 python __graft_entry__.py --smoke 2>&1 | tail -1 > $O/smoke.txt
-python bench.py > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python bench.py --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err
 bash tools/prof_bench.sh $T > $O/prof.log 2>&1
 cat $O/box_calibration.txt $O/pytest.log $O/smoke.txt
 python - <<PY
