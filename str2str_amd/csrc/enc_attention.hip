@@ -16,16 +16,13 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "f16x3.h"
 #include "range_flag.h"
 #include "str2str_hip.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ int rowmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 template <int DH>
 __global__ void __launch_bounds__(256) enc_attention_kernel(const float* __restrict__ qkv, const float* __restrict__ key_bias,
@@ -176,13 +173,12 @@ __global__ void __launch_bounds__(256) enc_attention_kernel(const float* __restr
             for (int u = 0; u < 2; ++u) {
                 if (2 * t + u >= DH / 16) continue;
                 // f16 pair planes of the node stream (x_h, x_l), csrc/node_gemm.hip
-                typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
                 f16x8 ph, pl;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     float v = O[t][8 * u + j] * inv;
                     amax = s2s::range_max(amax, v);
-                    asm volatile("" : "+v"(v));   // one materialised fp32 value feeds both planes (see node_gemm.hip split8_f16)
+                    asm volatile("" : "+v"(v));   // one materialised fp32 value feeds both planes (f16x3.h)
                     const _Float16 a_ = (_Float16)v;
                     ph[j] = a_; pl[j] = (_Float16)(v - (float)a_);
                 }
@@ -205,33 +201,15 @@ __global__ void __launch_bounds__(256) enc_attention_kernel(const float* __restr
 //   P        -> 2^10 p split in registers (the factor keeps the small part of small probabilities in f16's normal range; it is divided
 //               out with the row sum at the end)
 // RANGE: q, k, v are split here and feed the range maximum (range_flag.h, bit kRangeEncoderAttention).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4e __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-// four fp32 values -> elements at .. at+3 of the planes (x_h, x_l): the 1.5-instruction split of csrc/pair_mlp_f16.hip (split4_f16)
-__device__ __forceinline__ void enc_split4(float x0, float x1, float x2, float x3, unsigned& h0, unsigned& h1, unsigned& l0, unsigned& l1, float& amax) {
-    asm volatile(
-        "v_max3_f32 %4, %4, |%5|, |%6|\n\t"
-        "v_cvt_pk_f16_f32 %0, %5, %6\n\t"
-        "v_max3_f32 %4, %4, |%7|, |%8|\n\t"
-        "v_cvt_pk_f16_f32 %1, %7, %8\n\t"
-        "v_fma_mixlo_f16 %2, -%0, 1.0, %5 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %3, -%1, 1.0, %7 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %2, -%0, 1.0, %6 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %3, -%1, 1.0, %8 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(h0), "=&v"(h1), "=&v"(l0), "=&v"(l1), "+v"(amax)
-        : "v"(x0), "v"(x1), "v"(x2), "v"(x3));
-}
 
-// eight values -> one fragment pair (x_h, x_l)
+// eight values -> one fragment pair (x_h, x_l) (f16x3.h)
 __device__ __forceinline__ void enc_split8(float x0, float x1, float x2, float x3, float x4, float x5, float x6, float x7, f16x8& ph, f16x8& pl,
                                            float& amax) {
     unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    enc_split4(x0, x1, x2, x3, h0, h1, l0, l1, amax);
-    enc_split4(x4, x5, x6, x7, h2, h3, l2, l3, amax);
-    ph = __builtin_bit_cast(f16x8, u32x4e{h0, h1, h2, h3});
-    pl = __builtin_bit_cast(f16x8, u32x4e{l0, l1, l2, l3});
+    split4_f16(x0, x1, x2, x3, h0, h1, l0, l1, amax);
+    split4_f16(x4, x5, x6, x7, h2, h3, l2, l3, amax);
+    ph = __builtin_bit_cast(f16x8, u32x4{h0, h1, h2, h3});
+    pl = __builtin_bit_cast(f16x8, u32x4{l0, l1, l2, l3});
 }
 
 template <int DH>
@@ -275,7 +253,7 @@ __global__ void __launch_bounds__(256, 2) enc_attention_f16_kernel(const float* 
             const int idx = threadIdx.x + 256 * k;
             const int which = idx / 640, rem = idx % 640, r = rem / 20, c4 = rem % 20;   // key r of the tile, channels 4 c4 .. + 3
             unsigned h0, h1, l0, l1;
-            enc_split4(st[k].x, st[k].y, st[k].z, st[k].w, h0, h1, l0, l1, amax);
+            split4_f16(st[k].x, st[k].y, st[k].z, st[k].w, h0, h1, l0, l1, amax);
             if (!which) {
                 // K: fragment (k-step ch / 16, lane (key r, half (ch % 16) / 8)), elements ch % 8 .. + 3: one 8-byte store per plane
                 const int ch = 4 * c4, ks = ch >> 4, hh = (ch >> 3) & 1, e = ch & 7;
@@ -341,9 +319,9 @@ __global__ void __launch_bounds__(256, 2) enc_attention_f16_kernel(const float* 
         for (int ks = 0; ks < KSQ; ++ks) {
             const f16x8 kh = s_kf[cur][(ks * 2 + 0) * 64 + lane], kl = s_kf[cur][(ks * 2 + 1) * 64 + lane];
             f32x16& acc = (ks & 1) ? S1 : S;
-            acc = mfma16(kl, qh[ks], acc);
-            acc = mfma16(kh, ql[ks], acc);
-            acc = mfma16(kh, qh[ks], acc);
+            acc = mfma_f16(kl, qh[ks], acc);
+            acc = mfma_f16(kh, ql[ks], acc);
+            acc = mfma_f16(kh, qh[ks], acc);
         }
         float tmax = -INFINITY;
 #pragma unroll
@@ -381,9 +359,9 @@ __global__ void __launch_bounds__(256, 2) enc_attention_f16_kernel(const float* 
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const f16x8 vh = s_vf[cur][((t * 2 + u) * 2 + 0) * 64 + lane], vl = s_vf[cur][((t * 2 + u) * 2 + 1) * 64 + lane];
-                o = mfma16(vl, ph[u], o);
-                o = mfma16(vh, pl[u], o);
-                o = mfma16(vh, ph[u], o);
+                o = mfma_f16(vl, ph[u], o);
+                o = mfma_f16(vh, pl[u], o);
+                o = mfma_f16(vh, ph[u], o);
             }
             O[t] = o;
         }

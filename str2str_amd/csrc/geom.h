@@ -20,6 +20,12 @@ template <typename T> struct Quat { T w, x, y, z; };
 template <typename T> struct Vec3 { T x, y, z; };
 template <typename T> struct Mat3 { T m[3][3]; };
 
+// a rigid frame stored as 7 floats: quaternion (w, x, y, z), translation
+__device__ __forceinline__ void load7(const float* __restrict__ p, Quat<float>& q, Vec3<float>& t) {
+    q.w = p[0]; q.x = p[1]; q.y = p[2]; q.z = p[3];
+    t.x = p[4]; t.y = p[5]; t.z = p[6];
+}
+
 template <typename T> __device__ __forceinline__ T t_sqrt(T x);
 template <> __device__ __forceinline__ float t_sqrt<float>(float x) { return sqrtf(x); }
 template <> __device__ __forceinline__ double t_sqrt<double>(double x) { return sqrt(x); }

@@ -30,27 +30,22 @@
 //   [ o (H*C) | o_pt.x (H*Pv) | o_pt.y | o_pt.z | |o_pt| (H*Pv) | o_pair (H*PZ) ]
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
 
+#include "f16x3.h"
 #include "str2str_hip.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ f32x16 mfma_b16(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ int rowmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // LDS read pointers made opaque at the point of use: hipcc otherwise hoists every LDS read of a key tile (all 16 rows of
 // key points, all K fragments) to the top of the loop body -- there is no store in between that it can see -- and the
 // 400+ live values push the accumulators out to scratch.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const float lds_cf;
 typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
 __device__ __forceinline__ lds_cf* lds_pin(const float* p) {
@@ -88,14 +83,6 @@ __device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
     // 16 B per lane, destination = wave-uniform base + lane*16 (LDS-DMA semantics)
     __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)lds_wave_base, 16, 0, 0);
 }
-
-// Timeline probe (tools/ipa_probe.py; only in -DS2S_IPA_PROBE=<block> builds)
-#ifdef S2S_IPA_PROBE
-__device__ unsigned long long s2s_ipa_probe[4][128];
-#define IPROBE(idx) do { if (blockIdx.x == S2S_IPA_PROBE) s2s_ipa_probe[threadIdx.x >> 6][idx] = __builtin_readcyclecounter(); } while (0)
-#else
-#define IPROBE(idx) do { } while (0)
-#endif
 
 template <int C, int PQ>
 struct KeyStage {
@@ -166,16 +153,9 @@ __global__ void __launch_bounds__(256) ipa_attention_kernel(IpaArgs a) {
     load_tile(stage[0], 0);
 
     // ---- this lane's query row (B operand of QK^T), points and mask
-    // half of the query row lives in registers; the other half is re-read (L1/L2 hits) through a small
-    // ring every key tile: 64 fewer live VGPRs is what keeps this kernel out of scratch
-#ifndef S2S_IPA_QR
-#define S2S_IPA_QR 0
-#endif
-    constexpr int QR = S2S_IPA_QR == 0 ? 0 : QG / S2S_IPA_QR;
+    // the query row is not held in registers: it is re-read (L1/L2 hits) through a small ring every key tile,
+    // and the live VGPRs it saves are what keep this kernel out of scratch
     const float* qrow = a.q + (row_i * H + head) * C + 4 * h;
-    float4 qreg[QR > 0 ? QR : 1];
-#pragma unroll
-    for (int g = 0; g < QR; ++g) qreg[g] = *reinterpret_cast<const float4*>(qrow + 8 * g);
     float qpt[PQ * 3];
     {
         const float* p = a.q_pts + (row_i * H + head) * (PQ * 3);
@@ -200,7 +180,6 @@ __global__ void __launch_bounds__(256) ipa_attention_kernel(IpaArgs a) {
     int cur = 0;
     for (int j0 = 0; j0 < N; j0 += 32, cur ^= 1) {
         const Stage& st = stage[cur];
-        IPROBE(8 * (j0 >> 5) + 0);
         // this lane's 16 bias values (keys j0 + 8g + 4h + e): one 128 B line per (query, tile), issued a whole
         // QK^T loop ahead of their use
         float4 bias4[4];
@@ -233,7 +212,7 @@ __global__ void __launch_bounds__(256) ipa_attention_kernel(IpaArgs a) {
         constexpr int QD = 4;
         float4 qring[QD];
 #pragma unroll
-        for (int d = 0; d < QD; ++d) qring[d] = *reinterpret_cast<const float4*>(qrow + 8 * (QR + d));
+        for (int d = 0; d < QD; ++d) qring[d] = *reinterpret_cast<const float4*>(qrow + 8 * d);
         float4 kf_next = lds_ld4(lds_pin(st.k + c * KS + 4 * h));
         float4 kpv[PQ * 3 / 4];  // key points of the key row whose distance term is evaluated next
         {
@@ -246,13 +225,8 @@ __global__ void __launch_bounds__(256) ipa_attention_kernel(IpaArgs a) {
         for (int g = 0; g < QG; ++g) {
             const float4 kf = kf_next;
             if (g + 1 < QG) kf_next = lds_ld4(lds_pin(st.k + c * KS + 8 * (g + 1) + 4 * h));
-            float4 qf;
-            if (g < QR) {
-                qf = qreg[g];
-            } else {
-                qf = qring[(g - QR) % QD];
-                if (g + QD < QG) qring[(g - QR) % QD] = *reinterpret_cast<const float4*>(qrow + 8 * (g + QD));
-            }
+            const float4 qf = qring[g % QD];
+            if (g + QD < QG) qring[g % QD] = *reinterpret_cast<const float4*>(qrow + 8 * (g + QD));
             S = mfma32(kf.x, qf.x, S);
             S1 = mfma32(kf.y, qf.y, S1);
             S = mfma32(kf.z, qf.z, S);
@@ -279,12 +253,10 @@ __global__ void __launch_bounds__(256) ipa_attention_kernel(IpaArgs a) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        IPROBE(8 * (j0 >> 5) + 1);
         // VMEM loads return in order: the next tile's DMA is issued only now, behind the last load of this tile (bias, Q
         // ring), so that nothing consumed during this tile has to wait for 77 KB of DMA; it lands under softmax + PV,
         // which touch no global memory loads (and must stay free of scratch reloads for the same reason).
         if (j0 + 32 < N) load_tile(stage[cur ^ 1], j0 + 32);
-        IPROBE(8 * (j0 >> 5) + 2);
         // ---------------- logits (ipa.py:183-214)
         float tmax = -INFINITY;
 #pragma unroll
@@ -301,7 +273,6 @@ __global__ void __launch_bounds__(256) ipa_attention_kernel(IpaArgs a) {
             tmax = fmaxf(tmax, s);
         }
         __builtin_amdgcn_sched_barrier(0);
-        IPROBE(64 + 4 * (j0 >> 5) + 0);
         if (ivalid) {
             if (full_tile) {
 #pragma unroll
@@ -314,7 +285,6 @@ __global__ void __launch_bounds__(256) ipa_attention_kernel(IpaArgs a) {
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        IPROBE(64 + 4 * (j0 >> 5) + 1);
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
         const float m_new = fmaxf(m_run, tmax);
         const float alpha = expf(m_run - m_new);  // 0 on the first tile, 1 once the maximum has settled
@@ -328,9 +298,6 @@ __global__ void __launch_bounds__(256) ipa_attention_kernel(IpaArgs a) {
         }
         l_run = l_run * alpha + psum;
         __builtin_amdgcn_sched_barrier(0);
-        IPROBE(64 + 4 * (j0 >> 5) + 2);
-
-        IPROBE(8 * (j0 >> 5) + 3);
         // ---------------- O^T += V^T . P^T (+ value points)  (ipa.py:221-252), one output tile at a time; the A operands of
         // tile t+1 are fetched from LDS and split, and its accumulator is rescaled by alpha (16 VALU multiplies,
         // unconditionally: a wave-uniform branch around them brought scratch spills back and ran 10 % slower) while the
@@ -392,14 +359,9 @@ __global__ void __launch_bounds__(256) ipa_attention_kernel(IpaArgs a) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        IPROBE(8 * (j0 >> 5) + 4);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // next tile's DMA has landed
-        IPROBE(8 * (j0 >> 5) + 5);
         __syncthreads();                                   // ... and everyone is done reading this one
-        IPROBE(8 * (j0 >> 5) + 6);
     }
-
-    IPROBE(120);
     // ---------------- epilogue: normalise, inverse-transform points, write concat layout
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
@@ -455,7 +417,6 @@ __global__ void __launch_bounds__(256) ipa_attention_kernel(IpaArgs a) {
                 }
             }
     }
-    IPROBE(121);
     if (ivalid && h == 0) {
         float* st2 = a.stats + ((((long long)b * H + head) * N) + i) * 2;
         st2[0] = m_run;
@@ -550,12 +511,6 @@ __global__ void __launch_bounds__(256) ipa_opair_kernel(const float* __restrict_
 
 }  // namespace
 
-#ifdef S2S_IPA_PROBE
-extern "C" int s2s_debug_read_ipa_probe(void* dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(s2s_ipa_probe), sizeof(s2s_ipa_probe));
-}
-#endif
-
 extern "C" int s2s_ipa_opair(const float* logits, const float* stats, const float* pair_z, float* out, int n_samples, int n_res,
                              int n_heads, int c_pair_z, int out_row_stride, int out_col_offset, int logits_ld, void* stream) {
     if (n_samples <= 0 || n_res <= 0) return 0;
@@ -576,9 +531,8 @@ extern "C" int s2s_ipa_attention(const float* q, const float* kv, const float* q
         return (int)hipErrorInvalidValue;  // the reference configuration (configs/model/diffusion.yaml:29-40)
     const int n_qb = (n_res + 127) / 128;
     const long long blocks = (long long)n_samples * n_heads * n_qb;
-    static const int remap_env = getenv("S2S_IPA_XCD") ? atoi(getenv("S2S_IPA_XCD")) : 1;
     IpaArgs a{q, kv, q_pts, k_pts, v_pts64, attn_bias, logits_out, stats_out, mask, rigids7, head_w_scaled, out, n_samples, n_res, n_heads, inf, eps,
-              (remap_env && blocks % 8 == 0 && n_qb > 1) ? 1 : 0};
+              (blocks % 8 == 0 && n_qb > 1) ? 1 : 0};
     if (n_res % 32 == 0)
         hipLaunchKernelGGL((ipa_attention_kernel<256, 8, 12, 32, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     else

@@ -22,10 +22,10 @@
 // linear_out's input (the accumulator registers ARE its fragments).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
+#include "f16x3.h"
 #include "geom.h"
 #include "range_flag.h"
 #include "str2str_hip.h"
@@ -33,18 +33,6 @@
 namespace {
 
 using namespace s2s;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));   // a 16 B fragment
-
-__device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int rowmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-__device__ __forceinline__ void load7(const float* __restrict__ p, Quat<float>& q, Vec3<float>& t) {
-    q.w = p[0]; q.x = p[1]; q.y = p[2]; q.z = p[3];
-    t.x = p[4]; t.y = p[5]; t.z = p[6];
-}
 
 // e^x for x <= ~0 in 6 VALU instructions: v_exp_f32 (2^t, 1 ulp) on t = fl(x log2 e), corrected to first order for the rounding
 // of the product and of the constant (exact residual by FMA), so the argument error does not grow with |x|.  Relative error
@@ -58,27 +46,9 @@ __device__ __forceinline__ float exp_neg(float x) {
     return __builtin_fmaf(r, e * LN2, r);
 }
 
-// two values -> element pair `at / 2` of the planes (x_h = rn16(x), x_l = rn16(x - x_h)) in 3 instructions: v_cvt_pk_f16_f32 for both
-// x_h, then ONE fused multiply-add per value that reads x_h as f16 and rounds to f16 -- (-x_h) * 1.0 + x, whose exact fp32 result is
-// the difference -- the bits of convert back, subtract, convert (pair_mlp_f16.hip split2_f16; hipcc's expansion of the C form: 5 per value)
-typedef unsigned u32x4p __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split2(float x0, float x1, f16x8& ph, f16x8& pl, int at) {
-    unsigned hh, ll;
-    asm volatile(
-        "v_cvt_pk_f16_f32 %0, %2, %3\n\t"
-        "v_fma_mixlo_f16 %1, -%0, 1.0, %2 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %1, -%0, 1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(hh), "=&v"(ll)
-        : "v"(x0), "v"(x1));
-    u32x4p hv = __builtin_bit_cast(u32x4p, ph), lv = __builtin_bit_cast(u32x4p, pl);
-    hv[at / 2] = hh;
-    lv[at / 2] = ll;
-    ph = __builtin_bit_cast(f16x8, hv);
-    pl = __builtin_bit_cast(f16x8, lv);
-}
 __device__ __forceinline__ void split8(const float* v, f16x8& ph, f16x8& pl) {   // x_h, x_l
 #pragma unroll
-    for (int j = 0; j < 8; j += 2) split2(v[j], v[j + 1], ph, pl, j);
+    for (int j = 0; j < 8; j += 2) split2_f16(v[j], v[j + 1], ph, pl, j);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -236,14 +206,6 @@ __device__ __forceinline__ lds_frag* frag_pin(const f16x8* p) {
     return q;
 }
 
-// Timeline probe (tools/ipa_f16w_probe.py; only in -DS2S_IPA_PROBE=<block> builds)
-#ifdef S2S_IPA_PROBE
-__device__ unsigned long long s2s_ipa8_probe[4][128];
-#define IPROBE(idx) do { if (blockIdx.x == S2S_IPA_PROBE) s2s_ipa8_probe[threadIdx.x >> 6][idx] = __builtin_readcyclecounter(); } while (0)
-#else
-#define IPROBE(idx) do { } while (0)
-#endif
-
 constexpr int KQ = 18;   // k-steps of QK^T: 16 channels + 2 point coordinates
 constexpr int KH = KQ;       // every wave runs the whole contraction
 constexpr int OT = 10;   // output tiles of PV: 8 channels + 2 value points
@@ -276,13 +238,11 @@ struct PlaneStage {
     __attribute__((aligned(16))) float km[4][32];
 };
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // 16 B load that bypasses the (non-coherent) vector L1 (cache policy sc0 | sc1): the logits were stored by the partner wave, to
 // lines this CU read as attention bias a moment ago.
-__device__ __forceinline__ f32x4v load_l2(__amdgpu_buffer_rsrc_t rsrc, int byte_offset) {
+__device__ __forceinline__ f32x4 load_l2(__amdgpu_buffer_rsrc_t rsrc, int byte_offset) {
     const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_offset, 0, 17);
-    return __builtin_bit_cast(f32x4v, r);
+    return __builtin_bit_cast(f32x4, r);
 }
 
 // RAGGED (n_res % 32 != 0): operands arrive in the padded layout (NP = n_res rounded up to 32 rows per sample; padded key rows are
@@ -394,7 +354,6 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
     float sm_val;
 
     // ---- cold start: image 0 straight into LDS, image 1 into the staging registers
-    IPROBE(126);
 #pragma unroll
     for (int p = 0; p < 9; ++p)
         __builtin_amdgcn_global_load_lds((gbl_ptr_t)(piece_src(0, p) + lane), (lds_ptr_t)piece_dst(0, p), 16, 0, 0);
@@ -405,7 +364,6 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
     sm_val = small_load(cur, 2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    IPROBE(127);
 
     // ---- per-item state of a lane; the query fragments, scalars and the first bias tile of the NEXT item are fetched before the
     // epilogue of the current one (the registers are free there and the epilogue covers the HBM latency)
@@ -456,14 +414,7 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
     LaneItem Lc = lane_item(cur);
     load_queries(cur, Lc);
     float sm_n0, sm_n1, sm_n2;   // the next item's per-key scalars of tiles 0 .. 2
-#ifdef S2S_IPA_PROBE
-    int probe_item = 0;
-#endif
     for (;;) {
-#ifdef S2S_IPA_PROBE
-    if (probe_item < 16) IPROBE(100 + probe_item);
-    ++probe_item;
-#endif
     const int b = cur.b, head = cur.head;
     const long long rt_q = Lc.rt_q, row_i = Lc.row_i, brow0 = Lc.brow0;
     const int i = Lc.i;
@@ -477,7 +428,7 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
     const __amdgpu_buffer_rsrc_t lrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.logits + ((long long)b * H + head) * NP * NP), 0,
                                                                            NP * NP * 4, 0x00020000);
     const int loff0 = (i * NP + 4 * h) * 4;
-    f32x4v lg[4], lg1[4];   // logits of the tile whose probabilities are formed next (and of tile 1 across the phase change)
+    f32x4 lg[4], lg1[4];   // logits of the tile whose probabilities are formed next (and of tile 1 across the phase change)
     float tmax = -INFINITY;
     float4 k2g, kmg;   // per-key scalars of the 4 keys 8g + 4h .. of the element group being evaluated
     auto logit_elem = [&](int tp, int r, const float4 (&xa)[4], float (&sl)[16]) {
@@ -509,7 +460,6 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
     auto step1 = [&](int t, auto have_c, auto prev_c, auto flush_c) {
         constexpr bool have = decltype(have_c)::value, prev = decltype(prev_c)::value, flush = decltype(flush_c)::value;
         const int par = t & 1;
-        IPROBE(6 * t + 0);
         // S^T of tile t-1
         float4 xa[4];
         if constexpr (prev) {
@@ -555,7 +505,6 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
                 stage_slot(t + 1, 2 * x + 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            IPROBE(6 * t + 1);
 #pragma unroll
             for (int g = 0; g < 4; ++g)   // kept in registers for the next step's logit arithmetic (no exchange between waves here)
                 xkeep[g] = make_float4(S0[4 * g] + S1[4 * g], S0[4 * g + 1] + S1[4 * g + 1],
@@ -576,11 +525,8 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ... and they must have reached L2 before phase 2 reads them back
         }
         if constexpr (flush) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // logits stored so far have reached L2
-        IPROBE(6 * t + 2);
         __syncthreads();                                   // partial sums and image t + 1 visible; buffer t & 1 released
-        IPROBE(6 * t + 3);
         if constexpr (have) { small_store(t + 2, sm_val); sm_val = small_load(cur, t + 3); }
-        IPROBE(6 * t + 4);
     };
     step1(0, std::true_type{}, std::false_type{}, std::false_type{});
     for (int t = 1; t + 1 < NT; ++t) step1(t, std::true_type{}, std::true_type{}, std::false_type{});
@@ -588,7 +534,6 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
     step1(NT, std::false_type{}, std::true_type{}, std::false_type{});
     m_run = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
     // images NT (= V(0)) and NT + 1 are in flight; the last tile's logits have reached L2 (vmcnt(0) + barrier above)
-    IPROBE(120);
 
     // =========================================================== phase 2: probabilities and value aggregation
     // Software pipeline again: exp + split of tile t+1 between the MFMAs of tile t.
@@ -630,9 +575,7 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
     for (int g = 0; g < 4; ++g) lg[g] = lg1[g];
     auto step2 = [&](int t, auto more_c, auto first_c) {
         constexpr bool more = decltype(more_c)::value, first = decltype(first_c)::value;
-        IPROBE(60 + 6 * t + 0);
         if constexpr (!first) __syncthreads();               // V(t) visible; every wave is done with V(t - 1)
-        IPROBE(60 + 6 * t + 1);
         // ---------------- O^T += V^T . P^T for this wave's five output tiles
         const f16x8* v_half = st.img[(NT + t) & 1] + lane;
         auto load_v = [&](int x, f16x8 (&d)[2][2]) {
@@ -653,7 +596,7 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
         // tile t + 2 requested in group 16 (lg is dead by then); the next tile group's fragments are requested in this one's first groups.
         auto split_pair = [&](auto jc) {   // elements 2j, 2j+1 of 2^10 pe -> element pair (j & 3) of the planes of k-step j >> 2
             constexpr int j = decltype(jc)::value;
-            split2(pe[2 * j] * 1024.0f, pe[2 * j + 1] * 1024.0f, pn[j >> 2][0], pn[j >> 2][1], 2 * (j & 3));
+            split2_f16(pe[2 * j] * 1024.0f, pe[2 * j + 1] * 1024.0f, pn[j >> 2][0], pn[j >> 2][1], 2 * (j & 3));
             asm volatile("" : "+v"(pn[j >> 2][0]), "+v"(pn[j >> 2][1]) :: "memory");   // done here, not at the loop tail
         };
         auto ride = [&](auto gc) {
@@ -704,9 +647,7 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
                 for (int p = 0; p < 2; ++p) pc[u][p] = pn[u][p];
         }
         __builtin_amdgcn_sched_barrier(0);
-        IPROBE(60 + 6 * t + 3);
     };
-    IPROBE(123);
     if (NT > 1) {
         step2(0, std::true_type{}, std::true_type{});
         for (int t = 1; t + 1 < NT; ++t) step2(t, std::true_type{}, std::false_type{});
@@ -714,7 +655,6 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
     } else {
         step2(0, std::false_type{}, std::true_type{});
     }
-    IPROBE(121);
 
     // ---------------- the next item's query side (unconditionally: after the last item nxt == cur and the values are unused)
     const bool last = item + (int)gridDim.x >= n_items;
@@ -783,7 +723,6 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
         st2[0] = m_run;
         st2[1] = l_tot;
     }
-    IPROBE(122);
 
     // ---------------- next item: its image 0 is already in buffer 0, its image 1 in the staging registers
     item += (int)gridDim.x;
@@ -1001,12 +940,6 @@ __global__ void __launch_bounds__(256, 1) ipa_attention_short_kernel(PlaneArgs a
 
 }  // namespace
 
-#ifdef S2S_IPA_PROBE
-extern "C" int s2s_debug_read_ipa8_probe(void* dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(s2s_ipa8_probe), sizeof(s2s_ipa8_probe));
-}
-#endif
-
 extern "C" int s2s_ipa_prep_points_f16(const float* rigids7, const float* q_pts_lin, const float* kv_pts_lin,
                                           const float* head_w_scaled, void* qp_xp, void* kp_xp, void* vp_vf, float* q2, float* k2,
                                           int n_samples, int n_res, int n_heads, int n_qk_points, int n_v_points, int c_hidden,
@@ -1042,7 +975,6 @@ extern "C" int s2s_ipa_attention_f16w(const void* q_xp, const void* k_xp, const 
     // the kernel addresses its fragment arrays (and, for ragged lengths, the bias array) through 32-bit buffer offsets
     if ((long long)n_samples * (n_pad / 32) * 16 * n_heads * 2048 >= (1ll << 32)) return (int)hipErrorInvalidValue;
     if (ragged && (long long)n_samples * n_heads * n_res * n_res * 4 >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    static const int remap_env = getenv("S2S_IPA_XCD") ? atoi(getenv("S2S_IPA_XCD")) : 1;
     // persistent workgroups, one per CU (83 KiB of LDS each); a multiple of 8 so that workgroup w stays on XCD w % 8
     static int n_cu = 0;
     if (!n_cu) {
@@ -1054,9 +986,8 @@ extern "C" int s2s_ipa_attention_f16w(const void* q_xp, const void* k_xp, const 
     const long long blocks = items < n_cu ? items : n_cu;
     PlaneArgs a{(const f16x8*)q_xp, (const f16x8*)k_xp, (const f16x8*)v_vf, (const f16x8*)qp_xp, (const f16x8*)kp_xp,
                 (const f16x8*)vp_vf, q2, k2, attn_bias, logits_out, stats_out, mask, rigids7, out, (f16x8*)out_xp, out_xp_ksteps,
-                n_samples, n_res, n_heads, n_pad, inf, eps, (remap_env && items % 8 == 0 && blocks % 8 == 0 && n_qb > 1) ? 1 : 0, n_kv_heads};
-    static const int short_env = getenv("S2S_IPA_SHORT") ? atoi(getenv("S2S_IPA_SHORT")) : 1;
-    if (short_env && n_kv_heads == 1 && n_heads % 4 == 0 && n_pad <= 64) {   // one wave per (sample, head, query tile): see the short kernel
+                n_samples, n_res, n_heads, n_pad, inf, eps, (items % 8 == 0 && blocks % 8 == 0 && n_qb > 1) ? 1 : 0, n_kv_heads};
+    if (n_kv_heads == 1 && n_heads % 4 == 0 && n_pad <= 64) {   // one wave per (sample, head, query tile): see the short kernel
         const int nt = n_pad / 32;
         const long long wgs = (long long)n_samples * nt * (n_heads / 4);
         if (wgs < (1ll << 31)) {

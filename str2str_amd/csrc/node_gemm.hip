@@ -31,6 +31,7 @@
 
 #include <cstdlib>
 
+#include "f16x3.h"
 #include "range_flag.h"
 #include "str2str_hip.h"
 
@@ -38,47 +39,14 @@ namespace {
 
 using s2s::range_max;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32, 64); }
-
-constexpr float kInvWS = 1.0f / 32.0f;   // weights are packed as the split of 2^5 w: accumulators carry 32 x the output
-
-// planes of the node stream: (x_h, x_l), see the header.  8 values -> the two 16 B plane fragments, 64 fragments apart, and into the
-// caller's range maximum.  The split as in csrc/pair_mlp_f16.hip (split4_f16): x_h = rn16(x) two per v_cvt_pk_f16_f32, x_l = rn16(x - x_h)
-// as ONE v_fma_mixlo / mixhi_f16 that reads x_h as f16 ((-x_h) * 1.0 + x is exact in fp32), the maximum as v_max3_f32 with |.| -- 2
-// instructions per value; hipcc's expansion of the C expressions is 6 (convert, convert back, subtract, convert, pack, max), and this
-// epilogue is what the K = 256 layers spend most of their time in.  One opaque block per 4 values: both planes come from the same
-// materialised fp32 value (with fp contraction the compiler otherwise derives x_h and x_l from DIFFERENT fused forms of the producing
-// expression, and near an f16 rounding tie the pair then misses x by a whole f16 ulp).
+// planes of the node stream: (x_h, x_l), see the header.  8 values -> the two 16 B plane fragments, and into the caller's range
+// maximum, as two blocks of the split of f16x3.h (this epilogue is what the K = 256 layers spend most of their time in)
 __device__ __forceinline__ void split8_f16(const float* v, f16x8& ph, f16x8& pl, float& amax) {
-    typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-    u32x4s hv, lv;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        unsigned h0, h1, l0, l1;
-        asm volatile(
-            "v_max3_f32 %4, %4, |%5|, |%6|\n\t"
-            "v_cvt_pk_f16_f32 %0, %5, %6\n\t"
-            "v_max3_f32 %4, %4, |%7|, |%8|\n\t"
-            "v_cvt_pk_f16_f32 %1, %7, %8\n\t"
-            "v_fma_mixlo_f16 %2, -%0, 1.0, %5 op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mixlo_f16 %3, -%1, 1.0, %7 op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mixhi_f16 %2, -%0, 1.0, %6 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mixhi_f16 %3, -%1, 1.0, %8 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-            : "=&v"(h0), "=&v"(h1), "=&v"(l0), "=&v"(l1), "+v"(amax)
-            : "v"(v[4 * q]), "v"(v[4 * q + 1]), "v"(v[4 * q + 2]), "v"(v[4 * q + 3]));
-        hv[2 * q] = h0; hv[2 * q + 1] = h1;
-        lv[2 * q] = l0; lv[2 * q + 1] = l1;
-    }
-    ph = __builtin_bit_cast(f16x8, hv);
-    pl = __builtin_bit_cast(f16x8, lv);
+    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+    split4_f16(v[0], v[1], v[2], v[3], h0, h1, l0, l1, amax);
+    split4_f16(v[4], v[5], v[6], v[7], h2, h3, l2, l3, amax);
+    ph = __builtin_bit_cast(f16x8, u32x4{h0, h1, h2, h3});
+    pl = __builtin_bit_cast(f16x8, u32x4{l0, l1, l2, l3});
 }
 __device__ __forceinline__ void store_planes(f16x8* q, const float* v, float& amax) {
     f16x8 ph, pl;
@@ -129,7 +97,7 @@ __device__ __forceinline__ void node_epilogue(f32x16 (&acc)[TG], const GemmArgs&
     // The per-column / per-row operands of a tile are requested ONE TILE AHEAD of their use.  Written the obvious way (`if (a.bias)
     // load` inside the loop) every one of the 32 (tile, quarter) iterations was load, s_waitcnt vmcnt(0), use -- and at 256
     // registers the compiler serialises even unconditional loads through one temporary: up to 64 exposed L2 round trips, more time
-    // than the whole k loop of the K = 256 layers (tools/node_gemm_probe.py).  Absent operands read a block of zeros.
+    // than the whole k loop of the K = 256 layers (profiles/r03f_node_gemm_probe.txt).  Absent operands read a block of zeros.
     const float* bias_p = a.bias ? a.bias + col_base + 4 * h : s2s_zero + 4 * h;
     const float* res_p = a.residual ? a.residual + rowc * a.res_ld + col_base + 4 * h : s2s_zero + 4 * h;
     float4 qb[2][4], qr[2][4];
@@ -230,9 +198,6 @@ __device__ __forceinline__ void node_epilogue(f32x16 (&acc)[TG], const GemmArgs&
 // are then exactly the A fragment (k-step u) of a later  Z^T[col, i] += Y^T[col, row] P^T[row, i]  product over the rows, i.e. of
 // the attention's PV step with rows = keys (csrc/ipa_attention.hip).  The epilogue adds the bias, splits and stores them as
 //   out_vf[row tile][head][column tile in head][k-step u][plane 2][lane 64][8]   (f16 pairs; 1 KiB per (u, plane), lane-linear)
-#ifdef S2S_NODE_PROBE
-__device__ unsigned long long g_node_probe[8];
-#endif
 // (the body of one workgroup, as a device function: one launch can carry several independent layers -- node_gemm_multi_kernel below)
 template <int TG, int WAVES, bool VF>
 __device__ __forceinline__ void node_gemm_body(const GemmArgs& a, const int bx, const int by) {
@@ -243,10 +208,6 @@ __device__ __forceinline__ void node_gemm_body(const GemmArgs& a, const int bx, 
     constexpr int kStage = 2 * TG * 1024;
     constexpr int kFrags = 2 * TG;                          // 1 KiB pieces per stage
     constexpr int kPieces = (kFrags + WAVES - 1) / WAVES;   // per wave
-#ifdef S2S_NODE_PROBE
-    unsigned long long probe_t0;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(probe_t0)::"memory");
-#endif
     extern __shared__ __attribute__((aligned(16))) char s_w[];  // 2 stages
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // provably wave-uniform: scalar branches below
@@ -342,86 +303,20 @@ __device__ __forceinline__ void node_gemm_body(const GemmArgs& a, const int bx, 
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
     // k-steps in pairs (buffer parity is static: KS is even); loads past the end of the stream are clamped and never consumed
-#ifndef S2S_NODE_XDEPTH
-#define S2S_NODE_XDEPTH 1
-#endif
-#if S2S_NODE_XDEPTH == 2
-    // Both operand streams TWO k-steps ahead (-DS2S_NODE_XDEPTH=2; NOT the default): a second weight staging set (wst2: k-step
-    // ks + 2 is requested while ks + 1 still waits in the first) and a third activation fragment pair.  Measured in round 4 at
-    // M = 2240 / 5120 / 32768 rows (profiles/r04_node_gemm_small_m.txt): no change for the 8-tile layers at any M -- a [5120 x 256] x
-    // [256 x 256] layer takes 18.5 us either way, of which the k loop is the smaller part: the epilogue's 64 stores per wave go
-    // through a CU store path that moves ~1 KiB per 44-59 cycles (tools/ubench/store_rate.hip) -- and slower for the 10-tile layers
-    // (the 16 extra registers cost the second workgroup per CU).
-    f16x8 xc[2];
-    f32x4 wst2[kPieces];
-    auto w_load2 = [&](int ks) {
-        ks = ks < KS ? ks : KS - 1;
-        const char* src = wsrc + (long long)ks * kStage;
-#pragma unroll
-        for (int k = 0; k < kPieces; ++k) {
-            if (WAVES * k + WAVES - 1 < kFrags || WAVES * k + wave < kFrags)
-                wst2[k] = *reinterpret_cast<const f32x4*>(src + (WAVES * k + wave) * 1024);
-        }
-    };
-    auto w_store2 = [&](int par) {
-        lds_char* dst = (lds_char*)s_w + par * kStage + lane * 16;
-#pragma unroll
-        for (int k = 0; k < kPieces; ++k) {
-            if (WAVES * k + WAVES - 1 < kFrags || WAVES * k + wave < kFrags) *(lds_f4*)(dst + (WAVES * k + wave) * 1024) = wst2[k];
-        }
-    };
-    // on entry: LDS 0 = k-step 0, wst = k-step 1 (prologue above); now wst2 = k-step 2
-    w_load2(2);
-    x_load(1, xb);
-    for (int ks = 0; ks < KS; ks += 2) {
-        x_load(ks + 2, xc);
-        compute(0, xa);
-        w_store(1);                 // k-step ks + 1, requested two k-steps ago
-        w_load(ks + 3);
-        __syncthreads();
-        x_load(ks + 3, xa);
-        compute(1, xb);
-        w_store2(0);                // k-step ks + 2
-        w_load2(ks + 4);
-        __syncthreads();
-        // rotate: (xa, xb) <- (k-step ks + 2, ks + 3)
-#pragma unroll
-        for (int p = 0; p < 2; ++p) { const f16x8 t = xa[p]; xa[p] = xc[p]; xb[p] = t; }
-    }
-#else
-#ifdef S2S_NODE_PROBE
-    // phase probe (tools/node_gemm_probe.py): s_memtime at the kernel's start, before / after the k loop and, inside it, around compute,
-    // the weight copy and the barrier of the even k-steps; wave 0 of every workgroup, sums per launch in g_node_probe
-    unsigned long long p_loop, p_a = 0, p_b = 0, p_c = 0, p_d = 0, acc_cmp = 0, acc_cp = 0, acc_bar = 0;
-#define NP(x) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(x)::"memory")
-    NP(p_loop);
-#else
-#define NP(x)
-#endif
+    // (both operand streams two k-steps ahead: no faster for the 8-tile layers, slower for the 10-tile ones whose extra registers
+    //  cost the second workgroup per CU; profiles/r04_node_gemm_small_m.txt)
     for (int ks = 0; ks < KS; ks += 2) {
         x_load(ks + 1, xb);
-        NP(p_a);
         compute(0, xa);
-        NP(p_b);
         w_store(1);                 // k-step ks + 1 (loaded one stage ago) -> buffer 1 (last read two barriers ago)
         w_load(ks + 2);
-        NP(p_c);
         __syncthreads();
-        NP(p_d);
-#ifdef S2S_NODE_PROBE
-        acc_cmp += p_b - p_a; acc_cp += p_c - p_b; acc_bar += p_d - p_c;
-#endif
         x_load(ks + 2, xa);
         compute(1, xb);
         w_store(0);
         w_load(ks + 3);
         __syncthreads();
     }
-#ifdef S2S_NODE_PROBE
-    unsigned long long p_end;
-    NP(p_end);
-#endif
-#endif
 
     float amax = 0.f;   // range guard: largest magnitude written as planes
     if constexpr (VF) {
@@ -455,20 +350,6 @@ __device__ __forceinline__ void node_gemm_body(const GemmArgs& a, const int bx, 
         return;
     }
     node_epilogue<TG>(acc, a, rt, n_rt, lane, cb, ps);
-#ifdef S2S_NODE_PROBE
-    unsigned long long p_fin;
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(p_fin)::"memory");
-    if (threadIdx.x == 0) {
-        atomicAdd(&g_node_probe[0], p_loop - probe_t0);   // prologue
-        atomicAdd(&g_node_probe[1], acc_cmp);             // compute, even k-steps
-        atomicAdd(&g_node_probe[2], acc_cp);              // weight store + load issue
-        atomicAdd(&g_node_probe[3], acc_bar);             // barrier
-        atomicAdd(&g_node_probe[4], p_end - p_loop);      // whole k loop
-        atomicAdd(&g_node_probe[5], p_fin - p_end);       // epilogue incl. its stores
-        atomicAdd(&g_node_probe[6], 1ull);
-        atomicAdd(&g_node_probe[7], (unsigned long long)KS);
-    }
-#endif
 }
 
 template <int TG, int WAVES, bool VF>
@@ -534,14 +415,6 @@ struct ChainArgs {
     // the chain is then the whole post-attention half of the layer, ipa.py:312-317)
     const float* mid_ln_gamma; const float* mid_ln_beta; float mid_ln_eps;
 };
-template <int I> struct CI { static constexpr int value = I; };
-template <int B, int E, class F>
-__device__ __forceinline__ void chain_for(F&& f) {
-    if constexpr (B < E) {
-        f(CI<B>{});
-        chain_for<B + 1, E>(f);
-    }
-}
 
 template <int TG, int KS0>
 __global__ void __launch_bounds__(256, 1) node_chain_kernel(ChainArgs c) {
@@ -620,7 +493,7 @@ __global__ void __launch_bounds__(256, 1) node_chain_kernel(ChainArgs c) {
         for (int t = 0; t < TG; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-        chain_for<0, NK>([&](auto kc) {
+        static_for<0, NK>([&](auto kc) {
             constexpr int ks = decltype(kc)::value, par = ks & 1;
             compute(par, xr[ks]);
             if constexpr (ks + 1 < NK) {
@@ -660,10 +533,10 @@ __global__ void __launch_bounds__(256, 1) node_chain_kernel(ChainArgs c) {
                 split8_f16(v, xr[2 * t + u][0], xr[2 * t + u][1], amax);
             }
     };
-    run_layer(CI<KS0>{}, 0, c.n_layers == 1);
+    run_layer(IC<KS0>{}, 0, c.n_layers == 1);
     for (int l = 1; l < c.n_layers; ++l) {
         inner_epilogue(l - 1);
-        run_layer(CI<KS>{}, l, l == c.n_layers - 1);
+        run_layer(IC<KS>{}, l, l == c.n_layers - 1);
     }
     s2s::range_report(a.range_flag, amax, s2s::kRangeNodeGemm);
     GemmArgs fin = a;
@@ -960,16 +833,6 @@ extern "C" int s2s_node_linear_vfrag(const void* xp, const void* w_packed, const
     return launch_gemm_w<TG, 4, true>(a, (hipStream_t)stream);
 }
 
-#ifdef S2S_NODE_PROBE
-extern "C" int s2s_node_probe_read(unsigned long long* host_out, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_node_probe), sizeof(unsigned long long) * 8);
-    if (e == hipSuccess && reset) {
-        static unsigned long long z[8];
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_node_probe), z, sizeof(z));
-    }
-    return (int)e;
-}
-#endif
 
 // Up to six independent layers (bias / ReLU epilogues only) in ONE launch: see node_gemm_multi_kernel.
 extern "C" int s2s_node_chain(const void* xp, const s2s_chain_layer* layers, int n_layers, long long n_rows, int width, int k_in0,

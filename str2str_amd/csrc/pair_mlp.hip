@@ -23,20 +23,16 @@
 //     accumulator's initial value (491,520 FLOP/pair instead of 688,128).
 #include <hip/hip_runtime.h>
 
+#include "f16x3.h"
 #include "str2str_hip.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
-#ifndef S2S_PREFETCH
-#define S2S_PREFETCH 8
-#endif
-constexpr int kPrefetch = S2S_PREFETCH;  // weight fragments in flight per wave (x 1 KiB)
+constexpr int kPrefetch = 8;  // weight fragments in flight per wave (x 1 KiB)
 
 // acc[t] += Wpacked . B   for T output tiles and S4 step-groups (K = 8*S4 inputs).
 // bop(s4, q) returns this lane's B operand for step 4*s4+q (must be compile-time selectable).
@@ -95,14 +91,7 @@ __device__ __forceinline__ void mlp_layer_tiles(f32x16 (&acc)[T], const float4* 
     }
 }
 
-// this lane's 4 consecutive elements of group g of a B-layout vector
-__device__ __forceinline__ float4 ldg4(const float* __restrict__ base, int g, int h) {
-    return *reinterpret_cast<const float4*>(base + 8 * g + 4 * h);
-}
-
 __device__ __forceinline__ float f4(const float4& v, int q) { return q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w; }
-
-__device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32, 64); }
 
 // LayerNorm over the 32*T channels a pair owns (half in this lane, half in lane^32), gamma/beta,
 // optional scale, then float4 stores in B layout.

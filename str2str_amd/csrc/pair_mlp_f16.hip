@@ -26,9 +26,9 @@
 //                   (its first output tiles are complete early), every other B_t k-step major.
 //   order: A_0 A_1 | B_0 A_2 | B_1 A_3 | ... | B_9 A_11 | B_10 B_11 | final layer (48 slots, k-step major) [| projection, 8 slots].
 //   A slot = six MFMAs, each followed by at most one 1 KiB piece of the weight pipe and one small VALU piece, pinned there by
-//   sched_barrier (the slot body in the kernel has the table).  Found with the in-kernel probe (-DS2S_ET_PROBE, tools/
-//   et_phase_probe.py): a slot of bare MFMAs runs at the matrix pipe's 192 cycles; the four loads / four LDS stores of the weight
-//   pipe issued as a block cost 60 / 120 cycles, a 20-instruction VALU block behind one MFMA ~100.  So:
+//   sched_barrier (the slot body in the kernel has the table).  Found with an in-kernel timeline probe (profiles/
+//   r04a_et_phase_probe.txt): a slot of bare MFMAs runs at the matrix pipe's 192 cycles; the four loads / four LDS stores of the
+//   weight pipe issued as a block cost 60 / 120 cycles, a 20-instruction VALU block behind one MFMA ~100.  So:
 //     - the ReLU + per-node seeds + split of a1 tile t-1 runs in 2-value halves behind MFMAs 2 and 4 of the A_t slots;
 //     - the layer-2 epilogue (ReLU + residual + split = the final layer's input) runs in 4-value pieces: block 0 under the second
 //       half of B_11, block 1 under the final layer's k-steps 0..7 into a second plane buffer, block 2 under k-steps 8..15;
@@ -50,6 +50,7 @@
 
 #include <cstdlib>
 
+#include "f16x3.h"
 #include "range_flag.h"
 #include "str2str_hip.h"
 
@@ -62,66 +63,8 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kStageBytes = 32 * 1024;  // 8 slots x 4 fragments x 1 KiB
 constexpr int kStagesBase = 30;         // + 1 stage (8 slots) for the fused pair projection of the next IPA block
-constexpr float kWS = 32.0f, kInvWS = 1.0f / 32.0f;   // weights are packed as 2^5 w (see the header): accumulators carry 32 x the layer output
-
-__device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float4 ldg4(const float* __restrict__ base, int g, int h) {
-    return *reinterpret_cast<const float4*>(base + 8 * g + 4 * h);
-}
-__device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32, 64); }
-
-// Four fp32 values -> elements at .. at + 3 of the plane fragments (x_h, x_l), and into the range maximum (range_flag.h).
-//   x_h = rn16(x):            v_cvt_pk_f16_f32, two values per instruction
-//   x_l = rn16(x - x_h):      the difference is exact in fp32, so ONE fused multiply-add that reads x_h as f16 and rounds to f16
-//                             (v_fma_mixlo / mixhi_f16:  (-x_h) * 1.0 + x) gives the bits of convert-back + subtract + convert
-// = 1.5 VALU instructions per value (hipcc's expansion of the C expression: 3), written as ONE opaque block: both planes come from
-// the same materialised fp32 value (node_gemm.hip split8_f16), the block stays where it is written (the schedule pins VALU pieces
-// under specific MFMAs), and the maximum does not enter the compiler's reasoning (as an fmaxf chain it cost 300 spilled registers).
-typedef unsigned u32x4p __attribute__((ext_vector_type(4)));
-// two values -> elements at, at + 1 (at even) of the plane fragments: the unit the edge transition places behind single MFMAs
-__device__ __forceinline__ void split2_f16(float x0, float x1, f16x8& ph, f16x8& pl, int at, float& amax) {
-    unsigned hh, ll;
-    asm volatile(
-        "v_max3_f32 %2, %2, |%3|, |%4|\n\t"
-        "v_cvt_pk_f16_f32 %0, %3, %4\n\t"
-        "v_fma_mixlo_f16 %1, -%0, 1.0, %3 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %1, -%0, 1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(hh), "=&v"(ll), "+v"(amax)
-        : "v"(x0), "v"(x1));
-    u32x4p hv = __builtin_bit_cast(u32x4p, ph), lv = __builtin_bit_cast(u32x4p, pl);
-    hv[at / 2] = hh;
-    lv[at / 2] = ll;
-    ph = __builtin_bit_cast(f16x8, hv);
-    pl = __builtin_bit_cast(f16x8, lv);
-}
-__device__ __forceinline__ void split4_f16(const float (&x)[4], f16x8& ph, f16x8& pl, int at, float& amax) {
-    unsigned h0, h1, l0, l1;
-    asm volatile(
-        "v_max3_f32 %4, %4, |%5|, |%6|\n\t"
-        "v_cvt_pk_f16_f32 %0, %5, %6\n\t"
-        "v_max3_f32 %4, %4, |%7|, |%8|\n\t"
-        "v_cvt_pk_f16_f32 %1, %7, %8\n\t"
-        "v_fma_mixlo_f16 %2, -%0, 1.0, %5 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %3, -%1, 1.0, %7 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %2, -%0, 1.0, %6 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %3, -%1, 1.0, %8 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(h0), "=&v"(h1), "=&v"(l0), "=&v"(l1), "+v"(amax)
-        : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]));
-    u32x4p hv = __builtin_bit_cast(u32x4p, ph), lv = __builtin_bit_cast(u32x4p, pl);
-    hv[at / 2] = h0; hv[at / 2 + 1] = h1;
-    lv[at / 2] = l0; lv[at / 2 + 1] = l1;
-    ph = __builtin_bit_cast(f16x8, hv);
-    pl = __builtin_bit_cast(f16x8, lv);
-}
 
 // max(x, 0) as ONE instruction.  fmaxf() of a value the compiler cannot see through (a pinned register, an MFMA result) is preceded by
 // a canonicalising v_max_f32 x, x (IEEE quieting of a signalling NaN): 128 of the edge embedding's ~1500 VALU instructions per tile.
@@ -130,15 +73,6 @@ __device__ __forceinline__ float relu1(float x) {
     float r;
     asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
     return r;
-}
-
-template <int I> struct IC { static constexpr int value = I; };
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) {
-        f(IC<B>{});
-        static_for<B + 1, E>(f);
-    }
 }
 
 // slot s of the schedule: phase 0 = A (layer 1), 1 = B (layer 2), 2 = F (final layer)
@@ -167,16 +101,6 @@ constexpr int blob_stage(bool proj, int st) { return !proj ? st : (st == 0 ? 0 :
 #define S2S_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 __device__ float s2s_one[1] = {1.0f};   // stands in for an absent node mask (read with stride 0)
 
-#if defined(S2S_ET_PROBE) || defined(S2S_EE_PROBE)
-// Phase probe (tools/et_phase_probe.py): s_memtime stamps at 16 points of a tile, wave 0 of every workgroup, differences summed
-// per workgroup.  The stamps are SMEM results consumed only after the tile's last lgkmcnt(0) wait.
-__device__ unsigned long long g_et_probe[512 * 17];
-#endif
-#ifdef S2S_ET_PROBE
-#define ET_STAMP(k) asm volatile("s_memtime %0" : "=s"(st##k))
-#else
-#define ET_STAMP(k)
-#endif
 
 // PROJ: also emit the NEXT IPA block's linear_b / down_z (ipa.py:177,253) of the pair vector just produced -- one more
 // weight stage (64 x 128 Wcat, chain-packed), 8 more slots on the LayerNorm output while it is still in registers,
@@ -316,40 +240,15 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
     // cfg2), and as ordinary accesses they push the 0.97 MB weight stream -- which all 32 workgroups of an XCD re-read every tile -- out of the
     // 4 MiB L2 between two uses (the re-fetches from the Infinity Cache showed in FETCH_SIZE: 378 instead of 301 B per pair).  With the nt bit
     // on the row loads and the output stores: -0.5 .. -1.2 % per launch at every shape measured (same-call A/B, profiles/r06_et_nt_ab.txt;
-    // loads alone -0.4 %; nt on the fused projection's stores as well: no further gain, not kept).  -DS2S_ET_NT=0 restores plain accesses.
-#ifndef S2S_ET_NT
-#define S2S_ET_NT 2
-#endif
-    typedef float f32x4nt __attribute__((ext_vector_type(4)));
+    // loads alone -0.4 %; nt on the fused projection's stores as well: no further gain, not kept).
     auto ldrow = [&](const float* r, int g) -> float4 {
-        if constexpr (S2S_ET_NT >= 1) {
-            const f32x4nt v = __builtin_nontemporal_load(reinterpret_cast<const f32x4nt*>(r + g * in_step));
-            return make_float4(v.x, v.y, v.z, v.w);
-        } else {
-            return *reinterpret_cast<const float4*>(r + g * in_step);
-        }
+        const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(r + g * in_step));
+        return make_float4(v.x, v.y, v.z, v.w);
     };
     const long long n_wt = (M + 127) / 128;
     long long wt = blockIdx.x;
-#ifndef S2S_ET_PHASES
-#define S2S_ET_PHASES 1
-#endif
-    // Phase stagger (OFF since the end of round 4; -DS2S_ET_PHASES=16 restores it).  Every workgroup runs the same schedule on equal
-    // tiles: left alone they stay in lockstep and ask HBM for their next 64 KiB tile in the same microsecond.  Starting the workgroups
-    // of one XCD S2S_ET_PHASES different fractions of a tile apart was meant to spread those requests over the tile time -- but since
-    // the edge row is requested two loads per slot, 16+ slots ahead of its use (kXv0 below), lockstep costs nothing, while the start
-    // delay (up to 15/16 of a tile: ~45 us) is added to every launch: same-call A/B (profiles/r04t_et_phase_stagger_ab.txt)
-    // 11.290 -> 11.274 ms at cfg2, 0.245 -> 0.215 ms at 100 x 35^2 pairs (3.7 tiles per workgroup), 1.019 -> 1.002 at 100 x 80^2.
-    // What lockstep does cost is fabric READ REQUESTS, not time: PMC FETCH_SIZE 378 instead of 301 B per pair (1256 / 1104 B per pair
-    // of corrected traffic against 1013 algorithmic, profiles/r05d_pmc_hbm_traffic*.json, round 5).  The pair stream flows through
-    // the XCD's 4 MiB L2 and evicts the 0.97 MB weight stream between two uses of a stage when all 32 workgroups use it at the same
-    // moment once per tile (~43 us); staggered, some workgroup touches every stage every ~3 us and it stays resident.  The re-fetches
-    // are served by the 256 MiB Infinity Cache (the counter sits on the L2's fabric side and includes its hits), two stages ahead of
-    // their use.  A fine stagger (32 x 0.5 us, one L2 miss apart) changes neither time nor the counter (1245 -> 1225, r05e).
-    if constexpr (S2S_ET_PHASES > 1) {
-        const int phase = (blockIdx.x >> 3) % S2S_ET_PHASES;
-        for (int i = 0; i < phase * (16 / (S2S_ET_PHASES > 16 ? 16 : S2S_ET_PHASES)); ++i) __builtin_amdgcn_s_sleep(98);   // 98 x 64 cycles = 1/16 tile
-    }
+    // (No phase stagger between workgroups: each requests its next edge row 16+ slots ahead of its use (kXv0 below), so running in
+    //  lockstep costs no time, while a start delay would add to every launch: profiles/r04t_et_phase_stagger_ab.txt.)
     PairCtx cur = setup(wt);
 
     // ---- the pair's 128 edge channels, split once: xpl[ks][plane] = B operand of layer-1 k-step ks.  Element j of k-step
@@ -459,14 +358,10 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
     auto fetch = [&](int par, int slot_in_stage, f16x8 (&f)[4]) {
         typedef __attribute__((address_space(3))) f16x8 lds_frag;
         const lds_frag* s = (const lds_frag*)ring_buf(par) + slot_in_stage * 4 * 64;
-#ifndef S2S_ET_FETCH_INORDER
         // fragment 1 (W_l of the first unit) is what a slot's FIRST MFMA reads: requested last, the wait in front of that MFMA covers all
         // four reads (LDS returns in order) and the slot's other MFMAs need none -- one s_waitcnt per slot instead of two or three
+        // (profiles/r05l_et_waitcnt_ab.txt)
         f[0] = s[0]; f[2] = s[128]; f[3] = s[192]; f[1] = s[64];
-#else
-#pragma unroll
-        for (int k = 0; k < 4; ++k) f[k] = s[64 * k];
-#endif
     };
     // quarter qd (registers 4qd..4qd+3) of  relu(a1 tile + seeds)  -> planes of k-step qd>>1, elements 4(qd&1)..
     auto s_quarter = [&](const f32x16& tile_acc, auto qc) {
@@ -530,8 +425,7 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
         o.z = ((a3[t][4 * rq + 2] - ln_mean) * ln_rstd * ga.z + be.z) * ln_em;
         o.w = ((a3[t][4 * rq + 3] - ln_mean) * ln_rstd * ga.w + be.w) * ln_em;
         if (prv.valid && !no_out) {
-            if constexpr (S2S_ET_NT >= 2) __builtin_nontemporal_store(f32x4nt{o.x, o.y, o.z, o.w}, reinterpret_cast<f32x4nt*>(ln_orow + q * out_step));
-            else *reinterpret_cast<float4*>(ln_orow + q * out_step) = o;
+            __builtin_nontemporal_store(f32x4{o.x, o.y, o.z, o.w}, reinterpret_cast<f32x4*>(ln_orow + q * out_step));
         }
         if constexpr (PROJ) {
             const float x[4] = {o.x, o.y, o.z, o.w};
@@ -560,10 +454,6 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
 #pragma unroll
     for (int t = 0; t < 4; ++t) a3[t] = zero16;
 
-#ifdef S2S_ET_PROBE
-    unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0, st5 = 0, st6 = 0, st7 = 0, st8 = 0, st9 = 0, st10 = 0, st11 = 0, st12 = 0,
-                       st13 = 0, st14 = 0, st15 = 0;
-#endif
     constexpr int kHead = PROJ ? 16 : 15;  // slots that still work for the previous tile: A_0 A_1 + its projection (PROJ) or the first seven slots of B_0
     long long wt_next = wt;
     bool has_next = false;
@@ -581,40 +471,6 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
         constexpr bool barrier_here = true;
 #else
         constexpr bool barrier_here = !PROJ || (st_next & 1) == 0 || st_next == kStages - 2;    // in front of st_next (ring comment at s_w)
-#endif
-#if defined(S2S_ET_PROBE) && S2S_ET_PROBE == 3   // fine view of one layer-2 block: slot tops 72 .. 87 (B_4 A_6), 88
-        if constexpr (s >= 72 && s <= 87) { if constexpr (s == 72) ET_STAMP(0); if constexpr (s == 73) ET_STAMP(1); if constexpr (s == 74) ET_STAMP(2);
-            if constexpr (s == 75) ET_STAMP(3); if constexpr (s == 76) ET_STAMP(4); if constexpr (s == 77) ET_STAMP(5); if constexpr (s == 78) ET_STAMP(6);
-            if constexpr (s == 79) ET_STAMP(7); if constexpr (s == 80) ET_STAMP(8); if constexpr (s == 81) ET_STAMP(9); if constexpr (s == 82) ET_STAMP(10);
-            if constexpr (s == 83) ET_STAMP(11); if constexpr (s == 84) ET_STAMP(12); if constexpr (s == 85) ET_STAMP(13); if constexpr (s == 86) ET_STAMP(14);
-            if constexpr (s == 87) ET_STAMP(15); }
-#elif defined(S2S_ET_PROBE) && S2S_ET_PROBE == 2   // fine view of the last final-layer block: slot tops 216 .. 239
-        if constexpr (s == 216) ET_STAMP(0);
-        if constexpr (s == 220) ET_STAMP(1);
-        if constexpr (s == 224) ET_STAMP(2);
-        if constexpr (s == 225) ET_STAMP(3);
-        if constexpr (s == 226) ET_STAMP(4);
-        if constexpr (s == 227) ET_STAMP(5);
-        if constexpr (s == 228) ET_STAMP(6);
-        if constexpr (s == 229) ET_STAMP(7);
-        if constexpr (s == 230) ET_STAMP(8);
-        if constexpr (s == 232) ET_STAMP(9);
-        if constexpr (s == 234) ET_STAMP(10);
-        if constexpr (s == 236) ET_STAMP(11);
-        if constexpr (s == 237) ET_STAMP(12);
-        if constexpr (s == 238) ET_STAMP(13);
-        if constexpr (s == 239) ET_STAMP(14);
-#else   // phases of one pass of the loop, in time order
-        if constexpr (ns == 0) ET_STAMP(0);
-        if constexpr (ns == 4) ET_STAMP(1);
-        if constexpr (ns == 8) ET_STAMP(2);
-        if constexpr (ns == kHead) ET_STAMP(3);
-        if constexpr (s == 24) ET_STAMP(4);
-        if constexpr (s == 168) ET_STAMP(5);
-        if constexpr (s == 180) ET_STAMP(7);
-        if constexpr (s == 192) ET_STAMP(9);
-        if constexpr (s == 208) ET_STAMP(11);
-        if constexpr (s == 224) ET_STAMP(13);
 #endif
 
         // ---------------- top of the slot: next slot's fragments, loads that land under later slots
@@ -643,7 +499,7 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
         if constexpr (s == 237) { seedc_piece(nxt, 0, 0); seedc_piece(nxt, 0, 1); seedc_piece(nxt, 0, 2); seedc_piece(nxt, 0, 3); }
         if constexpr (s == 238) { seedc_piece(nxt, 1, 0); seedc_piece(nxt, 1, 1); seedc_piece(nxt, 1, 2); seedc_piece(nxt, 1, 3); }
         // seeds of a1 tile t+1 are fetched in the middle of B_t, in a slot without weight-pipe work (consumed under A_{t+2}, 6+ slots
-        // later; a fetch 3 slots ahead of its use cost ~300 cycles at the fetch and ~300 at the use: tools/et_phase_probe.py --block)
+        // later; a fetch 3 slots ahead of its use cost ~300 cycles at the fetch and ~300 at the use in the timeline probe)
         constexpr bool seeds_slot = d.phase == 1 && d.a == 1 && d.b == 0 && d.t + 1 < 12;   // a quarter behind each of its first 4 MFMAs
         // residual rows of the layer-2 epilogue blocks 1 (n'_i, under B_11) and 2 (n'_j, under the first final-layer block)
         if constexpr (s >= 184 && s < 192) row_load2(node_p + (unsigned long long)cur.bi * 128u, rs, 2 * (s - 184));
@@ -667,16 +523,11 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
         // complete 4+ slots before its first product (slot 192 / 193) and not live while the layer-2 blocks need every register --
         // same-call A/B against the kernel before (profiles/r05p_et_gseed_ab.txt): four pieces per slot from 184 -0.35 %, from 176 +1.7 %
         // (spills), two per slot from 180 / 182 / 184: -0.67 / -0.70 / -0.45 %.  (Bound: the kernel with that residual simply left out, -1.3 %.)
-#ifndef S2S_ET_GSLOT
-#define S2S_ET_GSLOT 182
-#endif
-#ifndef S2S_ET_GPER
-#define S2S_ET_GPER 2
-#endif
-        if constexpr (s >= S2S_ET_GSLOT && s < S2S_ET_GSLOT + 16 / S2S_ET_GPER) {
+        constexpr int kGSlot = 182, kGPer = 2;   // two pieces per slot from slot 182
+        if constexpr (s >= kGSlot && s < kGSlot + 16 / kGPer) {
 #pragma unroll
-            for (int u = 0; u < S2S_ET_GPER; ++u) {
-                constexpr int p0 = (s - S2S_ET_GSLOT) * S2S_ET_GPER;
+            for (int u = 0; u < kGPer; ++u) {
+                constexpr int p0 = (s - kGSlot) * kGPer;
                 const int t3 = (p0 + u) / 4, rq = (p0 + u) % 4;
                 const float4 v = ldg4(node_ab + (unsigned long long)cur.bj * 896u + 768 + 32 * t3, rq, h);
                 a3[t3][4 * rq + 0] = v.x; a3[t3][4 * rq + 1] = v.y; a3[t3][4 * rq + 2] = v.z; a3[t3][4 * rq + 3] = v.w;
@@ -730,16 +581,11 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
             f16x8 (&P)[2] = ep_blk == 1 ? xq[2 * t + (rq >> 1)] : xpl[2 * t + (rq >> 1)];
             float r0 = 0.f, r1 = 0.f;
             if constexpr (ep_blk == 0) {   // the residual of block 0 is the edge row = x_h + x_l of the planes this piece replaces (to 2^-24 |x|)
-#ifndef S2S_ET_NO_MIXRES
                 // (float) x_h + (float) x_l as ONE v_fma_mix_f32 per value (x_h * 1.0 + x_l with both read as f16: the same single rounding
                 //  as convert, convert, add)
-                const unsigned hw = __builtin_bit_cast(u32x4p, P[0])[e0 / 2], lw = __builtin_bit_cast(u32x4p, P[1])[e0 / 2];
+                const unsigned hw = __builtin_bit_cast(u32x4, P[0])[e0 / 2], lw = __builtin_bit_cast(u32x4, P[1])[e0 / 2];
                 asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,1]" : "=v"(r0) : "v"(hw), "v"(lw));
                 asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(r1) : "v"(hw), "v"(lw));
-#else
-                r0 = (float)P[0][e0] + (float)P[1][e0];
-                r1 = (float)P[0][e0 + 1] + (float)P[1][e0 + 1];
-#endif
             } else if constexpr (ep_blk == 1) {
                 r0 = rs[16 * t + j0];
                 r1 = rs[16 * t + j0 + 1];
@@ -757,14 +603,9 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
             if constexpr (i < 4) {
                 if constexpr (ss == 0) cp_load_piece(IC<1>{}, ic, st_fill);   // the pipe wraps into the next tile's first stages
                 if constexpr (ss == 4) cp_load_piece(IC<0>{}, ic, (stage + kAhead + 1) % kStages);
-#ifndef S2S_ET_STORE_INORDER
                 // (the piece loaded LAST is stored first: its wait on the in-order counter covers the group, three waits fewer per slot)
                 if constexpr (ss == 1) cp_store_piece(IC<0>{}, IC<3 - i>{}, st_fill & (kRing - 1));
                 if constexpr (ss == 5) cp_store_piece(IC<1>{}, IC<3 - i>{}, st_fill & (kRing - 1));
-#else
-                if constexpr (ss == 1) cp_store_piece(IC<0>{}, ic, st_fill & (kRing - 1));
-                if constexpr (ss == 5) cp_store_piece(IC<1>{}, ic, st_fill & (kRing - 1));
-#endif
             }
             if constexpr (seeds_slot && i < 4) seeds_piece(cur, d.t + 1, i);
             if constexpr (seeds_slot && i < 4 && d.t + 2 < 12) seedc_piece(cur, d.t + 2, i);   // start value of a1 tile t + 2 (A_{t+2} follows this block)
@@ -797,16 +638,6 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
         });
 
         // ---------------- exposed steps
-#if defined(S2S_ET_PROBE) && S2S_ET_PROBE == 2
-        if constexpr (s == 239) ET_STAMP(15);
-#elif defined(S2S_ET_PROBE) && S2S_ET_PROBE == 3
-#else
-        if constexpr (s == 179) ET_STAMP(6);
-        if constexpr (s == 191) ET_STAMP(8);
-        if constexpr (s == 207) ET_STAMP(10);
-        if constexpr (s == 223) ET_STAMP(12);
-        if constexpr (s == 239) ET_STAMP(14);
-#endif
         if constexpr (s == 179) {  // B_10 done: tile 11 -> planes (nothing left to hide it under)
             s_quarter(a1t[1], IC<0>{}); s_quarter(a1t[1], IC<1>{}); s_quarter(a1t[1], IC<2>{}); s_quarter(a1t[1], IC<3>{});
         }
@@ -816,19 +647,6 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
     has_next = wt_next < n_wt;
     static_for<0, kSlots>(slot);
 
-#ifdef S2S_ET_PROBE
-#if S2S_ET_PROBE == 1
-    ET_STAMP(15);
-#endif
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (wave == 0 && lane == 0 && blockIdx.x < 512) {
-        unsigned long long* pr = g_et_probe + blockIdx.x * 17;
-        const unsigned long long stv[16] = {st0, st1, st2, st3, st4, st5, st6, st7, st8, st9, st10, st11, st12, st13, st14, st15};
-#pragma unroll
-        for (int k = 0; k < 15; ++k) atomicAdd(pr + k, stv[k + 1] - stv[k]);
-        atomicAdd(pr + 16, 1ull);
-    }
-#endif
     prv = cur;   // a3 holds this tile's final-layer accumulators: LayerNorm, store and projection in the next pass
 #pragma unroll
     for (int i = 0; i < 8; ++i) { xpl[i][0] = xpn[i][0]; xpl[i][1] = xpn[i][1]; }
@@ -1107,11 +925,9 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
             o.y = __fmul_rn(__fmaf_rn(__fmul_rn(a3[t][4 * rq + 1] - ln_mean, ln_rstd), ga.y, be.y), c.em);
             o.z = __fmul_rn(__fmaf_rn(__fmul_rn(a3[t][4 * rq + 2] - ln_mean, ln_rstd), ga.z, be.z), c.em);
             o.w = __fmul_rn(__fmaf_rn(__fmul_rn(a3[t][4 * rq + 3] - ln_mean, ln_rstd), ga.w, be.w), c.em);
-#ifndef S2S_EE_NT
-#define S2S_EE_NT 0
-#endif
+            // (plain stores: with the nt bit, no change beyond the noise; profiles/r06_et_nt_ab.txt)
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(o.w)},
-                                                   rs_out, out_lane + (unsigned)g * out_step, 0, S2S_EE_NT ? 2 : 0);   // (aux bit 1 = nt)
+                                                   rs_out, out_lane + (unsigned)g * out_step, 0, 0);
             if constexpr (PROJ) {
                 const float xx[4] = {o.x, o.y, o.z, o.w};
                 split4(xx, xq[k & 1][0], xq[k & 1][1], 4 * u);
@@ -1132,7 +948,7 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
     fetch(0, 0, fr[0]);
     f32x16 initA0 = bias16(s_vec, 0), initA1 = bias16(s_vec, 1), initB0, initB1;
     // per-pair scalars (CA coordinates, residue indices, masks) of the tile after this one: requested a whole tile ahead -- used four
-    // slots after the request they cost the tile ~1.2 k cycles of waiting (tools/ee_phase_probe.py, slot 4)
+    // slots after the request they cost the tile ~1.2 k cycles of waiting (profiles/r03f_ee_phase_probe.txt)
     Raw nraw = setup_a(wt + gridDim.x < n_wt ? wt + gridDim.x : wt);
 
     for (;;) {
@@ -1140,41 +956,9 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
     const bool has_next = wt_next < n_wt;
     Ctx nxt = cur;
     f16x8 xl[2];  // the next tile's last k-step (xp[7] is read by the final layer's last slot)
-#ifdef S2S_EE_PROBE
-    unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0, st5 = 0, st6 = 0, st7 = 0, st8 = 0, st9 = 0, st10 = 0, st11 = 0, st12 = 0,
-                       st13 = 0, st14 = 0, st15 = 0;
-#define EE_STAMP(k) asm volatile("s_memtime %0" : "=s"(st##k))
-#else
-#define EE_STAMP(k)
-#endif
     static_for<0, kSlots>([&](auto sc) {
         constexpr int s = decltype(sc)::value;
         constexpr int stage = s / 8, ss = s % 8, par = stage & 1;
-#if defined(S2S_EE_PROBE) && S2S_EE_PROBE == 2   // slot by slot: tops of slots BASE .. BASE + 14
-#ifndef S2S_EE_PROBE_BASE
-#define S2S_EE_PROBE_BASE 0
-#endif
-        if constexpr (s >= S2S_EE_PROBE_BASE && s < S2S_EE_PROBE_BASE + 15) {
-            constexpr int k = s - S2S_EE_PROBE_BASE;
-            if constexpr (k == 0) EE_STAMP(0); if constexpr (k == 1) EE_STAMP(1); if constexpr (k == 2) EE_STAMP(2); if constexpr (k == 3) EE_STAMP(3);
-            if constexpr (k == 4) EE_STAMP(4); if constexpr (k == 5) EE_STAMP(5); if constexpr (k == 6) EE_STAMP(6); if constexpr (k == 7) EE_STAMP(7);
-            if constexpr (k == 8) EE_STAMP(8); if constexpr (k == 9) EE_STAMP(9); if constexpr (k == 10) EE_STAMP(10); if constexpr (k == 11) EE_STAMP(11);
-            if constexpr (k == 12) EE_STAMP(12); if constexpr (k == 13) EE_STAMP(13); if constexpr (k == 14) EE_STAMP(14);
-        }
-#else
-        if constexpr (s == 0) EE_STAMP(0);
-        if constexpr (s == 4) EE_STAMP(1);
-        if constexpr (s == 8) EE_STAMP(2);
-        if constexpr (s == 12) EE_STAMP(3);
-        if constexpr (s == 16) EE_STAMP(4);
-        if constexpr (s == 20) EE_STAMP(5);
-        if constexpr (s == 24) EE_STAMP(6);
-        if constexpr (s == 28) EE_STAMP(7);
-        if constexpr (s == 31) EE_STAMP(8);
-        if constexpr (s == 32) EE_STAMP(10);
-        if constexpr (s == 36) EE_STAMP(11);
-        if constexpr (s == 39) EE_STAMP(12);
-#endif
         constexpr int layer = s / 16;             // 0: layer 2, 1: layer 3, 2: projection
         constexpr int ks = layer < 2 ? (s % 16) / 2 : s - 32;
         constexpr int pr = layer < 2 ? s % 2 : 0;
@@ -1248,9 +1032,6 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
         __builtin_amdgcn_sched_barrier(0);
 
         // ---------------- exposed steps
-#if !(defined(S2S_EE_PROBE) && S2S_EE_PROBE == 2)
-        if constexpr (s == 31) EE_STAMP(9);
-#endif
         if constexpr (s == 31) {  // layer-3 output (bias included): LayerNorm statistics
             float sum = 0.f;
 #pragma unroll
@@ -1274,9 +1055,6 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
             }
         }
     });
-#if !(defined(S2S_EE_PROBE) && S2S_EE_PROBE == 2)
-    EE_STAMP(13);
-#endif
     if constexpr (PROJ) {
         if (cur.valid) {
             const float4 b0 = ldg4(s_vec + 512, 0, h);
@@ -1295,19 +1073,6 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
             }
         }
     }
-#ifdef S2S_EE_PROBE
-#if S2S_EE_PROBE != 2
-    EE_STAMP(14);
-#endif
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (PROJ && wave == 0 && lane == 0 && blockIdx.x < 512) {
-        unsigned long long* pr = g_et_probe + blockIdx.x * 17;
-        const unsigned long long stv[16] = {st0, st1, st2, st3, st4, st5, st6, st7, st8, st9, st10, st11, st12, st13, st14, st14};
-#pragma unroll
-        for (int k = 0; k < 14; ++k) atomicAdd(pr + k, stv[k + 1] - stv[k]);
-        atomicAdd(pr + 16, 1ull);
-    }
-#endif
     if (!has_next) break;
     cur = nxt;
     wt = wt_next;
@@ -1396,17 +1161,6 @@ extern "C" int s2s_et_f16x3_short_chains(S2S_ET_ARGS) { return et_launch<false>(
 #if S2S_PM_PART == 1
 extern "C" int s2s_edge_transition_f16x3(S2S_ET_ARGS) {
     return n_res >= 32 ? et_launch<true>(S2S_ET_PASS) : s2s_et_f16x3_short_chains(S2S_ET_PASS);
-}
-#endif
-
-#if (defined(S2S_ET_PROBE) && S2S_PM_PART == 1) || (defined(S2S_EE_PROBE) && S2S_PM_PART == 3)   // (a probe build replaces the one unit its kernel lives in)
-extern "C" int s2s_et_probe_read(unsigned long long* host_out, int reset) {   // 512 x 17 counters
-    hipError_t e = hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_et_probe), sizeof(unsigned long long) * 512 * 17);
-    if (e == hipSuccess && reset) {
-        static unsigned long long z[512 * 17];
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_et_probe), z, sizeof(z));
-    }
-    return (int)e;
 }
 #endif
 

@@ -16,11 +16,6 @@ using namespace s2s;
 
 namespace {
 
-__device__ __forceinline__ void load7(const float* __restrict__ p, Quat<float>& q, Vec3<float>& t) {
-    q.w = p[0]; q.x = p[1]; q.y = p[2]; q.z = p[3];
-    t.x = p[4]; t.y = p[5]; t.z = p[6];
-}
-
 __global__ void __launch_bounds__(256) compose_update_kernel(const float* __restrict__ rig, const float* __restrict__ upd,
                                                              const float* __restrict__ mask, float* __restrict__ out,
                                                              long long M, int upd_ld) {

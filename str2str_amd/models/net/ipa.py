@@ -26,8 +26,6 @@ import torch.nn.functional as F
 from ... import ops
 from ...arith import default_arith
 from ...common.rigid_utils import Rigid, Rotation
-_CHAIN4 = os.environ.get("S2S_CHAIN4", "1") != "0"   # trunk.linear + NodeTransition as one launch (s2s_node_chain)
-_ENC_CHAIN3 = os.environ.get("S2S_ENC_CHAIN3", "1") != "0"   # an encoder layer's out_proj + norm1 + feed-forward + norm2 as one launch
 from .layers import BackboneUpdate, EdgeTransition, Linear, NodeTransition, ParamCache, TorsionAngleHead
 
 
@@ -377,29 +375,18 @@ class TranslationIPA(nn.Module):
                 sa_f32, sa_xp = torch.ops.str2str_amd.encoder_attention(qkv, key_bias, B, N, layer.self_attn.num_heads, not f16, f16, self.arith)
                 # the post-attention half of the layer as ONE launch (s2s_node_chain): out_proj + residual + norm1 (its fp32 result is
                 # stored: the residual of norm2), linear1 -> relu -> linear2 + that residual + norm2; the hidden activations stay in
-                # registers.  (S2S_ENC_CHAIN3=0: out_proj on its own, then the two feed-forward layers as a chain -- the same bits)
-                if _ENC_CHAIN3:
-                    x1 = torch.empty(M, D, device=dev, dtype=torch.float32)
-                    xf, xx = ops.node_apply_chain(sa_xp if f16 else sa_f32, [lw["o"], lw["l1"], lw["l2"]], M, (False, True, False),
-                                                  first_residual=xf, first_out_f32=x1, first_ln=(layer.norm1.weight, layer.norm1.bias, layer.norm1.eps),
-                                                  residual=x1, ln=(layer.norm2.weight, layer.norm2.bias, layer.norm2.eps), want_xp=True)
-                else:
-                    x1, x1a = lin(sa_xp if f16 else sa_f32, lw["o"], residual=xf, ln=(layer.norm1.weight, layer.norm1.bias, layer.norm1.eps),
-                                  want_xp=True)
-                    xf, xx = ops.node_apply_chain(x1a, [lw["l1"], lw["l2"]], M, (True, False), residual=x1,
-                                                  ln=(layer.norm2.weight, layer.norm2.bias, layer.norm2.eps), want_xp=True)
+                # registers.
+                x1 = torch.empty(M, D, device=dev, dtype=torch.float32)
+                xf, xx = ops.node_apply_chain(sa_xp if f16 else sa_f32, [lw["o"], lw["l1"], lw["l2"]], M, (False, True, False),
+                                              first_residual=xf, first_out_f32=x1, first_ln=(layer.norm1.weight, layer.norm1.bias, layer.norm1.eps),
+                                              residual=x1, ln=(layer.norm2.weight, layer.norm2.bias, layer.norm2.eps), want_xp=True)
             # ---- node_embed + linear(tr) (:358), NodeTransition (:359, layers.py:128-145), mask (:360)
             # ... as ONE launch: trunk.linear's fp32 result is stored and read back as NodeTransition's residual (s2s_node_chain)
             nt = T[f"node_transition_{b}"]
-            if _CHAIN4:
-                n_f32 = torch.empty(M, C, device=dev, dtype=torch.float32)
-                s_f32, s_a = ops.node_apply_chain(xx, [w["lin"], w["nt1"], w["nt2"], w["nt3"]], M, (False, True, True, False),
-                                                  first_residual=x_f32, first_out_f32=n_f32, residual=n_f32,
-                                                  ln=(nt.ln.weight, nt.ln.bias, nt.ln.eps), post_mask=nm, want_xp=True)
-            else:
-                n_f32, n_a = lin(xx, w["lin"], residual=x_f32, want_xp=True)
-                s_f32, s_a = ops.node_apply_chain(n_a, [w["nt1"], w["nt2"], w["nt3"]], M, (True, True, False), residual=n_f32,
-                                                  ln=(nt.ln.weight, nt.ln.bias, nt.ln.eps), post_mask=nm, want_xp=True)
+            n_f32 = torch.empty(M, C, device=dev, dtype=torch.float32)
+            s_f32, s_a = ops.node_apply_chain(xx, [w["lin"], w["nt1"], w["nt2"], w["nt3"]], M, (False, True, True, False),
+                                              first_residual=x_f32, first_out_f32=n_f32, residual=n_f32,
+                                              ln=(nt.ln.weight, nt.ln.bias, nt.ln.eps), post_mask=nm, want_xp=True)
             # ---- backbone update (:361-365) and the layers that read the same s: the EdgeTransition's per-node parts (:367-372; their
             #      pair MLP runs in its own kernel below), after the last block the torsion head's first layer -- ONE launch
             has_et = b < self.num_blocks - 1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/build_variant.sh <name> [extra hipcc flags]: library variant with one differently compiled unit
 # (UNIT=pair_mlp_f16 by default = the edge transition for chains of 32+ residues; UNIT=pair_mlp_f16_b its short-chain form, UNIT=pair_mlp_f16_c the
-# edge embedding -- three translation units of one source, with SRC=<file> for _b / _c a wrapper that includes the other version; e.g. UNIT=ipa_attention tools/build_variant.sh qr0 -DS2S_IPA_QR=0).  Run
+# edge embedding -- three translation units of one source, with SRC=<file> for _b / _c a wrapper that includes the other version; e.g. git show <rev>:str2str_amd/csrc/ipa_attention.hip > old.hip; UNIT=ipa_attention SRC=old.hip tools/build_variant.sh old).  Run
 # `python -m str2str_amd.build` first: the other units are linked from its objects.
 # NOTE: .gpurunignore lists str2str_amd/csrc/build/ab_*.so (45 stale variants once cost every lease a 73 MB push): comment that line out for an
 # A/B session and delete the variants afterwards (rm str2str_amd/csrc/build/ab_*.so).
