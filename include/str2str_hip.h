@@ -13,7 +13,8 @@
  *   - float = IEEE binary32; frames are "tensor_7": quaternion (w,x,y,z) + translation (x,y,z)
  *     (Rigid.to_tensor_7, src/common/rigid_utils.py:1203-1215);
  *   - return value: 0 on success, otherwise a hipError_t (argument errors = hipErrorInvalidValue);
- *   - re-entrant across streams; the only global state is the immutable backbone table.
+ *   - re-entrant across streams and threads: every call takes what it reads and writes as arguments (the range guard's buffer
+ *     included, `range_words` below); the only library state is the backbone table, uploaded per device.
  */
 #ifndef STR2STR_HIP_H
 #define STR2STR_HIP_H
@@ -30,13 +31,13 @@ int s2s_abi_version(void);
  *           fp32-equivalent in precision, but an activation must stay below f16's 65504;
  *   "f32":  exact fp32 MFMA, no range limit (s2s_edge_transition, s2s_edge_embed, s2s_ipa_attention, s2s_node_linear_f32,
  *           s2s_encoder_attention): the reference arithmetic and the automatic fallback.
- * Range guard: every f16x3 kernel keeps a running maximum of the values it splits and ORs a bit into word 0 of the 8-int device
- * buffer registered here when that maximum reaches 2^15 or is not finite (bits: 1 node GEMM, 2 pack_planes, 4 edge transition,
- * 8 edge embedding, 16 IPA points, 32 encoder attention, 64 IPA attention).  Words 1..7 (1 + log2(bit)) collect magnitude buckets
- * of the same families: bit e set = a launch saw a maximum in [2^(8+e), 2^(9+e)) (e = 8: 2^16 or more); nothing is written below
- * 2^8.  The caller clears / reads the buffer (no kernel waits for it); NULL disables the reports.  The caller decides what a raised
- * bit means: str2str_amd/sampler.py re-runs the chunk with ONLY the flagged kernel families on their exact fp32 kernels. */
-int s2s_set_range_flag(int* device_words);
+ * Range guard: every entry point that splits values into f16 planes takes `int* range_words`, an 8-int DEVICE buffer passed per call
+ * (NULL disables the reports).  Its kernels keep a running maximum of the values they split and OR a bit into word 0 when that
+ * maximum reaches 2^15 or is not finite (bits: 1 node GEMM, 2 pack_planes, 4 edge transition, 8 edge embedding, 16 IPA points,
+ * 32 encoder attention).  Word 1 + log2(bit) collects magnitude buckets of the same family: bit e set = a launch saw a maximum in
+ * [2^(8+e), 2^(9+e)) (e = 8: 2^16 or more); nothing is written below 2^8.  The caller clears / reads the buffer (no kernel waits for
+ * it) and decides what a raised bit means: str2str_amd/sampler.py re-runs the chunk with ONLY the flagged kernel families on their
+ * exact fp32 kernels. */
 
 /* ---- Pair-stream MLPs (fp32 MFMA).  Weight blobs are "packed" for the kernels' lane order:
  *      packed[((s4*T + t)*64 + lane)*4 + q] = W[32*t + (lane & 31)][8*s4 + 4*(lane >> 5) + q]
@@ -87,7 +88,7 @@ int s2s_edge_transition_f16x3(const float* edge, const float* node_ab, const flo
                               const float* b2, const float* ln_gamma, const float* ln_beta,
                               const float* mask, float* out, int n_samples, int n_res, float ln_eps, int io_layout,
                               const float* proj_bias_cat64, float* proj_attn_bias, float* proj_pair_z, int prescale_exp,
-                              void* stream);
+                              int* range_words, void* stream);
 /*   prescale_exp = e in 0 .. 15 (0: none): BLOCK EXPONENT of the hidden activations.  The two hidden layers' outputs (relu(layer 1),
  *   relu(layer 2) + x) are kept as f16 planes of 2^-e x their value: relu is positively homogeneous, so the factor rides in
  *   constants the epilogues apply anyway and LayerNorm removes it -- exact for a power of two, no extra instruction, e = 0 is bit
@@ -123,7 +124,7 @@ int s2s_edge_embed_f16x3(const float* node_a, const float* node_b, const float* 
                          const void* weight_stream, const float* b2, const float* b3, const float* ln_gamma,
                          const float* ln_beta, const float* mask, float* out, int n_samples, int n_res, int rel_offset,
                          int n_rel, int n_bins, float ln_eps, int out_tiled, const float* proj_bias_cat64,
-                         float* proj_attn_bias, float* proj_pair_z, void* stream);
+                         float* proj_attn_bias, float* proj_pair_z, int* range_words, void* stream);
 
 /* linear_b and down_z of InvariantPointAttention (src/models/net/ipa.py:177, :253) in one pass over z.
  *   w_packed: [linear_b.weight (8 rows); down_z.weight (32 rows); 24 zero rows] (64x128) packed
@@ -189,7 +190,7 @@ int s2s_ipa_attention(const float* q, const float* kv, const float* q_pts, const
 int s2s_ipa_prep_points_f16(const float* rigids7, const float* q_pts_lin, const float* kv_pts_lin, const float* head_w_scaled,
                             void* qp_xp, void* kp_xp, void* vp_vf, float* q2, float* k2, int n_samples, int n_res, int n_heads,
                             int n_qk_points, int n_v_points, int c_hidden, const void* s_xp, void* k_shared, void* v_shared,
-                            void* stream);
+                            int* range_words, void* stream);
 int s2s_ipa_attention_f16w(const void* q_xp, const void* k_xp, const void* v_vf, const void* qp_xp, const void* kp_xp,
                              const void* vp_vf, const float* q2, const float* k2, const float* attn_bias, float* logits_out,
                              float* stats_out, const float* mask, const float* rigids7, float* out, void* out_xp,
@@ -224,8 +225,8 @@ int s2s_torsion_head(const float* u, int u_ld, int normalize, const float* gt_si
  * or translation / scale (true division) when divide != 0. */
 int s2s_rigid_scale_trans(const float* rigids7, float* out7, long long n_frames, float scale, int divide, void* stream);
 
-/* Upload the idealised-geometry tables used by s2s_frames_to_backbone (host pointers; synchronous;
- * call once per process).  Values: src/common/residue_constants.py:775-852 via all_atom.py:13-18. */
+/* Upload the idealised-geometry tables used by s2s_frames_to_backbone to the current device (host pointers; synchronous;
+ * call once per device).  Values: src/common/residue_constants.py:775-852 via all_atom.py:13-18. */
 int s2s_set_backbone_tables(const float* pos_21x5x3, const float* mask_21x5, const int* is_psi_group_21x5,
                             const float* default_frames_21x2x4x4);
 
@@ -265,7 +266,7 @@ int s2s_se3_step(const float* x0_7, const float* xt_7, const float* mask, const 
  *      node_a = t_img[256:384] + fa, node_b = t_img[384:512] + fb: the operands of s2s_node_linear / s2s_edge_embed(_f16x3). */
 int s2s_embed_assemble(const float* t_img, long long t_img_rows, const float* node_const, long long node_const_rows, const float* fa, const float* fb,
                        long long n_rows, int n_res, void* h_xp, float* h_f32, float* node_a, float* node_b, int b_col_blocked,
-                       void* stream);
+                       int* range_words, void* stream);
 
 /* ---- Per-node dense layers (split-f16 MFMA "f16x3", fp32-equivalent; see s2s_edge_transition_f16x3) ----
  * Activations travel between these layers as PACKED PLANES ("XP"): for X [M, K],
@@ -277,7 +278,7 @@ int s2s_embed_assemble(const float* t_img, long long t_img_rows, const float* no
 /* fp32 row-major x [n_rows, ld], columns col0 .. col0 + n_cols (n_cols % 32 == 0), optionally scaled per row, -> k-steps
  * xp_kstep0 .. of an XP buffer holding xp_ksteps k-steps (concatenation along K = k-step ranges). */
 int s2s_pack_planes(const float* x, long long n_rows, int ld, int col0, int n_cols, void* xp, int xp_ksteps, int xp_kstep0,
-                    const float* row_scale, void* stream);
+                    const float* row_scale, int* range_words, void* stream);
 
 /* One nn.Linear of the node stream with its surrounding elementwise ops (reference: Linear src/models/net/layers.py:64-124;
  * call sites ipa.py:131-171 (q/kv/points), :259-266 (linear_out), :343-366 (LayerNorm, skip, transformer, linear, transitions),
@@ -295,7 +296,7 @@ int s2s_node_linear(const void* xp, const void* w_packed, const float* bias, lon
                     int tiles_per_block, const float* pre_scale, int relu, const float* pre_mask, const float* residual,
                     int residual_ld, const float* ln_gamma, const float* ln_beta, float ln_eps, const float* post_mask,
                     float* out_f32, int out_ld, int out_col0, void* out_xp, int out_xp_ksteps, int out_xp_kstep0,
-                    int map_pad, int map_src, void* stream);
+                    int map_pad, int map_src, int* range_words, void* stream);
 
 /* The same layer, same epilogue, on EXACT fp32 MFMA: x fp32 row-major [n_rows, x_ld] (its first k_in columns, k_in % 8 == 0),
  * w_packed = ops.pack_node_weight_f32(W, tiles_per_block): [n_out/(32 TG)][k_in/8][TG][64][4] fp32 in the pack_weight lane order,
@@ -311,7 +312,7 @@ int s2s_node_linear_f32(const float* x, int x_ld, const float* w_packed, const f
  * [plane 2][lane 64][8], element j of lane (column c, half h) = row (r&3) + 8 (r>>2) + 4 h, r = 8 u + j, of the tile.  w_packed as
  * for s2s_node_linear with tiles_per_block = 8.  map_pad / map_src: the row map of s2s_node_linear. */
 int s2s_node_linear_vfrag(const void* xp, const void* w_packed, const float* bias, long long n_rows, int k_in, int n_out,
-                          int tiles_per_head, void* out_vf, int map_pad, int map_src, void* stream);
+                          int tiles_per_head, void* out_vf, int map_pad, int map_src, int* range_words, void* stream);
 
 /* Up to six INDEPENDENT node layers (bias / ReLU epilogues, no residual / LayerNorm / masks) in one launch -- the five projections of an
  * IPA block (linear_q, the k and v halves of linear_kv, linear_q_points, linear_kv_points: ipa.py:131-171) read the same activations
@@ -329,7 +330,7 @@ typedef struct s2s_node_problem {
     int map_pad, map_src, relu;
     const float* pre_scale;   /* [n_rows] or NULL: row scale applied to the accumulator before the bias (s2s_node_linear) */
 } s2s_node_problem;
-int s2s_node_linear_multi(const s2s_node_problem* problems, int n_problems, void* stream);
+int s2s_node_linear_multi(const s2s_node_problem* problems, int n_problems, int* range_words, void* stream);
 
 /* A chain of 2 .. 4 layers of one output width (256 or 320) in one launch: every layer but the last is relu?(W x + b), the last one
  * has the epilogue and outputs of s2s_node_linear.  The hidden activations stay in registers (the accumulator layout of a layer is the
@@ -345,7 +346,7 @@ int s2s_node_chain(const void* xp, const s2s_chain_layer* layers, int n_layers, 
                    const float* mid_residual, int mid_residual_ld, float* mid_out_f32, int mid_out_ld, const float* mid_ln_gamma,
                    const float* mid_ln_beta, float mid_ln_eps, const float* pre_mask, const float* residual, int residual_ld, const float* ln_gamma, const float* ln_beta, float ln_eps,
                    const float* post_mask, float* out_f32, int out_ld, int out_col0, void* out_xp, int out_xp_ksteps,
-                   int out_xp_kstep0, void* stream);
+                   int out_xp_kstep0, int* range_words, void* stream);
 
 /* The LayerNorm (+ post mask) half of a node layer on its own: fp32 rows x [n_rows, x_ld] (n_cols = 256 or 320) -> out_f32 and / or packed
  * planes, with the epilogue code of s2s_node_linear -- a layer run as s2s_node_linear(ln = NULL, out_f32 = x) followed by this call
@@ -353,19 +354,19 @@ int s2s_node_chain(const void* xp, const s2s_chain_layer* layers, int n_layers, 
  * in narrow column blocks instead of one block per row tile. */
 int s2s_row_layernorm(const float* x, int x_ld, long long n_rows, int n_cols, const float* ln_gamma, const float* ln_beta, float ln_eps,
                       const float* post_mask, float* out_f32, int out_ld, int out_col0, void* out_xp, int out_xp_ksteps,
-                      int out_xp_kstep0, void* stream);
+                      int out_xp_kstep0, int* range_words, void* stream);
 
 /* Self-attention core of the trunk's TransformerEncoderLayer (src/models/net/ipa.py:312-317,357; torch.nn.MultiheadAttention with
  * d_model = n_heads * head_dim, head_dim = 80): softmax(q k^T / sqrt(head_dim) + key_bias[j]) v per (sample, head), exact fp32 MFMA.
  *   qkv [B*N, 3*D] fp32 = in_proj output (q | k | v); key_bias [B,N] or NULL: added to the logits of key j (PyTorch's float
  *   key-padding-mask semantics; -inf removes a key); out_f32 [B*N, D] and/or out_xp = packed planes of it (see above). */
 int s2s_encoder_attention(const float* qkv, const float* key_bias, float* out_f32, void* out_xp, int n_samples, int n_res,
-                          int n_heads, int head_dim, void* stream);
+                          int n_heads, int head_dim, int* range_words, void* stream);
 
 /* The same operator on split-f16 MFMA ("f16x3", the default arithmetic): q, k, v and the probabilities as f16 pairs, three products
  * per block, fp32 softmax and accumulation; q, k, v feed the range guard.  Same arguments. */
 int s2s_encoder_attention_f16x3(const float* qkv, const float* key_bias, float* out_f32, void* out_xp, int n_samples, int n_res,
-                          int n_heads, int head_dim, void* stream);
+                          int n_heads, int head_dim, int* range_words, void* stream);
 
 /* ---- Forward process / prior, once per trajectory ---- */
 

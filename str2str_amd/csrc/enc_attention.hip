@@ -408,21 +408,21 @@ __global__ void __launch_bounds__(256, 2) enc_attention_f16_kernel(const float* 
 }  // namespace
 
 extern "C" int s2s_encoder_attention_f16x3(const float* qkv, const float* key_bias, float* out_f32, void* out_xp, int n_samples, int n_res,
-                                           int n_heads, int head_dim, void* stream) {
+                                           int n_heads, int head_dim, int* range_words, void* stream) {
     if (n_samples <= 0 || n_res <= 0) return 0;
     if (!qkv || (!out_f32 && !out_xp) || head_dim != 80 || n_heads < 1 || (n_heads * head_dim) % 32) return (int)hipErrorInvalidValue;
     const long long blocks = (long long)n_samples * n_heads * ((n_res + 127) / 128);
     hipLaunchKernelGGL((enc_attention_f16_kernel<80>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, qkv, key_bias, out_f32,
-                       (bf16x8*)out_xp, s2s::g_range_flag, n_samples, n_res, n_heads, 1.0f / sqrtf((float)head_dim));
+                       (bf16x8*)out_xp, range_words, n_samples, n_res, n_heads, 1.0f / sqrtf((float)head_dim));
     return (int)hipGetLastError();
 }
 
 extern "C" int s2s_encoder_attention(const float* qkv, const float* key_bias, float* out_f32, void* out_xp, int n_samples, int n_res,
-                                     int n_heads, int head_dim, void* stream) {
+                                     int n_heads, int head_dim, int* range_words, void* stream) {
     if (n_samples <= 0 || n_res <= 0) return 0;
     if (!qkv || (!out_f32 && !out_xp) || head_dim != 80 || n_heads < 1 || (n_heads * head_dim) % 32) return (int)hipErrorInvalidValue;
     const long long blocks = (long long)n_samples * n_heads * ((n_res + 127) / 128);
     hipLaunchKernelGGL((enc_attention_kernel<80>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, qkv, key_bias, out_f32,
-                       (bf16x8*)out_xp, s2s::g_range_flag, n_samples, n_res, n_heads, 1.0f / sqrtf((float)head_dim));
+                       (bf16x8*)out_xp, range_words, n_samples, n_res, n_heads, 1.0f / sqrtf((float)head_dim));
     return (int)hipGetLastError();
 }

@@ -943,7 +943,7 @@ __global__ void __launch_bounds__(256, 1) ipa_attention_short_kernel(PlaneArgs a
 extern "C" int s2s_ipa_prep_points_f16(const float* rigids7, const float* q_pts_lin, const float* kv_pts_lin,
                                           const float* head_w_scaled, void* qp_xp, void* kp_xp, void* vp_vf, float* q2, float* k2,
                                           int n_samples, int n_res, int n_heads, int n_qk_points, int n_v_points, int c_hidden,
-                                          const void* s_xp, void* k_shared, void* v_shared, void* stream) {
+                                          const void* s_xp, void* k_shared, void* v_shared, int* range_words, void* stream) {
     if (n_samples <= 0 || n_res <= 0) return 0;
     if (n_qk_points != PQ || n_v_points != PV || c_hidden != 256 || n_heads < 1) return (int)hipErrorInvalidValue;
     // shared K / V operands: 8 heads <-> 8 column tiles of a 256-wide s; padded lengths need the gathered K planes
@@ -953,7 +953,7 @@ extern "C" int s2s_ipa_prep_points_f16(const float* rigids7, const float* q_pts_
     if (blocks >= (1ll << 31)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(ipa_prep_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rigids7, q_pts_lin, kv_pts_lin,
                        head_w_scaled, sqrtf(1.0f / (3 * c_hidden)), (f16x8*)qp_xp, (f16x8*)kp_xp, (f16x8*)vp_vf, q2, k2, n_heads, n_res,
-                       n_pad, s2s::g_range_flag, (const f16x8*)s_xp, (f16x8*)(n_res % 32 != 0 ? k_shared : nullptr), (f16x8*)v_shared);
+                       n_pad, range_words, (const f16x8*)s_xp, (f16x8*)(n_res % 32 != 0 ? k_shared : nullptr), (f16x8*)v_shared);
     return (int)hipGetLastError();
 }
 
@@ -976,13 +976,10 @@ extern "C" int s2s_ipa_attention_f16w(const void* q_xp, const void* k_xp, const 
     if ((long long)n_samples * (n_pad / 32) * 16 * n_heads * 2048 >= (1ll << 32)) return (int)hipErrorInvalidValue;
     if (ragged && (long long)n_samples * n_heads * n_res * n_res * 4 >= (1ll << 31)) return (int)hipErrorInvalidValue;
     // persistent workgroups, one per CU (83 KiB of LDS each); a multiple of 8 so that workgroup w stays on XCD w % 8
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return (int)hipErrorUnknown;
-        n_cu = prop.multiProcessorCount >= 8 ? prop.multiProcessorCount / 8 * 8 : prop.multiProcessorCount;
-    }
+    int dev = 0, n_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
+        return (int)hipErrorUnknown;
+    if (n_cu >= 8) n_cu = n_cu / 8 * 8;
     const long long blocks = items < n_cu ? items : n_cu;
     PlaneArgs a{(const f16x8*)q_xp, (const f16x8*)k_xp, (const f16x8*)v_vf, (const f16x8*)qp_xp, (const f16x8*)kp_xp,
                 (const f16x8*)vp_vf, q2, k2, attn_bias, logits_out, stats_out, mask, rigids7, out, (f16x8*)out_xp, out_xp_ksteps,

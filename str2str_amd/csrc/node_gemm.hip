@@ -644,13 +644,6 @@ int launch_gemm_f32(const GemmArgs& a, hipStream_t stream) {
 template <int TG, int WAVES, bool VF = false>
 int launch_gemm_w(const GemmArgs& a, hipStream_t stream) {
     constexpr int lds = 2 * 2 * TG * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&node_gemm_kernel<TG, WAVES, VF>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     const long long n_rt = (a.M + 31) / 32;
     const long long row_blocks = (n_rt + WAVES - 1) / WAVES;
     hipLaunchKernelGGL((node_gemm_kernel<TG, WAVES, VF>), dim3((unsigned)row_blocks, (unsigned)a.n_col_blocks), dim3(64 * WAVES), lds, stream, a);
@@ -728,7 +721,7 @@ __global__ void __launch_bounds__(256) embed_assemble_kernel(const float* __rest
 
 extern "C" int s2s_embed_assemble(const float* t_img, long long t_img_rows, const float* node_const, long long node_const_rows, const float* fa, const float* fb,
                                   long long n_rows, int n_res, void* h_xp, float* h_f32, float* node_a, float* node_b, int b_col_blocked,
-                                  void* stream) {
+                                  int* range_words, void* stream) {
     if (n_rows <= 0) return 0;
     if (!t_img || !node_const || !fa || !fb || !node_a || !node_b || (!h_xp == !h_f32) || n_res <= 0 || node_const_rows <= 0 ||
         n_rows % n_res || (node_const_rows != n_rows && node_const_rows != n_res) || (t_img_rows != 1 && t_img_rows != n_rows / n_res))
@@ -738,19 +731,19 @@ extern "C" int s2s_embed_assemble(const float* t_img, long long t_img_rows, cons
     if (nh + 2 * na >= (1ll << 31)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(embed_assemble_kernel, dim3((unsigned)(nh + 2 * na)), dim3(256), 0, (hipStream_t)stream, t_img, t_img_rows == 1 ? 0 : 512, node_const,
                        node_const_rows, fa, fb, n_rows, n_res, (f16x8*)h_xp, h_f32, node_a, node_b, b_col_blocked, (unsigned)nh, (unsigned)na,
-                       s2s::g_range_flag);
+                       range_words);
     return (int)hipGetLastError();
 }
 
 extern "C" int s2s_pack_planes(const float* x, long long n_rows, int ld, int col0, int n_cols, void* xp, int xp_ksteps,
-                               int xp_kstep0, const float* row_scale, void* stream) {
+                               int xp_kstep0, const float* row_scale, int* range_words, void* stream) {
     if (n_rows <= 0) return 0;
     if (!x || !xp || n_cols <= 0 || n_cols % 32 || ld % 4 || col0 % 4 || xp_kstep0 < 0 || xp_kstep0 + n_cols / 16 > xp_ksteps)
         return (int)hipErrorInvalidValue;
     const int KS = n_cols / 16;
     const long long units = ((n_rows + 31) / 32) * KS;
     hipLaunchKernelGGL(pack_planes_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, n_rows, ld, col0, KS,
-                       (f16x8*)xp, xp_ksteps, xp_kstep0, row_scale, s2s::g_range_flag);
+                       (f16x8*)xp, xp_ksteps, xp_kstep0, row_scale, range_words);
     return (int)hipGetLastError();
 }
 
@@ -767,7 +760,7 @@ extern "C" int s2s_node_linear(const void* xp, const void* w_packed, const float
                                int tiles_per_block, const float* pre_scale, int relu, const float* pre_mask, const float* residual,
                                int residual_ld, const float* ln_gamma, const float* ln_beta, float ln_eps, const float* post_mask,
                                float* out_f32, int out_ld, int out_col0, void* out_xp, int out_xp_ksteps, int out_xp_kstep0,
-                               int map_pad, int map_src, void* stream) {
+                               int map_pad, int map_src, int* range_words, void* stream) {
     if (n_rows <= 0) return 0;
     // row map (padded output rows): n_rows counts OUTPUT rows; per-row epilogue operands are not mapped
     if (map_pad < 0 || (map_pad > 0 && (map_src <= 0 || map_src > map_pad || map_pad % 32 || n_rows % map_pad || pre_scale || pre_mask ||
@@ -781,7 +774,7 @@ extern "C" int s2s_node_linear(const void* xp, const void* w_packed, const float
     if (out_xp && (out_xp_kstep0 < 0 || out_xp_kstep0 % 2 || out_xp_kstep0 + n_out / 16 > out_xp_ksteps)) return (int)hipErrorInvalidValue;
     GemmArgs a{(const f16x8*)xp, (const char*)w_packed, bias, pre_scale, pre_mask, residual, ln_gamma, ln_beta, post_mask, out_f32,
                (f16x8*)out_xp, nullptr, 0, n_rows, k_in / 16, ncb, residual_ld, out_ld, out_col0, out_xp_ksteps, out_xp_kstep0, relu, ln_eps,
-               0, s2s::g_range_flag, map_pad, map_src};
+               0, range_words, map_pad, map_src};
     hipStream_t st = (hipStream_t)stream;
     switch (TG) {
         case 1: return launch_gemm<1>(a, st);
@@ -820,7 +813,7 @@ extern "C" int s2s_node_linear_f32(const float* x, int x_ld, const float* w_pack
 }
 
 extern "C" int s2s_node_linear_vfrag(const void* xp, const void* w_packed, const float* bias, long long n_rows, int k_in, int n_out,
-                                     int tiles_per_head, void* out_vf, int map_pad, int map_src, void* stream) {
+                                     int tiles_per_head, void* out_vf, int map_pad, int map_src, int* range_words, void* stream) {
     if (n_rows <= 0) return 0;
     constexpr int TG = 8;
     if (map_pad < 0 || (map_pad > 0 && (map_src <= 0 || map_src > map_pad || map_pad % 32 || n_rows % map_pad))) return (int)hipErrorInvalidValue;
@@ -828,7 +821,7 @@ extern "C" int s2s_node_linear_vfrag(const void* xp, const void* w_packed, const
         (n_out / 32) % tiles_per_head)
         return (int)hipErrorInvalidValue;
     GemmArgs a{(const f16x8*)xp, (const char*)w_packed, bias, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-               (f16x8*)out_vf, tiles_per_head, n_rows, k_in / 16, n_out / (32 * TG), 0, 0, 0, 0, 0, 0, 0.f, 0, s2s::g_range_flag, map_pad,
+               (f16x8*)out_vf, tiles_per_head, n_rows, k_in / 16, n_out / (32 * TG), 0, 0, 0, 0, 0, 0, 0.f, 0, range_words, map_pad,
                map_src};
     return launch_gemm_w<TG, 4, true>(a, (hipStream_t)stream);
 }
@@ -840,7 +833,7 @@ extern "C" int s2s_node_chain(const void* xp, const s2s_chain_layer* layers, int
                               const float* mid_ln_gamma, const float* mid_ln_beta, float mid_ln_eps,
                               const float* pre_mask, const float* residual, int residual_ld, const float* ln_gamma, const float* ln_beta,
                               float ln_eps, const float* post_mask, float* out_f32, int out_ld, int out_col0, void* out_xp,
-                              int out_xp_ksteps, int out_xp_kstep0, void* stream) {
+                              int out_xp_ksteps, int out_xp_kstep0, int* range_words, void* stream) {
     if (n_rows <= 0) return 0;
     const int TG = width / 32;
     if (!xp || !layers || n_layers < 2 || n_layers > kChainMax || width % 32 || (TG != 8 && TG != 10) || (!out_f32 && !out_xp) ||
@@ -852,7 +845,7 @@ extern "C" int s2s_node_chain(const void* xp, const s2s_chain_layer* layers, int
     ChainArgs c{};
     c.a = GemmArgs{(const f16x8*)xp, nullptr, nullptr, nullptr, pre_mask, residual, ln_gamma, ln_beta, post_mask, out_f32, (f16x8*)out_xp,
                    nullptr, 0, n_rows, width / 16, 1, residual_ld, out_ld, out_col0, out_xp_ksteps, out_xp_kstep0, 0, ln_eps, 0,
-                   s2s::g_range_flag, 0, 0};
+                   range_words, 0, 0};
     c.n_layers = n_layers;
     c.mid_residual = mid_residual; c.mid_res_ld = mid_residual_ld; c.mid_out = mid_out_f32; c.mid_out_ld = mid_out_ld;
     c.mid_ln_gamma = mid_ln_gamma; c.mid_ln_beta = mid_ln_beta; c.mid_ln_eps = mid_ln_eps;
@@ -876,7 +869,7 @@ extern "C" int s2s_node_chain(const void* xp, const s2s_chain_layer* layers, int
     return (int)hipGetLastError();
 }
 
-extern "C" int s2s_node_linear_multi(const s2s_node_problem* pr, int n, void* stream) {
+extern "C" int s2s_node_linear_multi(const s2s_node_problem* pr, int n, int* range_words, void* stream) {
     if (n <= 0) return 0;
     if (!pr || n > kMultiMax) return (int)hipErrorInvalidValue;
     MultiArgs ma{};
@@ -904,7 +897,7 @@ extern "C" int s2s_node_linear_multi(const s2s_node_problem* pr, int n, void* st
         ma.a[i] = GemmArgs{(const f16x8*)q.xp, (const char*)q.w_packed, q.bias, q.pre_scale, nullptr, nullptr, nullptr, nullptr, nullptr,
                            vf ? nullptr : q.out_f32, vf ? nullptr : (f16x8*)q.out_xp, vf ? (f16x8*)q.out_vf : nullptr,
                            vf ? q.vfrag_tiles_per_head : 0, q.n_rows, q.k_in / 16, ncb, 0, q.out_ld, q.out_col0, q.out_xp_ksteps,
-                           q.out_xp_kstep0, q.relu, 0.f, 0, s2s::g_range_flag, q.map_pad, q.map_src};
+                           q.out_xp_kstep0, q.relu, 0.f, 0, range_words, q.map_pad, q.map_src};
         ma.kind[i] = kind;
         const long long n_rt = (q.n_rows + 31) / 32;
         ma.nx[i] = (int)((n_rt + 3) / 4);
@@ -914,12 +907,6 @@ extern "C" int s2s_node_linear_multi(const s2s_node_problem* pr, int n, void* st
     }
     for (int i = n; i <= kMultiMax; ++i) ma.cum[i] = (int)total;
     constexpr int lds = 2 * 2 * 10 * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&node_gemm_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     hipLaunchKernelGGL(node_gemm_multi_kernel, dim3((unsigned)total), dim3(256), lds, (hipStream_t)stream, ma);
     return (int)hipGetLastError();
 }
@@ -928,7 +915,7 @@ extern "C" int s2s_node_linear_multi(const s2s_node_problem* pr, int n, void* st
 // epilogue code of s2s_node_linear: a layer run as  s2s_node_linear(ln = NULL, out_f32 = x)  +  this  equals the fused layer bit for bit.
 extern "C" int s2s_row_layernorm(const float* x, int x_ld, long long n_rows, int n_cols, const float* ln_gamma, const float* ln_beta,
                                  float ln_eps, const float* post_mask, float* out_f32, int out_ld, int out_col0, void* out_xp,
-                                 int out_xp_ksteps, int out_xp_kstep0, void* stream) {
+                                 int out_xp_ksteps, int out_xp_kstep0, int* range_words, void* stream) {
     if (n_rows <= 0) return 0;
     const int TG = n_cols / 32;
     if (!x || x_ld % 4 || !ln_gamma || !ln_beta || (n_cols != 256 && n_cols != 320) || (!out_f32 && !out_xp) ||
@@ -936,7 +923,7 @@ extern "C" int s2s_row_layernorm(const float* x, int x_ld, long long n_rows, int
         (out_xp && (out_xp_kstep0 < 0 || out_xp_kstep0 % 2 || out_xp_kstep0 + n_cols / 16 > out_xp_ksteps)))
         return (int)hipErrorInvalidValue;
     GemmArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ln_gamma, ln_beta, post_mask, out_f32, (f16x8*)out_xp, nullptr, 0, n_rows,
-               0, 1, 0, out_ld, out_col0, out_xp_ksteps, out_xp_kstep0, 0, ln_eps, 0, s2s::g_range_flag, 0, 0};
+               0, 1, 0, out_ld, out_col0, out_xp_ksteps, out_xp_kstep0, 0, ln_eps, 0, range_words, 0, 0};
     const long long n_rt = (n_rows + 31) / 32;
     const dim3 grid((unsigned)((n_rt + 3) / 4));
     if (TG == 8) hipLaunchKernelGGL(node_ln_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, a, x, x_ld);

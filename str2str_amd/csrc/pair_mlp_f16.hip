@@ -13,7 +13,7 @@
 // invariant, runs on the scaled values with 1024 eps).  A value of x_l below f16's normal range (|x| < 0.25) is rounded to 2^-25
 // absolute -- 1.7e-8 rms on an O(1) output, under fp32's own rounding.
 // RANGE: activations must stay below f16's 65504.  Every activation that is split here feeds a running maximum; a tile whose
-// maximum reaches 2^15 (or is not finite) raises the library's range flag (range_flag.h), and the sampler re-runs that chunk on the
+// maximum reaches 2^15 (or is not finite) raises the caller's range flag (range_flag.h), and the sampler re-runs that chunk on the
 // exact fp32 kernels (str2str_amd/sampler.py) -- an overflow is neither silent nor an error.  Weights with |32 w| >= 65504 are
 // refused at pack time (ops.pack_f16x2_layer).
 //
@@ -1094,10 +1094,19 @@ long long tile_aligned_samples(long long NN) {
     return 32 / q;
 }
 
+// persistent workgroups: one per CU of the current device
+int cu_count() {
+    int dev = 0, n_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
+        return 256;
+    return n_cu;
+}
+
 template <bool STAGE>
 int et_launch(const float* edge, const float* node_ab, const float* node_p, const void* weight_stream, const float* b2,
               const float* ln_gamma, const float* ln_beta, const float* mask, float* out, int n_samples, int n_res, float ln_eps,
-              int io_layout, const float* proj_bias_cat64, float* proj_attn_bias, float* proj_pair_z, int prescale_exp, void* stream) {
+              int io_layout, const float* proj_bias_cat64, float* proj_attn_bias, float* proj_pair_z, int prescale_exp, int* range_words,
+              void* stream) {
     if (n_samples <= 0 || n_res <= 0) return 0;
     if ((io_layout & ~7) || ((io_layout & 4) && !proj_attn_bias) || (!(io_layout & 4) && !out)) return (int)hipErrorInvalidValue;
     if (prescale_exp < 0 || prescale_exp > 15) return (int)hipErrorInvalidValue;
@@ -1110,17 +1119,9 @@ int et_launch(const float* edge, const float* node_ab, const float* node_p, cons
     long long chunk = cap / NN;
     if ((io_layout & 3) && chunk < n_samples) chunk -= chunk % tile_aligned_samples(NN);   // launches of a tiled tensor start on a 32-pair block
     if (chunk < 1) return (int)hipErrorInvalidValue;
-    static const float* one_of[64] = {};   // per device: the address of s2s_one
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return (int)hipErrorInvalidValue;
-    if (!one_of[dev_id] && hipGetSymbolAddress((void**)&one_of[dev_id], HIP_SYMBOL(s2s_one)) != hipSuccess) return (int)hipErrorInvalidValue;
-    const float* one = one_of[dev_id];
-    static int n_cu = 0;  // persistent workgroups, one per CU
-    if (n_cu == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-            n_cu = 256;
-    }
+    const float* one = nullptr;   // s2s_one of the current device
+    if (hipGetSymbolAddress((void**)&one, HIP_SYMBOL(s2s_one)) != hipSuccess) return (int)hipErrorInvalidValue;
+    const int n_cu = cu_count();
     for (long long b0 = 0; b0 < n_samples; b0 += chunk) {
         const long long nb = n_samples - b0 < chunk ? n_samples - b0 : chunk;
         const long long M = nb * NN, rows0 = b0 * n_res;
@@ -1137,11 +1138,11 @@ int et_launch(const float* edge, const float* node_ab, const float* node_p, cons
         if (proj_attn_bias)
             hipLaunchKernelGGL(k_proj, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, e, nab, np,
                                (const char*)weight_stream, b2, ln_gamma, ln_beta, mk, o, M, n_res, ln_eps, io_layout, mks, proj_bias_cat64,
-                               proj_attn_bias + b0 * 8 * NN, proj_pair_z + b0 * NN * 32, s2s::g_range_flag, sk);
+                               proj_attn_bias + b0 * 8 * NN, proj_pair_z + b0 * NN * 32, range_words, sk);
         else
             hipLaunchKernelGGL(k_plain, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, e, nab, np,
                                (const char*)weight_stream, b2, ln_gamma, ln_beta, mk, o, M, n_res, ln_eps, io_layout, mks,
-                               (const float*)nullptr, (float*)nullptr, (float*)nullptr, s2s::g_range_flag, sk);
+                               (const float*)nullptr, (float*)nullptr, (float*)nullptr, range_words, sk);
     }
     return (int)hipGetLastError();
 }
@@ -1150,9 +1151,10 @@ int et_launch(const float* edge, const float* node_ab, const float* node_p, cons
 
 #define S2S_ET_ARGS const float* edge, const float* node_ab, const float* node_p, const void* weight_stream, const float* b2, \
                     const float* ln_gamma, const float* ln_beta, const float* mask, float* out, int n_samples, int n_res, float ln_eps, \
-                    int io_layout, const float* proj_bias_cat64, float* proj_attn_bias, float* proj_pair_z, int prescale_exp, void* stream
+                    int io_layout, const float* proj_bias_cat64, float* proj_attn_bias, float* proj_pair_z, int prescale_exp, \
+                    int* range_words, void* stream
 #define S2S_ET_PASS edge, node_ab, node_p, weight_stream, b2, ln_gamma, ln_beta, mask, out, n_samples, n_res, ln_eps, io_layout, \
-                    proj_bias_cat64, proj_attn_bias, proj_pair_z, prescale_exp, stream
+                    proj_bias_cat64, proj_attn_bias, proj_pair_z, prescale_exp, range_words, stream
 // chains below 32 residues: a 32-pair tile spans more than two rows, the row seeds stay per-lane loads (its own translation unit)
 extern "C" __attribute__((visibility("hidden"))) int s2s_et_f16x3_short_chains(S2S_ET_ARGS);   // (inside the library only)
 #if S2S_PM_PART == 2
@@ -1170,7 +1172,7 @@ extern "C" int s2s_edge_embed_f16x3(const float* node_a, const float* node_b, co
                                      const void* weight_stream, const float* b2, const float* b3, const float* ln_gamma,
                                      const float* ln_beta, const float* mask, float* out, int n_samples, int n_res,
                                      int rel_offset, int n_rel, int n_bins, float ln_eps, int out_tiled, const float* proj_bias_cat64,
-                                     float* proj_attn_bias, float* proj_pair_z, void* stream) {
+                                     float* proj_attn_bias, float* proj_pair_z, int* range_words, void* stream) {
     if (n_samples <= 0 || n_res <= 0) return 0;
     if (n_bins > 32 || (out_tiled & ~1)) return (int)hipErrorInvalidValue;  // the distogram edges are counted from a 32-entry LDS table
     // 32-bit pair indices and buffer offsets inside a launch: split the samples over several launches when needed
@@ -1184,9 +1186,7 @@ extern "C" int s2s_edge_embed_f16x3(const float* node_a, const float* node_b, co
     if (rows_cap < chunk) chunk = rows_cap;
     if (out_tiled && chunk < n_samples) chunk -= chunk % tile_aligned_samples(NN);
     if (chunk < 1) return (int)hipErrorInvalidValue;
-    int n_cu = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-        n_cu = 256;
+    const int n_cu = cu_count();
     for (long long b0 = 0; b0 < n_samples; b0 += chunk) {
         const long long nb = n_samples - b0 < chunk ? n_samples - b0 : chunk;
         const long long M = nb * NN, rows0 = b0 * n_res;
@@ -1202,12 +1202,12 @@ extern "C" int s2s_edge_embed_f16x3(const float* node_a, const float* node_b, co
             hipLaunchKernelGGL(edge_embed_f16_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, na, nbp,
                                rel_table, bin_table, bin_lower, ridx, cap, (const char*)weight_stream, b2, b3, ln_gamma, ln_beta,
                                mk, o, M, n_res, rel_offset, n_rel, n_bins, ln_eps, out_tiled, proj_bias_cat64,
-                               proj_attn_bias + b0 * 8 * NN, proj_pair_z + b0 * NN * 32, s2s::g_range_flag);
+                               proj_attn_bias + b0 * 8 * NN, proj_pair_z + b0 * NN * 32, range_words);
         else
             hipLaunchKernelGGL(edge_embed_f16_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, na, nbp,
                                rel_table, bin_table, bin_lower, ridx, cap, (const char*)weight_stream, b2, b3, ln_gamma, ln_beta,
                                mk, o, M, n_res, rel_offset, n_rel, n_bins, ln_eps, out_tiled, (const float*)nullptr, (float*)nullptr,
-                               (float*)nullptr, s2s::g_range_flag);
+                               (float*)nullptr, range_words);
     }
     return (int)hipGetLastError();
 }

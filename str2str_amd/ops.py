@@ -16,25 +16,24 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STR2STR_HIP_LIB") or os.path.join(_HERE, "libstr2str_hip.so")  # env override: A/B builds
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 _lib = None
-_tables_loaded = False
+_tables_loaded = set()   # device indices that hold the backbone tables
 
 _vp, _i, _f, _d, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong
 
 _SIGNATURES = {
     "s2s_abi_version": [],
-    "s2s_set_range_flag": [_vp],
     "s2s_edge_transition": [_vp] * 12 + [_i, _i, _f, _vp, _vp, _vp, _vp, _vp],
-    "s2s_edge_transition_f16x3": [_vp] * 9 + [_i, _i, _f, _i, _vp, _vp, _vp, _i, _vp],
+    "s2s_edge_transition_f16x3": [_vp] * 9 + [_i, _i, _f, _i, _vp, _vp, _vp, _i, _vp, _vp],
     "s2s_edge_embed": [_vp] * 15 + [_i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
-    "s2s_edge_embed_f16x3": [_vp] * 14 + [_i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp],
+    "s2s_edge_embed_f16x3": [_vp] * 14 + [_i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
     "s2s_pair_project": [_vp] * 5 + [_i, _i, _vp],
     "s2s_ipa_prep_points": [_vp] * 6 + [_ll, _i, _i, _i, _i, _vp],
     "s2s_ipa_attention": [_vp] * 12 + [_i, _i, _i, _i, _i, _i, _i, _f, _f, _vp],
     "s2s_ipa_opair": [_vp] * 4 + [_i, _i, _i, _i, _i, _i, _i, _vp],
-    "s2s_ipa_prep_points_f16": [_vp] * 9 + [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "s2s_ipa_prep_points_f16": [_vp] * 9 + [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "s2s_ipa_attention_f16w": [_vp] * 15 + [_i] * 8 + [_f, _f, _i, _vp],
     "s2s_rigid_compose_update": [_vp] * 4 + [_ll, _i, _vp],
     "s2s_torsion_head": [_vp, _i, _i, _vp, _ll, _vp, _f, _vp, _ll, _vp],
@@ -43,16 +42,16 @@ _SIGNATURES = {
     "s2s_frames_to_backbone": [_vp] * 5 + [_ll, _vp],
     "s2s_se3_step": [_vp] * 12 + [_i, _i, _d, _vp, _d, _i, _i, _d, _vp],
     "s2s_forward_marginal": [_vp] * 7 + [_i, _vp, _vp, _f, _vp, _i, _i, _vp],
-    "s2s_pack_planes": [_vp, _ll, _i, _i, _i, _vp, _i, _i, _vp, _vp],
-    "s2s_node_linear": [_vp, _vp, _vp, _ll, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp],
+    "s2s_pack_planes": [_vp, _ll, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp],
+    "s2s_node_linear": [_vp, _vp, _vp, _ll, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp],
     "s2s_node_linear_f32": [_vp, _i, _vp, _vp, _ll, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp],
-    "s2s_node_linear_multi": [_vp, _i, _vp],
-    "s2s_node_chain": [_vp, _vp, _i, _ll, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
-    "s2s_embed_assemble": [_vp, _ll, _vp, _ll, _vp, _vp, _ll, _i, _vp, _vp, _vp, _vp, _i, _vp],
-    "s2s_row_layernorm": [_vp, _i, _ll, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
-    "s2s_node_linear_vfrag": [_vp, _vp, _vp, _ll, _i, _i, _i, _vp, _i, _i, _vp],
-    "s2s_encoder_attention": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "s2s_encoder_attention_f16x3": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "s2s_node_linear_multi": [_vp, _i, _vp, _vp],
+    "s2s_node_chain": [_vp, _vp, _i, _ll, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp],
+    "s2s_embed_assemble": [_vp, _ll, _vp, _ll, _vp, _vp, _ll, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp],
+    "s2s_row_layernorm": [_vp, _i, _ll, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp],
+    "s2s_node_linear_vfrag": [_vp, _vp, _vp, _ll, _i, _i, _i, _vp, _i, _i, _vp, _vp],
+    "s2s_encoder_attention": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "s2s_encoder_attention_f16x3": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "s2s_ca_sample_stats": [_vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp],
     "s2s_ca_pairwise_distances": [_vp, _i, _i, _i, _vp, _vp],
     "s2s_ca_pwd_js": [_vp, _i, _vp, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp],
@@ -141,33 +140,33 @@ def load_library(path: Optional[str] = None):
 
 
 # ------------------------------------------------------------------------------------------ range guard of the f16x3 kernels
-_range_flag = None   # eight int32 device words, owned here for the life of the process (captured HIP graphs hold the address)
-RANGE_BITS = {1: "node GEMM", 2: "pack_planes", 4: "edge transition", 8: "edge embedding", 16: "IPA points", 32: "encoder attention",
-              64: "IPA attention"}
+_range_flags = {}   # device index -> its eight int32 words, kept for the life of the process (captured HIP graphs hold the address)
+RANGE_BITS = {1: "node GEMM", 2: "pack_planes", 4: "edge transition", 8: "edge embedding", 16: "IPA points", 32: "encoder attention"}
 # kernel families as the sampler demotes them (str2str_amd/arith.py): flag bits -> family
-RANGE_FAMILIES = {"node": 1 | 2 | 32, "edge_transition": 4, "edge_embed": 8, "ipa": 16 | 64}
+RANGE_FAMILIES = {"node": 1 | 2 | 32, "edge_transition": 4, "edge_embed": 8, "ipa": 16}
 
 
-def range_flag() -> torch.Tensor:
-    """The device buffer of the range guard (csrc/range_flag.h): word 0 = one bit per kernel family whose split values reached 2^15
-    (half of f16's largest finite number) or were not finite; words 1..7 = magnitude buckets per family (``range_headroom``).
-    Registered with the library on first use."""
-    global _range_flag
-    if _range_flag is None:
-        if not torch.cuda.is_available():
-            raise HipLibraryError("the range flag lives on the HIP device")
-        _range_flag = torch.zeros(8, dtype=torch.int32, device="cuda")
-        _check(load_library().s2s_set_range_flag(_p(_range_flag)), "s2s_set_range_flag")
-    return _range_flag
+def range_flag(device=None) -> torch.Tensor:
+    """The range guard's buffer on ``device`` (default: the current one; csrc/range_flag.h): word 0 = one bit per kernel family whose
+    split values reached 2^15 (half of f16's largest finite number) or were not finite; words 1..7 = magnitude buckets per family
+    (``range_headroom``).  Every wrapper of an f16x3 entry point passes the current device's buffer with the call."""
+    if not torch.cuda.is_available():
+        raise HipLibraryError("the range flag lives on the HIP device")
+    idx = None if device is None else torch.device(device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    buf = _range_flags.get(idx)
+    if buf is None:
+        buf = _range_flags[idx] = torch.zeros(8, dtype=torch.int32, device=torch.device("cuda", idx))
+    return buf
 
 
-def range_flag_reset():
-    range_flag().zero_()
+def range_flag_reset(device=None):
+    range_flag(device).zero_()
 
 
-def range_flag_read() -> int:
+def range_flag_read(device=None) -> int:
     """Synchronising read of the flag word (0 = every f16x3 launch since the last reset stayed in range)."""
-    return int(range_flag()[0].item())
+    return int(range_flag(device)[0].item())
 
 
 def range_flag_names(bits: int) -> str:
@@ -179,11 +178,11 @@ def range_families(bits: int):
     return [f for f, m in RANGE_FAMILIES.items() if bits & m]
 
 
-def range_headroom() -> dict:
+def range_headroom(device=None) -> dict:
     """{family: upper bound of max |x| / 2^15} over every f16x3 launch since the last reset (synchronising read).  The kernels record
     maxima in power-of-two buckets from 2^8 up (nothing below: ordinary activations cost no atomic), so the figure is the bucket's
     upper edge: 2^-6 = "never reached 256", 1.0 = "in [2^14, 2^15)", 2.0 and 4.0 = the guard fired (4.0: 2^16 or more / not finite)."""
-    words = range_flag().tolist()
+    words = range_flag(device).tolist()
     out = {}
     for fam, mask in RANGE_FAMILIES.items():
         top = -1
@@ -389,11 +388,11 @@ def edge_transition_f16x3(edge, node_ab, node_p, wstream, b2, gamma, beta, mask,
     elif isinstance(out, PairTiled) != (out_layout == "tiled"):
         raise HipLibraryError("edge_transition_f16x3: out does not have the requested layout")
     io = (1 if in_tiled else 0) | {"rowmajor": 0, "tiled": 2, "none": 4}[out_layout]
-    range_flag()
     _check(_timed("s2s_edge_transition", lambda: lib.s2s_edge_transition_f16x3(
         _p(edge.buf if in_tiled else edge), _p(node_ab), _p(node_p), _p(wstream), _p(b2), _p(gamma), _p(beta),
         _p(mask),
-        _p(out.buf if isinstance(out, PairTiled) else out), B, N, ln_eps, io, _p(pb), _p(pbias), _p(ppz), int(prescale_exp), _stream())),
+        _p(out.buf if isinstance(out, PairTiled) else out), B, N, ln_eps, io, _p(pb), _p(pbias), _p(ppz), int(prescale_exp),
+        _p(range_flag()), _stream())),
         "s2s_edge_transition_f16x3")
     return out if proj is None else (out, pbias, ppz)
 
@@ -501,11 +500,10 @@ def edge_embed_f16x3(node_a, node_b, rel_table, bin_table, bin_lower, residue_id
         out = PairTiled(B, N, node_a.device) if tiled else torch.empty(B, N, N, 128, device=node_a.device, dtype=torch.float32)
     elif isinstance(out, PairTiled) != tiled:
         raise HipLibraryError("edge_embed_f16x3: out does not have the requested layout")
-    range_flag()
     _check(_timed("s2s_edge_embed", lambda: lib.s2s_edge_embed_f16x3(
         _p(node_a), _p(node_b), _p(rel_table), _p(bin_table), _p(bin_lower), _p(residue_idx), _p(ca), _p(wstream), _p(b2), _p(b3),
         _p(gamma), _p(beta), _p(mask), _p(out.buf if tiled else out), B, N, int(rel_offset), rel_table.shape[1], bin_table.shape[1],
-        ln_eps, 1 if tiled else 0, _p(pb), _p(pbias), _p(ppz), _stream())), "s2s_edge_embed_f16x3")
+        ln_eps, 1 if tiled else 0, _p(pb), _p(pbias), _p(ppz), _p(range_flag()), _stream())), "s2s_edge_embed_f16x3")
     return out if proj is None else (out, pbias, ppz)
 
 
@@ -597,9 +595,9 @@ def ipa_prep_points_f16(rigids7, q_pts_lin, kv_pts_lin, head_w_scaled, n_heads=8
             raise HipLibraryError("ipa_prep_points_f16: s_xp must hold the packed planes of a [B*N, 256] activation")
         v_sh = torch.empty(rt * 32 * 256 * 2, dtype=torch.int16, device=dev)
         k_sh = None if N % 32 == 0 else torch.empty_like(v_sh)
-    range_flag()
     _check(lib.s2s_ipa_prep_points_f16(_p(rigids7), _p(q_pts_lin), _p(kv_pts_lin), _p(head_w_scaled), _p(qp), _p(kp), _p(vp), _p(q2),
-                                       _p(k2), B, N, n_heads, n_qk, n_v, c_hidden, _p(s_xp), _p(k_sh), _p(v_sh), _stream()),
+                                       _p(k2), B, N, n_heads, n_qk, n_v, c_hidden, _p(s_xp), _p(k_sh), _p(v_sh), _p(range_flag()),
+                                       _stream()),
            "s2s_ipa_prep_points_f16")
     return (qp, kp, vp, q2, k2) if s_xp is None else (qp, kp, vp, q2, k2, k_sh, v_sh)
 
@@ -699,8 +697,8 @@ def rigid_scale_trans(rigids7, scale: float, divide: bool = False, out=None):
 
 
 def _ensure_tables():
-    global _tables_loaded
-    if _tables_loaded:
+    dev = torch.cuda.current_device()
+    if dev in _tables_loaded:
         return
     from .data import backbone_tables as bt
 
@@ -711,15 +709,15 @@ def _ensure_tables():
     frm = np.ascontiguousarray(bt.BB_FRAMES, dtype=np.float32)
     _check(lib.s2s_set_backbone_tables(pos.ctypes.data_as(_vp), msk.ctypes.data_as(_vp), grp.ctypes.data_as(_vp),
                                        frm.ctypes.data_as(_vp)), "s2s_set_backbone_tables")
-    _tables_loaded = True
+    _tables_loaded.add(dev)
 
 
 def frames_to_backbone(rigids7, psi, aatype=None, want_atom37=True, want_atom14=False):
     lib = load_library()
-    _ensure_tables()
     _req(rigids7, name="rigids7"); _req(psi, name="psi")
     if aatype is not None:
         _req(aatype, torch.int64, "aatype")
+    _ensure_tables()
     lead = rigids7.shape[:-1]
     dev = rigids7.device
     a37 = torch.empty(*lead, 37, 3, device=dev, dtype=torch.float32) if want_atom37 else None
@@ -890,9 +888,8 @@ def pack_planes(x2d: torch.Tensor, col0: int = 0, n_cols: Optional[int] = None, 
         out = xp_alloc(M, out_k, x2d.device)
     if row_scale is not None:
         _req(row_scale, name="row_scale")
-    range_flag()
-    _check(lib.s2s_pack_planes(_p(x2d), M, ld, col0, n_cols, _p(out), out_k // 16, k0 // 16, _p(row_scale), _stream()),
-           "s2s_pack_planes")
+    _check(lib.s2s_pack_planes(_p(x2d), M, ld, col0, n_cols, _p(out), out_k // 16, k0 // 16, _p(row_scale), _p(range_flag()),
+                               _stream()), "s2s_pack_planes")
     return out
 
 
@@ -932,12 +929,11 @@ def node_linear(xp, wpk, bias, n_rows: int, k_in: int, n_out: int, tiles: int, *
     g, b, eps = ln if ln is not None else (None, None, 0.0)
     if ln is not None:
         _req(g, name="ln.gamma"); _req(b, name="ln.beta")
-    range_flag()
     _check(_timed("s2s_node_linear", lambda: lib.s2s_node_linear(
         _p(xp), _p(wpk), _p(bias), n_rows, k_in, n_out, tiles, _p(pre_scale), int(bool(relu)), _p(pre_mask), _p(residual),
         residual.shape[-1] if residual is not None else 0, _p(g), _p(b), float(eps), _p(post_mask), _p(out_f32),
         out_f32.shape[-1] if out_f32 is not None else 0, out_col0, _p(out_xp), (out_xp_k or 0) // 16, out_xp_k0 // 16,
-        map_pad, map_src, _stream()), flops=2 * n_rows * k_in * n_out), "s2s_node_linear")
+        map_pad, map_src, _p(range_flag()), _stream()), flops=2 * n_rows * k_in * n_out), "s2s_node_linear")
     return out_f32, out_xp
 
 
@@ -990,9 +986,8 @@ def embed_assemble(t_img, node_const, fa, fb, n_samples: int, n_res: int, planes
         raise HipLibraryError("embed_assemble: bad shapes")
     h = xp_alloc(M, 256, dev) if planes else torch.empty(M, 256, device=dev, dtype=torch.float32)
     node_a, node_b = torch.empty(n_samples, n_res, 128, device=dev, dtype=torch.float32), torch.empty_like(fb)
-    range_flag()
     _check(lib.s2s_embed_assemble(_p(t_img), t_img.numel() // 512 if t_img.numel() != 512 else 1, _p(node_const), node_const.numel() // 256, _p(fa), _p(fb), M, n_res, _p(h) if planes else None,
-                                  None if planes else _p(h), _p(node_a), _p(node_b), int(b_col_blocked), _stream()), "s2s_embed_assemble")
+                                  None if planes else _p(h), _p(node_a), _p(node_b), int(b_col_blocked), _p(range_flag()), _stream()), "s2s_embed_assemble")
     return h, node_a, node_b
 
 
@@ -1012,10 +1007,10 @@ def row_layernorm(x, n_rows: int, n_cols: int, gamma, beta, eps: float, post_mas
         out_xp = xp_alloc(n_rows, out_xp_k, dev)
     if out_xp is not None:
         out_xp_k = n_cols if out_xp_k is None else out_xp_k
-    range_flag()
     _check(_timed("s2s_node_linear", lambda: lib.s2s_row_layernorm(
         _p(x), x.shape[-1], n_rows, n_cols, _p(gamma), _p(beta), float(eps), _p(post_mask), _p(out_f32),
-        out_f32.shape[-1] if out_f32 is not None else 0, out_col0, _p(out_xp), (out_xp_k or 0) // 16, out_xp_k0 // 16, _stream())),
+        out_f32.shape[-1] if out_f32 is not None else 0, out_col0, _p(out_xp), (out_xp_k or 0) // 16, out_xp_k0 // 16, _p(range_flag()),
+        _stream())),
         "s2s_row_layernorm")
     return out_f32, out_xp
 
@@ -1076,9 +1071,9 @@ def node_linear_vfrag(xp, wpk, bias, n_rows: int, k_in: int, n_out: int, tiles_p
         out = torch.empty(n_el, dtype=torch.int16, device=xp.device)
     _req(out, torch.int16, "out_vf")
     map_pad, map_src = row_map if row_map is not None else (0, 0)
-    range_flag()
     _check(_timed("s2s_node_linear", lambda: lib.s2s_node_linear_vfrag(_p(xp), _p(wpk), _p(bias), n_rows, k_in, n_out, tiles_per_head,
-                                                                       _p(out), map_pad, map_src, _stream()), flops=2 * n_rows * k_in * n_out),
+                                                                       _p(out), map_pad, map_src, _p(range_flag()), _stream()),
+                  flops=2 * n_rows * k_in * n_out),
            "s2s_node_linear_vfrag")
     return out
 
@@ -1118,8 +1113,7 @@ def node_linear_multi(xp, w, bias, pre_scale, dims, out_f32, out_xp):
         if out_xp[i].numel():
             _req(out_xp[i], torch.int16, "out_xp")
             p.out_xp, p.out_xp_ksteps, p.out_xp_kstep0 = out_xp[i].data_ptr(), xk // 16, xk0 // 16
-    range_flag()
-    _check(_timed("s2s_node_linear", lambda: lib.s2s_node_linear_multi(ctypes.byref(arr), n, _stream()),
+    _check(_timed("s2s_node_linear", lambda: lib.s2s_node_linear_multi(ctypes.byref(arr), n, _p(range_flag()), _stream()),
                   flops=sum(2 * arr[i].n_rows * arr[i].k_in * arr[i].n_out for i in range(n))), "s2s_node_linear_multi")
 
 
@@ -1158,8 +1152,7 @@ def ipa_projections(s_xp, q, k, v, qp, kvp, n_rows: int, n_rows_padded: int, row
         fill(v, n_rows_padded, vfrag_tiles_per_head=tiles_per_head, out_vf=v_vf.data_ptr(), map_pad=mp, map_src=ms)
     fill(qp, n_rows, out_f32=qp_o.data_ptr(), out_ld=qp["n"])
     fill(kvp, n_rows, out_f32=kvp_o.data_ptr(), out_ld=kvp["n"])
-    range_flag()
-    _check(_timed("s2s_node_linear", lambda: lib.s2s_node_linear_multi(ctypes.byref(arr), n, _stream()),
+    _check(_timed("s2s_node_linear", lambda: lib.s2s_node_linear_multi(ctypes.byref(arr), n, _p(range_flag()), _stream()),
                   flops=sum(2 * arr[i].n_rows * arr[i].k_in * arr[i].n_out for i in range(n))), "s2s_node_linear_multi")
     return q_xp, k_xp, v_vf, qp_o, kvp_o
 
@@ -1205,12 +1198,12 @@ def node_chain(xp, w_row, bias, relu, n_rows: int, width: int, pre_mask=None, re
         out_xp = xp_alloc(n_rows, out_xp_k, dev)
     if out_xp is not None:
         out_xp_k = width if out_xp_k is None else out_xp_k
-    range_flag()
     _check(_timed("s2s_node_linear", lambda: lib.s2s_node_chain(
         _p(xp), ctypes.byref(arr), n, n_rows, width, k0, _p(mid_residual), mid_residual.shape[-1] if mid_residual is not None else 0,
         _p(mid_out_f32), mid_out_f32.shape[-1] if mid_out_f32 is not None else 0, _p(mg), _p(mb), float(meps), _p(pre_mask), _p(residual), residual.shape[-1] if residual is not None else 0,
         _p(ln_gamma), _p(ln_beta), float(ln_eps), _p(post_mask), _p(out_f32), out_f32.shape[-1] if out_f32 is not None else 0, out_col0,
-        _p(out_xp), (out_xp_k or 0) // 16, out_xp_k0 // 16, _stream()), flops=2 * n_rows * width * (k0 + (n - 1) * width)), "s2s_node_chain")
+        _p(out_xp), (out_xp_k or 0) // 16, out_xp_k0 // 16, _p(range_flag()), _stream()), flops=2 * n_rows * width * (k0 + (n - 1) * width)),
+        "s2s_node_chain")
     return out_f32, out_xp
 
 
@@ -1308,11 +1301,10 @@ def encoder_attention(qkv: torch.Tensor, key_bias: Optional[torch.Tensor], n_sam
     oxp = xp_alloc(M, D, qkv.device) if want_xp else None
     if arith not in ("f32", "f16x3"):
         raise HipLibraryError(f"encoder_attention: arith {arith!r}")
-    if want_xp or arith == "f16x3":
-        range_flag()
     fn = lib.s2s_encoder_attention_f16x3 if arith == "f16x3" else lib.s2s_encoder_attention
+    rw = _p(range_flag()) if want_xp or arith == "f16x3" else None   # (the fp32 kernel splits only what it writes to out_xp)
     _check(_timed("s2s_encoder_attention", lambda: fn(_p(qkv), _p(key_bias), _p(out), _p(oxp), n_samples, n_res, n_heads, D // n_heads,
-                                                      _stream())), "s2s_encoder_attention")
+                                                      rw, _stream())), "s2s_encoder_attention")
     return out, oxp
 
 

@@ -192,7 +192,7 @@ def denoise_loop(net, diffuser, feats: dict, rigids_t: torch.Tensor, ts, dt: flo
     then per step  network -> fused SE(3) step, last step returns the x0 prediction.  ``host_noise()`` (optional)
     returns the (z_rot, z_trans) float64 [b,N,3] device tensors of a step or None.  -> (atom37, final rigids7, psi).
 
-    Range guard: in the split-f16 arithmetic the pass runs with the library's range flag cleared; if a kernel raised it (an
+    Range guard: in the split-f16 arithmetic the pass runs with its device's range flag cleared; if a kernel raised it (an
     activation reached 2^15 -- f16 tops out at 65504) or the result is not finite, the SAME chunk (same starting frames, same
     noise) is run again with ONLY the kernel families that raised it (str2str_amd/arith.py: node stream, edge transition, edge
     embedding, IPA) on their exact fp32 kernels; a warning is logged once per family and those families stay in fp32 for later
@@ -226,12 +226,12 @@ def _range_guarded(net, run_pass, device, *, host_draws: bool, device_draws: boo
     while True:
         if host_state is not None:
             torch.set_rng_state(host_state)
-        ops.range_flag_reset()
+        ops.range_flag_reset(device)
         try:
             with use_arith(net, "f32", families=tuple(demoted)):
                 out = run_pass()
             finite = bool(torch.isfinite(out[1]).all())     # (the synchronisation point of the chunk)
-            bits = ops.range_flag_read()
+            bits = ops.range_flag_read(device)
             if bits == 0 and finite:
                 return out
             new = set(ops.range_families(bits)) - demoted

@@ -932,7 +932,7 @@ def test_small_node_modules_run_on_the_node_kernel(net_rough):
 
 
 def test_range_guard_flags_every_f16_producer():
-    """Every kernel that splits fp32 values into f16 planes reports a value beyond 2^15 into the library's range flag (one bit per
+    """Every kernel that splits fp32 values into f16 planes reports a value beyond 2^15 into the range flag passed with the call (one bit per
     kernel family, csrc/range_flag.h), and stays quiet on in-range data -- ops level, through the C ABI."""
     from str2str_amd import ops
     from str2str_amd.factory import build_synthetic_net
@@ -985,6 +985,38 @@ def test_range_guard_flags_every_f16_producer():
     for ar in MODES:   # the exact kernel reports what it writes as planes, the f16x3 kernel also the q / k / v it splits
         assert flags(lambda: ops.encoder_attention(qkv, None, 2, 32, arith=ar)) == 0
         assert flags(lambda: ops.encoder_attention(qkv * 1.0e5, None, 2, 32, arith=ar)) == 32
+
+
+def test_range_buffer_is_per_call_across_streams():
+    """The C ABI takes the range guard's buffer with each call (include/str2str_hip.h): two streams with two buffers each see only their
+    own call's report, and a call with range_words = NULL records nothing anywhere."""
+    import ctypes
+
+    from str2str_amd import ops
+
+    lib = ops.load_library()
+    g = torch.Generator().manual_seed(9)
+    M, K = 64, 256
+    ok = torch.randn(M, K, generator=g).to(DEV)
+    big = ok.clone(); big[7, 33] = 4.0e4
+    words_a, words_b = (torch.zeros(8, dtype=torch.int32, device=DEV) for _ in range(2))
+    xp_a, xp_b = ops.xp_alloc(M, K, DEV), ops.xp_alloc(M, K, DEV)
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    ops.range_flag_reset()
+    torch.cuda.synchronize()
+
+    def pack(x, xp, words, stream):
+        assert lib.s2s_pack_planes(ops._p(x), M, K, 0, K, ops._p(xp), K // 16, 0, None, ops._p(words),
+                                   ctypes.c_void_p(stream.cuda_stream)) == 0
+
+    pack(big, xp_a, words_a, sa)
+    pack(ok, xp_b, words_b, sb)
+    torch.cuda.synchronize()
+    assert words_a[0].item() == 2 and not words_b.any()
+    words_a.zero_()
+    pack(big, xp_a, None, sa)
+    torch.cuda.synchronize()
+    assert not words_a.any() and not words_b.any() and not ops.range_flag().any()
 
 
 @pytest.mark.parametrize("where,scale,why,fams", [("et", 8.0e3, "edge transition", ()),

@@ -33,6 +33,18 @@ def test_library_exports_every_declared_symbol(built_library):
     assert lib.s2s_abi_version() == ops.ABI_VERSION
 
 
+def test_every_binding_has_the_arity_of_its_prototype():
+    """ops._SIGNATURES types as many arguments as the header declares for each entry point: a missing one would shift the stream."""
+    from str2str_amd import ops
+
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "str2str_hip.h")).read(), flags=re.S)
+    protos = dict(re.findall(r"^(?:int|long long)\s+(s2s_\w+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M))
+    assert set(protos) == set(ops._SIGNATURES), sorted(set(protos) ^ set(ops._SIGNATURES))
+    for name, params in protos.items():
+        n = 0 if params.strip() in ("", "void") else params.count(",") + 1
+        assert n == len(ops._SIGNATURES[name]), (name, n, len(ops._SIGNATURES[name]))
+
+
 def test_missing_library_fails_loudly(tmp_path):
     from str2str_amd import ops
 
