@@ -42,8 +42,22 @@ def load_model_checkpoint(model, ckpt_path):
     raise ValueError(f"ckpt_path {ckpt_path} is not a valid checkpoint file.")
 
 
-def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None):
-    """reference src/eval.py:47-99: one row per target, one column per metric, plus the mean row."""
+EXTRA_METRICS = ("div_rmsd", "rmsd_recall", "rmsd_precision")   # optional columns (minimum RMSD under optimal superposition)
+
+
+def metric_columns(extra_metrics=None):
+    """The reference's five columns in its order (src/eval.py:64-70), then the requested extra ones in the order asked for."""
+    extra = [extra_metrics] if isinstance(extra_metrics, str) else list(extra_metrics or [])
+    unknown = [m for m in extra if m not in EXTRA_METRICS]
+    if unknown or len(set(extra)) != len(extra):
+        raise ValueError(f"extra_metrics {extra}: expected distinct names out of {list(EXTRA_METRICS)}")
+    return ["val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"] + extra
+
+
+def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None):
+    """reference src/eval.py:47-99: one row per target, one column per metric, plus the mean row.  ``extra_metrics``: names out of
+    EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's)."""
+    columns = metric_columns(extra_metrics)
     from time import strftime
 
     import numpy as np
@@ -60,7 +74,10 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None):
     output_dir = os.path.dirname(os.path.dirname(os.path.abspath(pred_dir)))
     tag = tag if tag is not None else "dev"
     fns = {"val_clash": metrics.validity, "val_bond": metrics.bonding_validity, "js_pwd": metrics.js_pwd, "js_rg": metrics.js_rg,
-           "js_tica": metrics.js_tica}   # the reference's five columns, in its order (src/eval.py:64-70)
+           "js_tica": metrics.js_tica,   # the reference's five columns, in its order (src/eval.py:64-70)
+           "div_rmsd": metrics.diversity_rmsd, "rmsd_recall": lambda ca: metrics.coverage_rmsd(ca, ref_key="target")[0],
+           "rmsd_precision": lambda ca: metrics.coverage_rmsd(ca, ref_key="target")[1]}
+    fns = {k: fns[k] for k in columns}
     eval_res = {k: {} for k in fns}
     for target in targets:
         pred_file = os.path.join(pred_dir, f"{target}.pdb")
@@ -85,7 +102,8 @@ def evaluate(cfg):
     pred_dir = cfg.get("pred_dir")
     if pred_dir and os.path.isdir(pred_dir):
         log.info(f"Found pre-computed prediction directory {pred_dir}.")
-        return evaluate_prediction(pred_dir, target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"))
+        return evaluate_prediction(pred_dir, target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"),
+                                   extra_metrics=cfg.get("extra_metrics"))
     log.info(f"Instantiating datamodule <{cfg.data['_target_']}>")
     datamodule = C.instantiate(cfg.data)
     log.info(f"Instantiating model <{cfg.model['_target_']}>")
@@ -112,7 +130,7 @@ def evaluate(cfg):
     pred_dir = trainer.predict(model=model, dataloaders=dataloaders, ckpt_path=ckpt_path)[-1]
     log.info(f"Samples written under {pred_dir}.")
     if int(os.environ.get("RANK", "0")) == 0 and cfg.get("target_dir"):
-        log.info(f"metrics: {dict(evaluate_prediction(pred_dir, target_dir=cfg.get('target_dir'), tag=cfg.get('task_name')))}")
+        log.info(f"metrics: {dict(evaluate_prediction(pred_dir, target_dir=cfg.get('target_dir'), tag=cfg.get('task_name'), extra_metrics=cfg.get('extra_metrics')))}")
     return pred_dir
 
 

@@ -401,6 +401,32 @@ int s2s_ca_pairwise_distances(const float* ca, int n_samples, int n_res, int off
 int s2s_ca_pwd_js(const float* ref_ca, int n_ref, const float* pred_ca, int n_pred, int n_res, int offset, int n_bins,
                   double pseudo_count, double* js_per_channel, const double* ref_weights, const double* pred_weights, void* stream);
 
+/* ---- Minimum RMSD under optimal rigid superposition (csrc/ensemble_rmsd.hip; no counterpart in the reference) ----
+ * Convention: MSD = min over PROPER rotations R (det R = +1: a mirror image is not superposable) and translations t of
+ * sum_i w_i |R a_i + t - b_i|^2 / sum_i w_i;  rmsd = sqrt(max(MSD, 0)).  weights [n_res] float32 >= 0 with a positive sum, NULL = all ones.
+ * Arithmetic: the float32 coordinates are widened to float64; weighted centroids, G = sum w |x - x-bar|^2, the cross-covariance
+ * H = sum w (a - a-bar)(b - b-bar)^T and the largest eigenvalue lambda of Horn's 4 x 4 quaternion matrix of H (cyclic Jacobi) are all
+ * float64; MSD = (G_a + G_b - 2 lambda) / W.  n_res = 1 gives exactly 0. */
+
+/* All pairs of two ensembles a [n_a, n_res, 3], b [n_b, n_res, 3] -> rmsd [n_a, n_b] float64 (H of 16 x 16 pairs per wave on the
+ * float64 matrix instruction).  b == a with n_b == n_a is the self case: the upper triangle is computed and mirrored.  a may also be a
+ * contiguous run of b's structures (a row chunk of the self matrix): the rows are then bit for bit those of the self matrix, which is
+ * exactly symmetric.  workspace: caller-owned scratch of workspace_doubles >= 2 + r(n_b) + r(n_a) doubles (r(n_a) not needed in the
+ * self case), r(n) = 16 ceil(n / 16) (3 * 4 ceil(n_res / 4) + 1); nothing survives the call.  n_a * n_b < 2^31 and n_a <= 16 * 65535 per
+ * call (the binding chunks rows). */
+int s2s_ca_rmsd_matrix(const float* a, int n_a, const float* b, int n_b, int n_res, const float* weights, double* rmsd,
+                       double* workspace, long long workspace_doubles, void* stream);
+
+/* mobile [n_mobile, n_res, 3] onto target [n_res, 3] -> rmsd [n_mobile] float64 and xform [n_mobile, 12] float64: the row-major rotation R
+ * (from the normalised eigen-quaternion of lambda; any optimal rotation where the eigenspace is degenerate) followed by the translation
+ * t = b-bar - R a-bar, so that R x + t maps mobile onto target. */
+int s2s_ca_superpose(const float* mobile, int n_mobile, const float* target, int n_res, const float* weights, double* rmsd,
+                     double* xform, void* stream);
+
+/* out[s, m] = float32(R_s points[s, m] + t_s) for points [n_samples, n_points, 3] float32 (CA: n_points = n_res; atom37: 37 n_res) and
+ * xform [n_samples, 12] as above, accumulated in float64; out may alias points. */
+int s2s_apply_xform(const float* points, const double* xform, int n_samples, long long n_points, float* out, void* stream);
+
 /* ---- PDB text at the exit of the path (HOST pointers, host code; byte-identical to the reference's writers) ---- */
 
 /* protein.to_pdb per model (src/common/protein.py:152-234) over atom37 [n_models, n_res, 37, 3] float32 HOST coordinates with

@@ -1,0 +1,308 @@
+// Minimum RMSD under optimal rigid superposition, on the device: what users do first with the ensembles the sampler writes
+// (superpose, distance from the start, diversity, coverage of an MD reference, RMSF).  The reference repository has no such
+// function; the yardstick is a float64 SVD Kabsch (tests/test_ensemble_rmsd.py).
+//
+//   s2s_ca_rmsd_matrix   all pairs of two ensembles.  With weighted centroids a-bar, b-bar and centred coordinates,
+//                          MSD = (G_a + G_b - 2 lambda) / W,   G = sum_i w_i |x_i - x-bar|^2,   W = sum_i w_i,
+//                        lambda = the largest eigenvalue of Horn's symmetric 4 x 4 matrix built from the nine entries of
+//                        H_ab = sum_i w_i (a_i - a-bar)(b_i - b-bar)^T: the maximum of tr(R H) over PROPER rotations (det R = +1; a
+//                        mirror image is not superposable).  All H of a 16 x 16 block of pairs are one [48, L] x [L, 48] float64
+//                        matrix product on v_mfma_f64_16x16x4_f64: nine accumulator tiles, tile (c_a, c_b) = H[c_a][c_b] of the 256 pairs,
+//                        so every lane ends the loop over residues holding the complete H of its four pairs.
+//   s2s_ca_superpose     many mobile structures onto one target: RMSD and the transform (rotation from the eigen-quaternion).
+//   s2s_apply_xform      one transform per sample applied to float32 points.
+//
+// Everything is float64 (the float32 inputs are widened first): the MSD is the small difference of numbers of size L Rg^2, and a
+// float32 evaluation of the same formula errs by 1e-3 .. 1e-2 A in RMSD between near-identical conformations.
+// Eigenvalues by cyclic Jacobi on the 4 x 4: it converges on identical structures, mirror images, collinear / planar chains and
+// L = 1, 2, 3, where Newton on the characteristic quartic from (G_a + G_b) / 2 stalls on the (near-)multiple root.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "str2str_hip.h"
+
+namespace {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// One Jacobi rotation in the (P, Q) plane of the symmetric a (both triangles kept) and, with VEC, of the eigenvector columns v.
+template <int P, int Q, bool VEC>
+__device__ __forceinline__ bool jacobi_rotate(double (&a)[4][4], double (&v)[4][4], double thr) {
+    const double apq = a[P][Q];
+    if (!(fabs(apq) > thr)) return false;
+    const double d = a[Q][Q] - a[P][P], b = 2.0 * apq;
+    const double t = (d >= 0.0 ? b : -b) / (fabs(d) + sqrt(d * d + b * b));   // the smaller root of t^2 + 2 t theta - 1, theta = d / b
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    a[P][P] -= t * apq;
+    a[Q][Q] += t * apq;
+    a[P][Q] = a[Q][P] = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (r != P && r != Q) {
+            const double g = a[r][P], h = a[r][Q];
+            a[r][P] = a[P][r] = c * g - s * h;
+            a[r][Q] = a[Q][r] = s * g + c * h;
+        }
+        if (VEC) {
+            const double g = v[r][P], h = v[r][Q];
+            v[r][P] = c * g - s * h;
+            v[r][Q] = s * g + c * h;
+        }
+    }
+    return true;
+}
+
+// Cyclic Jacobi on a symmetric 4 x 4: sweeps until no off-diagonal entry exceeds 2^-58 ||a||_F (what is left moves an eigenvalue by
+// far less than one rounding of ||a||), at most 16 sweeps (convergence is quadratic; 5-7 in practice).  a's diagonal = eigenvalues.
+template <bool VEC>
+__device__ __forceinline__ void jacobi4(double (&a)[4][4], double (&v)[4][4]) {
+    double n2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            n2 += a[i][j] * a[i][j];
+            if (VEC) v[i][j] = i == j ? 1.0 : 0.0;
+        }
+    if (!(n2 > 1e-260)) return;   // (a zero matrix; also keeps d*d + b*b above the underflow range)
+    const double thr = sqrt(n2) * 0x1p-58;
+    for (int sweep = 0; sweep < 16; ++sweep) {
+        bool any = false;
+        any |= jacobi_rotate<0, 1, VEC>(a, v, thr);
+        any |= jacobi_rotate<0, 2, VEC>(a, v, thr);
+        any |= jacobi_rotate<0, 3, VEC>(a, v, thr);
+        any |= jacobi_rotate<1, 2, VEC>(a, v, thr);
+        any |= jacobi_rotate<1, 3, VEC>(a, v, thr);
+        any |= jacobi_rotate<2, 3, VEC>(a, v, thr);
+        if (!any) break;
+    }
+}
+
+// Horn's matrix of H[i][j] = sum w a_i b_j (the rotation takes a onto b); quaternion order (w, x, y, z).
+__device__ __forceinline__ void horn_matrix(const double (&h)[3][3], double (&k)[4][4]) {
+    k[0][0] = h[0][0] + h[1][1] + h[2][2];
+    k[1][1] = h[0][0] - h[1][1] - h[2][2];
+    k[2][2] = -h[0][0] + h[1][1] - h[2][2];
+    k[3][3] = -h[0][0] - h[1][1] + h[2][2];
+    k[0][1] = k[1][0] = h[1][2] - h[2][1];
+    k[0][2] = k[2][0] = h[2][0] - h[0][2];
+    k[0][3] = k[3][0] = h[0][1] - h[1][0];
+    k[1][2] = k[2][1] = h[0][1] + h[1][0];
+    k[1][3] = k[3][1] = h[2][0] + h[0][2];
+    k[2][3] = k[3][2] = h[1][2] + h[2][1];
+}
+
+__device__ __forceinline__ double max_diag(const double (&k)[4][4]) {
+    return fmax(fmax(k[0][0], k[1][1]), fmax(k[2][2], k[3][3]));
+}
+
+// Prepass, one wave per structure slot (slots n .. 16 ceil(n/16) - 1 and residues L .. Lp - 1 are zero padding): weighted centroid, G, and
+// sqrt(w_i) (x_i - x-bar) as float64 in blocks of 16 structures, out[(blk * Lp + i) * 48 + 16 c + s].  The SAME scaled coordinates serve
+// as either operand of the product, so H_ba is the transpose of H_ab bit for bit (products commute, the sums run in one order).
+__global__ void __launch_bounds__(64) rmsd_prep_kernel(const float* __restrict__ x, int n, int L, int Lp, const float* __restrict__ w,
+                                                       double* __restrict__ g_out, double* __restrict__ out, double* __restrict__ w_sum) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    double* o = out + ((size_t)(s >> 4) * Lp) * 48 + (s & 15);
+    if (s >= n) {
+        for (int i = lane; i < Lp; i += 64) { o[(size_t)i * 48] = 0.0; o[(size_t)i * 48 + 16] = 0.0; o[(size_t)i * 48 + 32] = 0.0; }
+        if (lane == 0) g_out[s] = 0.0;
+        return;
+    }
+    const float* p = x + (size_t)s * L * 3;
+    double sw = 0, sx = 0, sy = 0, sz = 0;
+    for (int i = lane; i < L; i += 64) {
+        const double wi = w ? (double)w[i] : 1.0;
+        sw += wi; sx += wi * p[3 * i]; sy += wi * p[3 * i + 1]; sz += wi * p[3 * i + 2];
+    }
+    sw = wave_sum(sw); sx = wave_sum(sx); sy = wave_sum(sy); sz = wave_sum(sz);
+    const double cx = sx / sw, cy = sy / sw, cz = sz / sw;
+    double g = 0;
+    for (int i = lane; i < Lp; i += 64) {
+        double dx = 0, dy = 0, dz = 0;
+        if (i < L) {
+            const double wi = w ? (double)w[i] : 1.0, r = w ? sqrt(wi) : 1.0;
+            dx = p[3 * i] - cx; dy = p[3 * i + 1] - cy; dz = p[3 * i + 2] - cz;
+            g += wi * (dx * dx + dy * dy + dz * dz);
+            dx *= r; dy *= r; dz *= r;
+        }
+        o[(size_t)i * 48] = dx; o[(size_t)i * 48 + 16] = dy; o[(size_t)i * 48 + 32] = dz;
+    }
+    g = wave_sum(g);
+    if (lane == 0) {
+        g_out[s] = g;
+        if (s == 0 && w_sum) *w_sum = sw;
+    }
+}
+
+// One wave per 16 x 16 block of pairs (A block = blockIdx.y, B block = 4 blockIdx.x + wave).  MFMA operands (lane maps of the f64
+// 16x16x4 form): lane l feeds A[row = l & 15][k = l >> 4] and B[k = l >> 4][col = l & 15], and receives D[row = (l >> 4) + 4 r][col = l & 15]
+// in register r.  row0 >= 0: the A ensemble is rows row0 .. of the B ensemble (a row chunk of a self matrix); a pair below the diagonal is
+// then evaluated as its mirror pair (H transposed in registers), so the matrix is exactly symmetric and independent of the chunking.
+// mirror: the whole self matrix in one launch -- blocks below the diagonal are skipped and written by their mirror block.
+__global__ void __launch_bounds__(256) rmsd_pairs_kernel(const double* __restrict__ a_buf, const double* __restrict__ g_a, int n_a,
+                                                         const double* __restrict__ b_buf, const double* __restrict__ g_b, int n_b, int L,
+                                                         int Lp, const double* __restrict__ w_sum, long long row0, int mirror,
+                                                         double* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bi = blockIdx.y, bj = blockIdx.x * 4 + wave;
+    if (bj >= (n_b + 15) / 16) return;   // wave-uniform; no block-level synchronisation in this kernel
+    if (mirror && bi > bj) return;
+    const int q = lane >> 4, col = lane & 15;
+    const double* pa = a_buf + (size_t)bi * Lp * 48 + q * 48 + col;
+    const double* pb = b_buf + (size_t)bj * Lp * 48 + q * 48 + col;
+    d4 acc[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < Lp; k0 += 4) {
+        double av[3], bv[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { av[c] = pa[16 * c]; bv[c] = pb[16 * c]; }
+        pa += 192; pb += 192;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i], bv[j], acc[i][j], 0, 0, 0);
+    }
+    const double W = *w_sum;
+    const int gj = bj * 16 + col;
+    const double gb = g_b[gj];   // (the G arrays are padded to whole blocks)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int gi = bi * 16 + q + 4 * r;
+        if (gi >= n_a || gj >= n_b) continue;
+        const bool swap = row0 >= 0 && row0 + gi > gj;
+        double h[3][3], k[4][4], v[4][4];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) h[i][j] = swap ? acc[j][i][r] : acc[i][j][r];
+        horn_matrix(h, k);
+        jacobi4<false>(k, v);
+        const double msd = L == 1 ? 0.0 : (g_a[gi] + gb - 2.0 * max_diag(k)) / W;   // (one point superposes exactly)
+        const double rmsd = sqrt(fmax(msd, 0.0));
+        out[(size_t)gi * n_b + gj] = rmsd;
+        if (mirror && bi < bj) out[(size_t)gj * n_b + gi] = rmsd;
+    }
+}
+
+// One wave per mobile structure; every lane repeats the 4 x 4 eigenproblem (no divergence), lane 0 writes.
+__global__ void __launch_bounds__(64) superpose_kernel(const float* __restrict__ mobile, int L, const float* __restrict__ target,
+                                                       const float* __restrict__ w, double* __restrict__ rmsd, double* __restrict__ xform) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const float* m = mobile + (size_t)s * L * 3;
+    double sw = 0, cm[3] = {0, 0, 0}, ct[3] = {0, 0, 0};
+    for (int i = lane; i < L; i += 64) {
+        const double wi = w ? (double)w[i] : 1.0;
+        sw += wi;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { cm[c] += wi * m[3 * i + c]; ct[c] += wi * target[3 * i + c]; }
+    }
+    sw = wave_sum(sw);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { cm[c] = wave_sum(cm[c]) / sw; ct[c] = wave_sum(ct[c]) / sw; }
+    double h[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, g = 0;
+    for (int i = lane; i < L; i += 64) {
+        const double wi = w ? (double)w[i] : 1.0;
+        double a[3], b[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { a[c] = m[3 * i + c] - cm[c]; b[c] = target[3 * i + c] - ct[c]; }
+        g += wi * (a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double wa = wi * a[c];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) h[c][e] += wa * b[e];
+        }
+    }
+    g = wave_sum(g);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) h[c][e] = wave_sum(h[c][e]);
+    double k[4][4], v[4][4];
+    horn_matrix(h, k);
+    jacobi4<true>(k, v);
+    const double lam = max_diag(k);
+    double qv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) qv[r] = k[0][0] == lam ? v[r][0] : k[1][1] == lam ? v[r][1] : k[2][2] == lam ? v[r][2] : v[r][3];
+    const double qn = 1.0 / sqrt(qv[0] * qv[0] + qv[1] * qv[1] + qv[2] * qv[2] + qv[3] * qv[3]);
+    const double qw = qv[0] * qn, qx = qv[1] * qn, qy = qv[2] * qn, qz = qv[3] * qn;
+    double R[3][3];
+    R[0][0] = 1.0 - 2.0 * (qy * qy + qz * qz); R[0][1] = 2.0 * (qx * qy - qw * qz); R[0][2] = 2.0 * (qx * qz + qw * qy);
+    R[1][0] = 2.0 * (qx * qy + qw * qz); R[1][1] = 1.0 - 2.0 * (qx * qx + qz * qz); R[1][2] = 2.0 * (qy * qz - qw * qx);
+    R[2][0] = 2.0 * (qx * qz - qw * qy); R[2][1] = 2.0 * (qy * qz + qw * qx); R[2][2] = 1.0 - 2.0 * (qx * qx + qy * qy);
+    if (lane == 0) {
+        const double msd = L == 1 ? 0.0 : (g - 2.0 * lam) / sw;
+        rmsd[s] = sqrt(fmax(msd, 0.0));
+        double* o = xform + (size_t)s * 12;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            o[3 * c] = R[c][0]; o[3 * c + 1] = R[c][1]; o[3 * c + 2] = R[c][2];
+            o[9 + c] = ct[c] - (R[c][0] * cm[0] + R[c][1] * cm[1] + R[c][2] * cm[2]);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) apply_xform_kernel(const float* __restrict__ pts, const double* __restrict__ xform, long long n_total,
+                                                          long long M, float* __restrict__ out) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_total) return;
+    const double* t = xform + (idx / M) * 12;
+    const double x = pts[3 * idx], y = pts[3 * idx + 1], z = pts[3 * idx + 2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[3 * idx + c] = (float)(t[3 * c] * x + t[3 * c + 1] * y + t[3 * c + 2] * z + t[9 + c]);
+}
+
+inline long long region_doubles(long long n, long long Lp) { return ((n + 15) / 16) * 16 * (3 * Lp + 1); }
+
+}  // namespace
+
+extern "C" int s2s_ca_rmsd_matrix(const float* a, int n_a, const float* b, int n_b, int n_res, const float* weights, double* rmsd,
+                                  double* workspace, long long workspace_doubles, void* stream) {
+    if (!a || !b || !rmsd || !workspace || n_a < 1 || n_b < 1 || n_res < 1) return (int)hipErrorInvalidValue;
+    const long long Lp = ((long long)n_res + 3) / 4 * 4, nba = ((long long)n_a + 15) / 16, nbb = ((long long)n_b + 15) / 16;
+    if ((long long)n_a * n_b >= (1ll << 31) || nba > 65535) return (int)hipErrorInvalidValue;
+    const bool whole = a == b && n_a == n_b;
+    const long long need = 2 + region_doubles(n_b, Lp) + (whole ? 0 : region_doubles(n_a, Lp));
+    if (workspace_doubles < need) return (int)hipErrorInvalidValue;
+    // a inside b's storage on a structure boundary = a row chunk of the self matrix
+    long long row0 = -1;
+    const long long stride = 3ll * n_res;
+    if (a >= b && a - b < stride * n_b && (a - b) % stride == 0 && (a - b) / stride + n_a <= n_b) row0 = (a - b) / stride;
+    hipStream_t st = (hipStream_t)stream;
+    double* gb = workspace + 2;
+    double* cb = gb + nbb * 16;
+    double* ga = whole ? gb : cb + nbb * Lp * 48;
+    double* ca = whole ? cb : ga + nba * 16;
+    hipLaunchKernelGGL(rmsd_prep_kernel, dim3((unsigned)(nbb * 16)), dim3(64), 0, st, b, n_b, n_res, (int)Lp, weights, gb, cb, workspace);
+    if (!whole)
+        hipLaunchKernelGGL(rmsd_prep_kernel, dim3((unsigned)(nba * 16)), dim3(64), 0, st, a, n_a, n_res, (int)Lp, weights, ga, ca,
+                           (double*)nullptr);
+    hipLaunchKernelGGL(rmsd_pairs_kernel, dim3((unsigned)((nbb + 3) / 4), (unsigned)nba), dim3(256), 0, st, ca, ga, n_a, cb, gb, n_b, n_res,
+                       (int)Lp, workspace, row0, whole ? 1 : 0, rmsd);
+    return (int)hipGetLastError();
+}
+
+extern "C" int s2s_ca_superpose(const float* mobile, int n_mobile, const float* target, int n_res, const float* weights, double* rmsd,
+                                double* xform, void* stream) {
+    if (!mobile || !target || !rmsd || !xform || n_mobile < 1 || n_res < 1) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(superpose_kernel, dim3((unsigned)n_mobile), dim3(64), 0, (hipStream_t)stream, mobile, n_res, target, weights, rmsd,
+                       xform);
+    return (int)hipGetLastError();
+}
+
+extern "C" int s2s_apply_xform(const float* points, const double* xform, int n_samples, long long n_points, float* out, void* stream) {
+    if (!points || !xform || !out || n_samples < 1 || n_points < 1) return (int)hipErrorInvalidValue;
+    const long long total = (long long)n_samples * n_points, blocks = (total + 255) / 256;
+    if (blocks >= (1ll << 31)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(apply_xform_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, points, xform, total, n_points, out);
+    return (int)hipGetLastError();
+}

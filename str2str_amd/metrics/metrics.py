@@ -9,6 +9,10 @@ projection -- deeptime's estimator when it is installed (the reference's), other
 deeptime 0.4.4's conventions -- reversible covariances, absolute 1e-6 cut-off, eigenpairs by descending magnitude, canonical signs,
 kinetic-map scaling -- so that the projections themselves, not only the score, are the reference's).  Per-sample ``weights=``
 (:139-150,178-179,206-208) are histogram weights on both paths.
+
+Not in the reference (its paper's diversity figures came from external tools): minimum RMSD under optimal rigid superposition --
+``pairwise_rmsd``, ``diversity_rmsd``, ``coverage_rmsd``, ``superpose``, ``rmsf`` -- on csrc/ensemble_rmsd.hip.  Proper rotations only
+(a mirror image is not superposable), float64 arithmetic on the float32 coordinates, optional per-RESIDUE weights.
 """
 from __future__ import annotations
 
@@ -158,3 +162,69 @@ def js_tica(ca_coords_dict, ref_key="target", n_bins=50, lagtime=20, return_tic=
     if return_tic:
         return results, ca_dr2d
     return results
+
+
+# ---- minimum RMSD under optimal superposition (csrc/ensemble_rmsd.hip) -----------------------------------------------------------
+COVERAGE_CHUNK_PAIRS = 1 << 24   # pairs per launch of coverage_rmsd: 128 MiB of float64 RMSDs at a time, whatever the ensembles' sizes
+
+
+def pairwise_rmsd(a, b=None, weights=None) -> np.ndarray:
+    """Minimum RMSD of every structure of ``a`` [Ra, L, 3] against every structure of ``b`` [Rb, L, 3] (default: ``a`` itself; the self
+    matrix is exactly symmetric) -> float64 [Ra, Rb]."""
+    return ops.ca_rmsd_matrix(_dev(a), None if b is None else _dev(b), weights).cpu().numpy()
+
+
+def diversity_rmsd(ca_coords_dict, weights=None):
+    """Ensemble diversity: the mean RMSD over the pairs i < j of each ensemble (0.0 for a single structure)."""
+    out = {}
+    for k, v in ca_coords_dict.items():
+        x = _dev(v)
+        n = x.shape[0]
+        # (the matrix is symmetric with a diagonal of rounding size, which the upper-triangle sum leaves out)
+        out[k] = np.around(float(torch.triu(ops.ca_rmsd_matrix(x, None, weights), diagonal=1).sum()) / (n * (n - 1) / 2), decimals=4) if n > 1 else 0.0
+    return out
+
+
+def _coverage_minima(samples: torch.Tensor, ref: torch.Tensor, weights=None, chunk_pairs=None):
+    """(per reference frame: min RMSD to any sample, per sample: min RMSD to any reference frame), device float64, over row chunks of
+    the sample x reference matrix with running minima: the matrix itself is never held."""
+    rows = ops.rmsd_row_chunk(ref.shape[0], COVERAGE_CHUNK_PAIRS if chunk_pairs is None else chunk_pairs)
+    per_ref = torch.full((ref.shape[0],), float("inf"), dtype=torch.float64, device=ref.device)
+    per_sample = torch.empty(samples.shape[0], dtype=torch.float64, device=ref.device)
+    for r0 in range(0, samples.shape[0], rows):
+        m = ops.ca_rmsd_matrix(samples[r0:r0 + rows], ref, weights)
+        per_sample[r0:r0 + rows] = m.min(dim=1).values
+        per_ref = torch.minimum(per_ref, m.min(dim=0).values)
+    return per_ref, per_sample
+
+
+def coverage_rmsd(ca_coords_dict, ref_key="target", weights=None, chunk_pairs=None):
+    """How well each ensemble covers the reference ensemble -> (recall, precision): recall[k] = mean over reference frames of the
+    minimum RMSD to any sample of k, precision[k] = mean over samples of k of the minimum RMSD to any reference frame."""
+    ref = _dev(ca_coords_dict[ref_key])
+    recall, precision = {}, {}
+    for k, v in ca_coords_dict.items():
+        if k == ref_key:
+            continue
+        per_ref, per_sample = _coverage_minima(_dev(v), ref, weights, chunk_pairs)
+        recall[k] = np.around(float(per_ref.mean()), decimals=4)
+        precision[k] = np.around(float(per_sample.mean()), decimals=4)
+    recall[ref_key] = precision[ref_key] = 0.0
+    return recall, precision
+
+
+def superpose(coords, target, weights=None):
+    """Every structure of ``coords`` [R, L, 3] moved onto ``target`` [L, 3] by its optimal proper rotation + translation
+    -> (aligned float32 [R, L, 3], rmsd float64 [R])."""
+    x = _dev(coords)
+    rmsd, xform = ops.ca_superpose(x, _dev(target)[0], weights)
+    return ops.apply_xform(x, xform).cpu().numpy(), rmsd.cpu().numpy()
+
+
+def rmsf(coords, target=None, weights=None) -> np.ndarray:
+    """Per-residue root-mean-square fluctuation of an ensemble [R, L, 3] after superposition on ``target`` (default: its first
+    structure): sqrt(mean over samples |x - mean x|^2) -> float64 [L]."""
+    x = _dev(coords)
+    rmsd, xform = ops.ca_superpose(x, x[0] if target is None else _dev(target)[0], weights)
+    y = ops.apply_xform(x, xform).double()
+    return (y - y.mean(0, keepdim=True)).square().sum(-1).mean(0).sqrt().cpu().numpy()
