@@ -1,0 +1,119 @@
+"""Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD and superposition."""
+from typing import Optional
+
+import torch
+
+from .binding import HipLibraryError, _check, _p, _req, _stream, load_library
+
+RMSD_LAUNCH_PAIRS = 2 ** 31 - 1   # s2s_ca_rmsd_matrix takes fewer than 2^31 pairs per call
+
+
+def ca_sample_stats(ca: torch.Tensor, clash_bar: float = 3.0, k_exclusion: int = 0):
+    """CA [R, L, 3] fp32 device tensor -> (n_clash [R] int32, adjacent_max [R] fp32, radius_of_gyration [R] fp64)."""
+    lib = load_library()
+    _req(ca, name="ca")
+    R, L = ca.shape[:2]
+    nc = torch.empty(R, dtype=torch.int32, device=ca.device)
+    am = torch.empty(R, dtype=torch.float32, device=ca.device)
+    rg = torch.empty(R, dtype=torch.float64, device=ca.device)
+    _check(lib.s2s_ca_sample_stats(_p(ca), R, L, float(clash_bar), int(k_exclusion), _p(nc), _p(am), _p(rg), _stream()), "s2s_ca_sample_stats")
+    return nc, am, rg
+
+
+def ca_pairwise_distances(ca: torch.Tensor, offset: int = 1) -> torch.Tensor:
+    """Upper-triangular CA distances [R, D] float32 of every sample (np.triu_indices(L, k=offset) order) in numpy's float32 arithmetic."""
+    lib = load_library()
+    _req(ca, name="ca")
+    R, L = ca.shape[0], ca.shape[1]
+    if ca.ndim != 3 or ca.shape[2] != 3 or L <= offset:
+        raise HipLibraryError(f"ca_pairwise_distances: coordinates {tuple(ca.shape)}, offset {offset}")
+    D = (L - offset) * (L - offset + 1) // 2
+    out = torch.empty(R, D, dtype=torch.float32, device=ca.device)
+    for r0 in range(0, R, 65535):
+        n = min(65535, R - r0)
+        _check(lib.s2s_ca_pairwise_distances(_p(ca[r0:r0 + n]), n, L, int(offset), _p(out[r0:r0 + n]), _stream()), "s2s_ca_pairwise_distances")
+    return out
+
+
+def ca_pwd_js(ref_ca: torch.Tensor, pred_ca: torch.Tensor, offset: int = 3, n_bins: int = 50, pseudo: float = 1e-6,
+              ref_weights: Optional[torch.Tensor] = None, pred_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per pair channel Jensen-Shannon distance between the distance histograms of two CA ensembles -> [D] fp64.
+    ``ref_weights`` / ``pred_weights``: per-sample float64 histogram weights (device tensors), None = ones."""
+    lib = load_library()
+    _req(ref_ca, name="ref_ca"); _req(pred_ca, name="pred_ca")
+    L = ref_ca.shape[1]
+    if pred_ca.shape[1] != L:
+        raise HipLibraryError("ca_pwd_js: the ensembles have different lengths")
+    for nme, w, n in (("ref_weights", ref_weights, ref_ca.shape[0]), ("pred_weights", pred_weights, pred_ca.shape[0])):
+        if w is not None:
+            _req(w, torch.float64, nme)
+            if w.numel() != n:
+                raise HipLibraryError(f"ca_pwd_js: {nme} has {w.numel()} entries for {n} samples")
+    out = torch.empty((L - offset) * (L - offset + 1) // 2, dtype=torch.float64, device=ref_ca.device)
+    _check(lib.s2s_ca_pwd_js(_p(ref_ca), ref_ca.shape[0], _p(pred_ca), pred_ca.shape[0], L, int(offset), int(n_bins), float(pseudo),
+                             _p(out), _p(ref_weights), _p(pred_weights), _stream()), "s2s_ca_pwd_js")
+    return out
+
+
+def _rmsd_weights(weights, L: int, device):
+    if weights is None:
+        return None
+    w = torch.as_tensor(weights).to(device, torch.float32).contiguous()
+    if w.shape != (L,):
+        raise HipLibraryError(f"weights: expected [{L}] (one per residue), got {tuple(w.shape)}")
+    return w
+
+
+def rmsd_row_chunk(n_b: int, max_pairs: Optional[int] = None) -> int:
+    """Rows of A per s2s_ca_rmsd_matrix call so that one call stays within ``max_pairs`` pairs (at least one row)."""
+    cap = RMSD_LAUNCH_PAIRS if max_pairs is None else min(int(max_pairs), RMSD_LAUNCH_PAIRS)
+    return max(1, min(cap // n_b, 16 * 65535))
+
+
+def ca_rmsd_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, weights=None, max_pairs: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Minimum RMSD (optimal proper rotation + translation, float64) of every pair of a [Ra, L, 3] and b [Rb, L, 3] fp32 device tensors
+    -> [Ra, Rb] fp64.  ``b=None``: the self matrix of ``a`` (exactly symmetric).  ``weights``: per-residue [L], >= 0.  ``max_pairs``
+    bounds the pairs (and with them the scratch) of one launch: rows are chunked, the result is bit for bit the same for any value.
+    The caller bounds Ra x Rb (the output); metrics.coverage_rmsd shows the chunked use that never holds the whole matrix."""
+    lib = load_library()
+    _req(a, name="a")
+    b = a if b is None else _req(b, name="b")
+    if a.ndim != 3 or b.ndim != 3 or a.shape[2] != 3 or b.shape[1:] != a.shape[1:] or a.shape[0] < 1 or b.shape[0] < 1 or a.shape[1] < 1:
+        raise HipLibraryError(f"ca_rmsd_matrix: coordinates {tuple(a.shape)} and {tuple(b.shape)}")
+    (n_a, L), n_b = a.shape[:2], b.shape[0]
+    w = _rmsd_weights(weights, L, a.device)
+    out = torch.empty(n_a, n_b, dtype=torch.float64, device=a.device) if out is None else out
+    rows = rmsd_row_chunk(n_b, max_pairs)
+    region = lambda n: -(-n // 16) * 16 * (3 * (-(-L // 4) * 4) + 1)  # noqa: E731
+    ws = torch.empty(2 + region(n_b) + region(min(rows, n_a)), dtype=torch.float64, device=a.device)
+    for r0 in range(0, n_a, rows):
+        n = min(rows, n_a - r0)
+        _check(lib.s2s_ca_rmsd_matrix(_p(a[r0:r0 + n]), n, _p(b), n_b, L, _p(w), _p(out[r0:r0 + n]), _p(ws), ws.numel(), _stream()), "s2s_ca_rmsd_matrix")
+    return out
+
+
+def ca_superpose(mobile: torch.Tensor, target: torch.Tensor, weights=None):
+    """mobile [R, L, 3] onto target [L, 3] (fp32 device tensors) -> (rmsd [R] fp64, xform [R, 12] fp64: row-major proper rotation, then
+    translation; rotation @ x + translation maps mobile onto target)."""
+    lib = load_library()
+    _req(mobile, name="mobile"); _req(target, name="target")
+    if mobile.ndim != 3 or mobile.shape[2] != 3 or target.shape != mobile.shape[1:] or mobile.shape[0] < 1 or mobile.shape[1] < 1:
+        raise HipLibraryError(f"ca_superpose: mobile {tuple(mobile.shape)}, target {tuple(target.shape)}")
+    R, L = mobile.shape[:2]
+    w = _rmsd_weights(weights, L, mobile.device)
+    rmsd = torch.empty(R, dtype=torch.float64, device=mobile.device)
+    xform = torch.empty(R, 12, dtype=torch.float64, device=mobile.device)
+    _check(lib.s2s_ca_superpose(_p(mobile), R, _p(target), L, _p(w), _p(rmsd), _p(xform), _stream()), "s2s_ca_superpose")
+    return rmsd, xform
+
+
+def apply_xform(points: torch.Tensor, xform: torch.Tensor) -> torch.Tensor:
+    """points [R, M, 3] fp32, xform [R, 12] fp64 (ca_superpose) -> rotation @ point + translation, float64 arithmetic, fp32 result."""
+    lib = load_library()
+    _req(points, name="points"); _req(xform, torch.float64, "xform")
+    if points.ndim != 3 or points.shape[2] != 3 or xform.shape != (points.shape[0], 12) or points.shape[0] < 1 or points.shape[1] < 1:
+        raise HipLibraryError(f"apply_xform: points {tuple(points.shape)}, xform {tuple(xform.shape)}")
+    out = torch.empty_like(points)
+    _check(lib.s2s_apply_xform(_p(points), _p(xform), points.shape[0], points.shape[1], _p(out), _stream()), "s2s_apply_xform")
+    return out

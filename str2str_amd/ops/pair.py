@@ -1,0 +1,151 @@
+"""Pair stream: edge transition, edge embedding and the pair projection of an IPA block."""
+import torch
+
+from .binding import HipLibraryError, _check, _p, _req, _req_all, _req_opt, _stream, _timed, load_library
+from .packing import PairTiled, column_blocked
+from .range_guard import range_flag
+
+
+def _proj_outputs(proj, B, N, dev, dtype=torch.float32, name="proj.wp"):
+    """``proj`` = (weights, bias64) of the next IPA block, fused into a pair kernel -> (weights, bias64, attn_bias [B,8,N,N] (head-major),
+    pair_z [B,N,N,32]) with the two outputs allocated here, or four Nones."""
+    if proj is None:
+        return None, None, None, None
+    w, b64 = proj
+    _req(w, dtype, name); _req(b64, name="proj.b64")
+    return w, b64, torch.empty(B, 8, N, N, device=dev, dtype=torch.float32), torch.empty(B, N, N, 32, device=dev, dtype=torch.float32)
+
+
+def edge_transition_f16x3(edge, node_ab, node_p, wstream, b2, gamma, beta, mask, ln_eps=1e-5, out=None, proj=None,
+                          out_layout: str = "rowmajor", prescale_exp: int = 0, ab_kernel_form: bool = False):
+    """EdgeTransition on split-f16 MFMA (fp32-equivalent accuracy; csrc/pair_mlp_f16.hip); same contract as ``edge_transition``.
+    ``proj`` = (31-stage stream = this layer's 30 stages (``pack_f16x3_stream``) + the next IPA block's projection stage
+    (``pack_f16x2_layer``), bias64) also returns that block's (attn_bias [B,8,N,N], pair_z [B,N,N,32]).
+    ``edge`` may be a ``PairTiled``; ``out_layout``: "rowmajor" (the reference's tensor), "tiled" (-> ``PairTiled``) or "none" (the pair
+    vectors are not written: only with ``proj``, for the last EdgeTransition of a trunk; returns None in their place).
+    ``prescale_exp`` = e (0 .. 15): the kernel keeps its hidden activations as f16 planes of 2^-e x the value (a block exponent: exact,
+    same speed) -- what the sampler sets when the range guard reports hidden activations of 2^15 and beyond.
+    ``node_ab`` [B,N,896] = [W1[:,128:256] n' + b1 | W1[:,256:] n' | Wf[:,256:] n' + bf] as ``EdgeTransition.node_parts`` gives it (the
+    pair's per-node linear parts: row half and column half of the first layer, the j-side residual taken through the final layer incl.
+    its bias); ``ab_kernel_form``: the column half and the third group already carry the accumulators' 2^5 (the trunk's per-node layers
+    produce them so: no extra launch), see the C header."""
+    lib = load_library()
+    B, N = edge.shape[0], edge.shape[1]
+    in_tiled = isinstance(edge, PairTiled)
+    if not 0 <= int(prescale_exp) <= 15:
+        raise HipLibraryError(f"edge_transition_f16x3: prescale_exp {prescale_exp} outside 0 .. 15")
+    # C ABI: node_ab = [2^-e (A_i + b1) | 2^5 B_j | 2^(5-e) G_j] -- the row half at the planes' scale, the column half and the final layer's
+    # start values at the accumulators' (the caller's job)
+    if tuple(edge.shape) != (B, N, N, 128) or tuple(node_ab.shape) != (B, N, 896) or tuple(node_p.shape) != (B, N, 128):
+        raise HipLibraryError(f"edge_transition_f16x3: bad shapes (edge {tuple(edge.shape)}, node_ab {tuple(node_ab.shape)}, node_p {tuple(node_p.shape)}): "
+                              "edge is [B, N, N, 128], node_p [B, N, 128] and node_ab [B, N, 896] = EdgeTransition.node_parts (row half | column half | "
+                              "j-side residual through the final layer; the 768-column form of earlier ABI versions is not accepted)")
+    if not ab_kernel_form or prescale_exp:
+        sc = node_ab.new_ones(896)
+        sc[:384] = 2.0 ** -int(prescale_exp)
+        sc[384:768] = 1.0 if ab_kernel_form else 32.0
+        sc[768:] = (1.0 if ab_kernel_form else 32.0) * 2.0 ** -int(prescale_exp)
+        node_ab = node_ab * sc
+    if out_layout not in ("rowmajor", "tiled", "none") or (out_layout == "none" and proj is None):
+        raise HipLibraryError(f"edge_transition_f16x3: out_layout {out_layout!r}" + (" needs proj" if out_layout == "none" else ""))
+    _req(edge.buf if in_tiled else edge, name="edge")
+    _req_all(node_ab=node_ab, node_p=node_p, b2=b2, gamma=gamma, beta=beta)
+    pw, pb, pbias, ppz = _proj_outputs(proj, B, N, edge.device, torch.int16, "wstream")
+    wstream = _req(wstream, torch.int16, "wstream") if proj is None else pw
+    if wstream.numel() * 2 != (31 if proj is not None else 30) * 32 * 1024:
+        raise HipLibraryError("edge_transition_f16x3: weight stream has the wrong number of stages")
+    _req_opt(mask=mask)
+    if out_layout == "none":
+        out = None
+    elif out is None:
+        out = PairTiled(B, N, edge.device) if out_layout == "tiled" else torch.empty(B, N, N, 128, device=edge.device, dtype=torch.float32)
+    elif out.data_ptr() == edge.data_ptr():
+        raise HipLibraryError("edge_transition: out may not alias edge")
+    elif isinstance(out, PairTiled) != (out_layout == "tiled"):
+        raise HipLibraryError("edge_transition_f16x3: out does not have the requested layout")
+    io = (1 if in_tiled else 0) | {"rowmajor": 0, "tiled": 2, "none": 4}[out_layout]
+    _check(_timed("s2s_edge_transition", lambda: lib.s2s_edge_transition_f16x3(
+        _p(edge.buf if in_tiled else edge), _p(node_ab), _p(node_p), _p(wstream), _p(b2), _p(gamma), _p(beta), _p(mask),
+        _p(out.buf if isinstance(out, PairTiled) else out), B, N, ln_eps, io, _p(pb), _p(pbias), _p(ppz), int(prescale_exp), _p(range_flag()),
+        _stream())), "s2s_edge_transition_f16x3")
+    return out if proj is None else (out, pbias, ppz)
+
+
+def edge_transition(edge, node_ab, node_p, w1p, w2p, wfp, b2, bf, gamma, beta, mask, ln_eps=1e-5, out=None, proj=None):
+    """-> out, or (out, attn_bias, pair_z) when ``proj`` = (packed Wcat, bias64) of the next IPA block is given."""
+    lib = load_library()
+    B, N = edge.shape[0], edge.shape[1]
+    _req(edge, name="edge")
+    if edge.shape != (B, N, N, 128) or node_ab.shape != (B, N, 768) or node_p.shape != (B, N, 128):
+        raise HipLibraryError(f"edge_transition: bad shapes {tuple(edge.shape)} {tuple(node_ab.shape)} {tuple(node_p.shape)}")
+    _req_all(node_ab=node_ab, node_p=node_p, w1p=w1p, w2p=w2p, wfp=wfp, b2=b2, bf=bf, gamma=gamma, beta=beta)
+    _req_opt(mask=mask)
+    if out is None:
+        out = torch.empty_like(edge)
+    elif out.data_ptr() == edge.data_ptr():
+        raise HipLibraryError("edge_transition: out may not alias edge")
+    _req(out, name="out")
+    pw, pb, pbias, ppz = _proj_outputs(proj, B, N, edge.device)
+    _check(_timed("s2s_edge_transition", lambda: lib.s2s_edge_transition(
+        _p(edge), _p(node_ab), _p(node_p), _p(w1p), _p(w2p), _p(wfp), _p(b2), _p(bf), _p(gamma), _p(beta), _p(mask),
+        _p(out), B, N, ln_eps, _p(pw), _p(pb), _p(pbias), _p(ppz), _stream())), "s2s_edge_transition")
+    return out if proj is None else (out, pbias, ppz)
+
+
+def edge_embed(node_a, node_b, rel_table, bin_table, bin_lower, residue_idx, ca, w2p, w3p, b2, b3, gamma, beta, mask,
+               rel_offset: int, ln_eps=1e-5, out=None, proj=None):
+    lib = load_library()
+    B, N = node_a.shape[0], node_a.shape[1]
+    _req_all(node_a=node_a, node_b=node_b, rel_table=rel_table, bin_table=bin_table, bin_lower=bin_lower, ca=ca, w2p=w2p, w3p=w3p, b2=b2, b3=b3,
+             gamma=gamma, beta=beta)
+    _req(residue_idx, torch.int64, "residue_idx")
+    _req_opt(mask=mask)
+    out = torch.empty(B, N, N, 128, device=node_a.device, dtype=torch.float32) if out is None else out
+    pw, pb, pbias, ppz = _proj_outputs(proj, B, N, node_a.device)
+    _check(lib.s2s_edge_embed(_p(node_a), _p(node_b), _p(rel_table), _p(bin_table), _p(bin_lower), _p(residue_idx), _p(ca),
+                              _p(w2p), _p(w3p), _p(b2), _p(b3), _p(gamma), _p(beta), _p(mask), _p(out), B, N,
+                              int(rel_offset), rel_table.shape[0], bin_table.shape[0], ln_eps, _p(pw), _p(pb), _p(pbias),
+                              _p(ppz), _stream()), "s2s_edge_embed")
+    return out if proj is None else (out, pbias, ppz)
+
+
+def edge_embed_f16x3(node_a, node_b, rel_table, bin_table, bin_lower, residue_idx, ca, wstream, b2, b3, gamma, beta, mask,
+                     rel_offset: int, ln_eps=1e-5, out=None, proj=None, column_blocked_tables=False, out_layout: str = "rowmajor"):
+    """Edge embedding on split-f16 MFMA (csrc/pair_mlp_f16.hip); ``proj`` = (5-stage stream, bias64) also returns (attn_bias, pair_z).
+    node_b / rel_table / bin_table: [.., rows, 128], or already ``column_blocked`` ([.., 32, rows, 4]) with the flag set.
+    ``out_layout`` "tiled" -> a ``PairTiled`` for ``edge_transition_f16x3``."""
+    lib = load_library()
+    B, N = node_a.shape[0], node_a.shape[1]
+    if not column_blocked_tables:
+        node_b, rel_table, bin_table = column_blocked(node_b), column_blocked(rel_table), column_blocked(bin_table)
+    if node_b.shape != (B, 32, N, 4) or rel_table.shape[0] != 32 or bin_table.shape[0] != 32:
+        raise HipLibraryError("edge_embed_f16x3: tables are not column-blocked [.., 32, rows, 4]")
+    _req_all(node_a=node_a, node_b=node_b, rel_table=rel_table, bin_table=bin_table, bin_lower=bin_lower, ca=ca, b2=b2, b3=b3, gamma=gamma, beta=beta)
+    _req(residue_idx, torch.int64, "residue_idx")
+    pw, pb, pbias, ppz = _proj_outputs(proj, B, N, node_a.device, torch.int16, "wstream")
+    wstream = _req(wstream, torch.int16, "wstream") if proj is None else pw
+    if wstream.numel() * 2 != (5 if proj is not None else 4) * 32 * 1024:
+        raise HipLibraryError("s2s_edge_embed_f16x3: weight stream has the wrong number of stages")
+    _req_opt(mask=mask)
+    if out_layout not in ("rowmajor", "tiled"):
+        raise HipLibraryError(f"edge_embed_f16x3: out_layout {out_layout!r}")
+    tiled = out_layout == "tiled"
+    if out is None:
+        out = PairTiled(B, N, node_a.device) if tiled else torch.empty(B, N, N, 128, device=node_a.device, dtype=torch.float32)
+    elif isinstance(out, PairTiled) != tiled:
+        raise HipLibraryError("edge_embed_f16x3: out does not have the requested layout")
+    _check(_timed("s2s_edge_embed", lambda: lib.s2s_edge_embed_f16x3(
+        _p(node_a), _p(node_b), _p(rel_table), _p(bin_table), _p(bin_lower), _p(residue_idx), _p(ca), _p(wstream), _p(b2), _p(b3),
+        _p(gamma), _p(beta), _p(mask), _p(out.buf if tiled else out), B, N, int(rel_offset), rel_table.shape[1], bin_table.shape[1],
+        ln_eps, 1 if tiled else 0, _p(pb), _p(pbias), _p(ppz), _p(range_flag()), _stream())), "s2s_edge_embed_f16x3")
+    return out if proj is None else (out, pbias, ppz)
+
+
+def pair_project(edge, wp, bias64, attn_bias=None, pair_z=None):
+    lib = load_library()
+    B, N = edge.shape[0], edge.shape[1]
+    _req(edge, name="edge"); _req(wp, name="wp"); _req(bias64, name="bias64")
+    attn_bias = torch.empty(B, 8, N, N, device=edge.device, dtype=torch.float32) if attn_bias is None else attn_bias  # head-major [B,H,N,N]
+    pair_z = torch.empty(B, N, N, 32, device=edge.device, dtype=torch.float32) if pair_z is None else pair_z
+    _check(lib.s2s_pair_project(_p(edge), _p(wp), _p(bias64), _p(attn_bias), _p(pair_z), B, N, _stream()), "s2s_pair_project")
+    return attn_bias, pair_z

@@ -30,7 +30,7 @@ def test_header_declares_and_ops_exports_the_entry_points():
     protos = dict(re.findall(r"^int\s+(s2s_\w+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M))
     for name in NAMES:
         assert name in protos and name in ops.EXPORTS
-        assert "void* stream" in protos[name] and protos[name].count(",") + 1 == len(ops._SIGNATURES[name])
+        assert "void* stream" in protos[name] and protos[name].count(",") + 1 == len(ops.binding._SIGNATURES[name])
     assert callable(ops.ca_rmsd_matrix) and callable(ops.ca_superpose) and callable(ops.apply_xform)
 
 

@@ -694,7 +694,7 @@ def test_every_torch_op_equals_its_ops_function(net_rough, diffuser):
     from str2str_amd import ops
 
     K = torch.ops.str2str_amd
-    names = {sch.split("(")[0] for sch in ops._TORCH_OPS}
+    names = {sch.split("(")[0] for sch in ops.torch_ops._TORCH_OPS}
     assert names >= {"edge_transition", "edge_transition_f16x3", "edge_transition_f16x3_chain", "edge_embed", "edge_embed_f16x3", "pair_project",
                      "ipa_prep_points", "ipa_attention", "ipa_prep_points_f16", "ipa_prep_points_shared_kv", "ipa_attention_f16w", "encoder_attention", "node_linear",
                      "node_linear_f32", "node_linear_vfrag", "ipa_projections", "node_linear_multi", "node_chain", "row_layernorm", "embed_assemble", "pack_planes", "se3_step", "forward_marginal", "rigid_compose_update",
@@ -1006,7 +1006,7 @@ def test_range_buffer_is_per_call_across_streams():
     torch.cuda.synchronize()
 
     def pack(x, xp, words, stream):
-        assert lib.s2s_pack_planes(ops._p(x), M, K, 0, K, ops._p(xp), K // 16, 0, None, ops._p(words),
+        assert lib.s2s_pack_planes(ops.binding._p(x), M, K, 0, K, ops.binding._p(xp), K // 16, 0, None, ops.binding._p(words),
                                    ctypes.c_void_p(stream.cuda_stream)) == 0
 
     pack(big, xp_a, words_a, sa)

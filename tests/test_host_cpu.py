@@ -34,15 +34,28 @@ def test_library_exports_every_declared_symbol(built_library):
 
 
 def test_every_binding_has_the_arity_of_its_prototype():
-    """ops._SIGNATURES types as many arguments as the header declares for each entry point: a missing one would shift the stream."""
-    from str2str_amd import ops
+    """ops.binding._SIGNATURES types the arguments the header declares for each entry point, one for one: a missing one, or an int where
+    the prototype says long long, would shift every later argument.  A pointer is c_void_p (const char*: c_char_p), the scalars their
+    ctypes; the return type is c_longlong exactly for the prototypes declared long long."""
+    from str2str_amd.ops import binding
+
+    scalars = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
+               "unsigned long long": ctypes.c_ulonglong}
+
+    def ctype_of(param):
+        decl = re.sub(r"\s+", " ", param.replace("*", " * ")).strip()
+        if "*" in decl:
+            return ctypes.c_char_p if decl.startswith("const char *") and decl.count("*") == 1 else ctypes.c_void_p
+        return scalars[" ".join(w for w in decl.split(" ")[:-1] if w != "const")]       # (the last word is the parameter's name)
 
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "str2str_hip.h")).read(), flags=re.S)
-    protos = dict(re.findall(r"^(?:int|long long)\s+(s2s_\w+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M))
-    assert set(protos) == set(ops._SIGNATURES), sorted(set(protos) ^ set(ops._SIGNATURES))
-    for name, params in protos.items():
-        n = 0 if params.strip() in ("", "void") else params.count(",") + 1
-        assert n == len(ops._SIGNATURES[name]), (name, n, len(ops._SIGNATURES[name]))
+    protos = {name: (ret, params) for ret, name, params in re.findall(r"^(int|long long)\s+(s2s_\w+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M)}
+    assert set(protos) == set(binding._SIGNATURES), sorted(set(protos) ^ set(binding._SIGNATURES))
+    for name, (ret, params) in protos.items():
+        want = [] if params.strip() in ("", "void") else [ctype_of(p) for p in params.split(",")]
+        assert len(want) == len(binding._SIGNATURES[name]), (name, len(want), len(binding._SIGNATURES[name]))
+        assert want == binding._SIGNATURES[name], (name, [i for i, (a, b) in enumerate(zip(want, binding._SIGNATURES[name])) if a is not b])
+        assert (ret == "long long") == (name in binding._LL_RETURN), (name, ret)
 
 
 def test_missing_library_fails_loudly(tmp_path):
@@ -389,23 +402,48 @@ def test_every_global_name_the_package_uses_resolves():
             if isinstance(k, types.CodeType):
                 yield from codes(k)
 
-    missing = set()
+    missing, walked, covered_torch_ops = set(), set(), False
     for info in pkgutil.walk_packages(str2str_amd.__path__, "str2str_amd."):
         if info.name.rsplit(".", 1)[-1].startswith("lib"):         # the built shared library, not a Python module
             continue
         mod = importlib.import_module(info.name)
+        walked.add(info.name)
         fns = [v for v in vars(mod).values() if isinstance(v, types.FunctionType) and v.__module__ == mod.__name__]
         for cls in [v for v in vars(mod).values() if isinstance(v, type) and v.__module__ == mod.__name__]:
             fns += [getattr(v, "__func__", v) for v in vars(cls).values()
                     if isinstance(getattr(v, "__func__", v), types.FunctionType)]
-        if info.name == "str2str_amd.ops":
+        if info.name == "str2str_amd.ops.torch_ops":
             fns += [f for f in mod._TORCH_OPS.values() if isinstance(f, types.FunctionType)]
+            covered_torch_ops = True
         for f in fns:
             for c in codes(f.__code__):
                 for ins in dis.get_instructions(c):
                     if ins.opname == "LOAD_GLOBAL" and ins.argval not in f.__globals__ and not hasattr(builtins, ins.argval):
                         missing.add((info.name, f.__name__, ins.argval))
     assert not missing, sorted(missing)
+    ops_dir = os.path.join(ROOT, "str2str_amd", "ops")
+    assert covered_torch_ops and {"str2str_amd.ops." + f[:-3] for f in os.listdir(ops_dir) if f.endswith(".py") and f != "__init__.py"} <= walked
+
+
+def test_every_ops_attribute_the_tree_uses_exists():
+    """Most call sites of the binding run only on a GPU: check on the CPU that every ``ops.<name>`` in a tracked Python file that imports
+    ``ops`` from the package is an attribute of ``str2str_amd.ops`` (a name dropped from its ``__init__`` would otherwise show up only
+    there).  The lookbehind keeps ``torch.ops.str2str_amd`` out."""
+    import subprocess
+
+    from str2str_amd import ops
+
+    tracked = subprocess.run(["git", "ls-files", "*.py"], cwd=ROOT, capture_output=True, text=True)
+    files = tracked.stdout.split() if tracked.returncode == 0 and tracked.stdout.strip() else [
+        os.path.relpath(os.path.join(d, f), ROOT) for d, _, fs in os.walk(ROOT) for f in fs if f.endswith(".py")]       # (an exported tree: every file is a tracked one)
+    users, unresolved = 0, set()
+    for rel in files:
+        src = open(os.path.join(ROOT, rel)).read()
+        if not re.search(r"^\s*from\s+(str2str_amd|\.+)\s+import\s+(\w+\s*,\s*)*ops\b", src, flags=re.M):
+            continue
+        users += 1
+        unresolved |= {(rel, name) for name in re.findall(r"(?<![\w.])ops\.([A-Za-z_]\w*)", src) if not hasattr(ops, name)}
+    assert users >= 33 and not unresolved, (users, sorted(unresolved))
 
 
 def test_edge_prescale_ladder():
