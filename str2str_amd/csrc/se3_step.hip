@@ -191,7 +191,9 @@ __global__ void __launch_bounds__(kThreads) se3_step_kernel(
     if (tid < 3) {
         double v = 0.0, cnt = 0.0;
         for (int w = 0; w < kThreads / 64; ++w) { v += s_red[tid][w]; cnt += s_red[3][w]; }
-        s_com[tid] = center ? v / (double)(float)cnt : 0.0;
+        // a sample without residues (center == 2, mask all zero) has no centre: 0, not 0 / 0, which would turn the
+        // translations of its frozen residues into NaN through 0 * NaN in the blend below
+        s_com[tid] = (center && cnt > 0.0) ? v / (double)(float)cnt : 0.0;
     }
     __syncthreads();
 
