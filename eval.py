@@ -42,7 +42,8 @@ def load_model_checkpoint(model, ckpt_path):
     raise ValueError(f"ckpt_path {ckpt_path} is not a valid checkpoint file.")
 
 
-EXTRA_METRICS = ("div_rmsd", "rmsd_recall", "rmsd_precision")   # optional columns (minimum RMSD under optimal superposition)
+# optional columns: minimum RMSD under optimal superposition, TM-score under the identity correspondence
+EXTRA_METRICS = ("div_rmsd", "rmsd_recall", "rmsd_precision", "div_tm", "tm_recall", "tm_precision")
 
 
 def metric_columns(extra_metrics=None):
@@ -76,7 +77,9 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     fns = {"val_clash": metrics.validity, "val_bond": metrics.bonding_validity, "js_pwd": metrics.js_pwd, "js_rg": metrics.js_rg,
            "js_tica": metrics.js_tica,   # the reference's five columns, in its order (src/eval.py:64-70)
            "div_rmsd": metrics.diversity_rmsd, "rmsd_recall": lambda ca: metrics.coverage_rmsd(ca, ref_key="target")[0],
-           "rmsd_precision": lambda ca: metrics.coverage_rmsd(ca, ref_key="target")[1]}
+           "rmsd_precision": lambda ca: metrics.coverage_rmsd(ca, ref_key="target")[1],
+           "div_tm": metrics.diversity_tm, "tm_recall": lambda ca: metrics.coverage_tm(ca, ref_key="target")[0],
+           "tm_precision": lambda ca: metrics.coverage_tm(ca, ref_key="target")[1]}
     fns = {k: fns[k] for k in columns}
     eval_res = {k: {} for k in fns}
     for target in targets:

@@ -427,6 +427,28 @@ int s2s_ca_superpose(const float* mobile, int n_mobile, const float* target, int
  * xform [n_samples, 12] as above, accumulated in float64; out may alias points. */
 int s2s_apply_xform(const float* points, const double* xform, int n_samples, long long n_points, float* out, void* stream);
 
+/* ---- TM-score under the identity correspondence (csrc/ensemble_tm.hip; no counterpart in the reference) ----
+ * TM(a, b) = max over the evaluated superpositions (R proper, t) of (1/L) sum_i 1 / (1 + |R a_i + t - b_i|^2 / d0^2), L = n_res, residue i
+ * of a against residue i of b (the TMscore program's convention, not TM-align's), float64 arithmetic on the widened float32 coordinates.
+ * d0 <= 0 selects d0(L) = max(0.5, 1.24 cbrt(L - 15) - 1.8) for L > 15, else 0.5.
+ * Search (fixed; no data-dependent termination): for every seed window (s, n) start from weights 1 on residues s .. s+n-1 and 0 elsewhere,
+ * then 33 times: weighted Kabsch of a onto b (proper rotation from the eigen-quaternion of Horn's 4 x 4, cyclic Jacobi), evaluate the score,
+ * w_i <- f_i^2.  A reweighting never lowers the score; the result is the maximum over all seeds and evaluations, a lower bound of the true
+ * optimum and a continuous function of the coordinates.  Seeds: (0, L); then for div in (2, 4): n = max(L / div, 4), skipped if n >= L,
+ * starts 0, n/2, 2 (n/2), ... while s + n <= L, plus (L - n, n) if the last window stops short of L (at most 16).  n_res = 1 gives exactly 1. */
+#define S2S_TM_MAX_RES 800   /* the coordinates of a 4 x 4 tile of pairs stay in LDS: 192 B per residue */
+
+/* All pairs of a [n_a, n_res, 3] and b [n_b, n_res, 3] -> tm [n_a, n_b] float64.  b == a with n_b == n_a is the self case: pairs i <= j are
+ * evaluated and mirrored (exactly symmetric; the diagonal comes from its own pair).  a may also be a contiguous run of b's structures (a row
+ * chunk of the self matrix): the rows are then bit for bit those of the self matrix.  No scratch.  Per call n_a * n_b < 2^31,
+ * n_b <= 4 * 65535 and n_res <= S2S_TM_MAX_RES (the binding chunks rows). */
+int s2s_ca_tm_matrix(const float* a, int n_a, const float* b, int n_b, int n_res, double d0, double* tm, void* stream);
+
+/* mobile [n_mobile, n_res, 3] onto target [n_res, 3] -> tm [n_mobile] (the s2s_ca_tm_matrix entry of the pair) and xform12 [n_mobile, 12]
+ * in the layout of s2s_ca_superpose (s2s_apply_xform consumes it): the superposition that scored the maximum (the first seed to reach it). */
+int s2s_ca_tm_superpose(const float* mobile, int n_mobile, const float* target, int n_res, double d0, double* tm, double* xform12,
+                        void* stream);
+
 /* ---- PDB text at the exit of the path (HOST pointers, host code; byte-identical to the reference's writers) ---- */
 
 /* protein.to_pdb per model (src/common/protein.py:152-234) over atom37 [n_models, n_res, 37, 3] float32 HOST coordinates with

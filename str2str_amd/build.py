@@ -32,6 +32,7 @@ UNITS = {
     "forward_marginal.hip": ["-ffp-contract=off"],
     "ensemble_metrics.hip": ["-ffp-contract=off"],
     "ensemble_rmsd.hip": [],   # float64 throughout; contraction stays on (an fma only removes a rounding)
+    "ensemble_tm.hip": [],     # (as above)
     # the MFMA chains are fully unrolled on purpose (accumulator tiles must be statically indexed)
     "pair_mlp.hip": ["-mllvm", "-pragma-unroll-threshold=10000000"],
     # (no SLP vectorisation in the split-f16 pair kernels: hipcc packs the LayerNorm / epilogue arithmetic into v_pk_*_f32, and a packed

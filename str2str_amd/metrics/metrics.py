@@ -12,7 +12,9 @@ kinetic-map scaling -- so that the projections themselves, not only the score, a
 
 Not in the reference (its paper's diversity figures came from external tools): minimum RMSD under optimal rigid superposition --
 ``pairwise_rmsd``, ``diversity_rmsd``, ``coverage_rmsd``, ``superpose``, ``rmsf`` -- on csrc/ensemble_rmsd.hip.  Proper rotations only
-(a mirror image is not superposable), float64 arithmetic on the float32 coordinates, optional per-RESIDUE weights.
+(a mirror image is not superposable), float64 arithmetic on the float32 coordinates, optional per-RESIDUE weights.  Its length-normalised
+companion, the TM-score under the identity correspondence -- ``tm_d0``, ``pairwise_tm``, ``diversity_tm``, ``coverage_tm``,
+``tm_superpose`` -- runs on csrc/ensemble_tm.hip.
 """
 from __future__ import annotations
 
@@ -228,3 +230,66 @@ def rmsf(coords, target=None, weights=None) -> np.ndarray:
     rmsd, xform = ops.ca_superpose(x, x[0] if target is None else _dev(target)[0], weights)
     y = ops.apply_xform(x, xform).double()
     return (y - y.mean(0, keepdim=True)).square().sum(-1).mean(0).sqrt().cpu().numpy()
+
+
+# ---- TM-score under the identity correspondence (csrc/ensemble_tm.hip) ------------------------------------------------------------
+def tm_d0(L: int) -> float:
+    """The TM-score's distance scale for chains of L residues: max(0.5, 1.24 cbrt(L - 15) - 1.8) for L > 15, else 0.5 (A)."""
+    return max(0.5, 1.24 * float(np.cbrt(L - 15.0)) - 1.8) if L > 15 else 0.5
+
+
+def pairwise_tm(a, b=None, d0=None) -> np.ndarray:
+    """TM-score of every structure of ``a`` [Ra, L, 3] against every structure of ``b`` [Rb, L, 3] (default: ``a`` itself; the self
+    matrix is exactly symmetric) -> float64 [Ra, Rb].  Residue i is matched with residue i and the score is normalised by the common
+    length L (the TMscore program's convention, not TM-align's); ``d0`` overrides ``tm_d0(L)``.  The superposition search is a fixed
+    monotone one (33 reweighted Kabsch steps from each of at most 16 seed windows): every value is the score of a real
+    superposition, hence a lower bound of the optimum -- a heuristic, like the original program's search."""
+    return ops.ca_tm_matrix(_dev(a), None if b is None else _dev(b), d0).cpu().numpy()
+
+
+def diversity_tm(ca_coords_dict):
+    """Ensemble diversity: the mean TM-score over the pairs i < j of each ensemble (1.0 for a single structure).  LOWER means more
+    diverse, the opposite sense of ``diversity_rmsd``."""
+    out = {}
+    for k, v in ca_coords_dict.items():
+        x = _dev(v)
+        n = x.shape[0]
+        out[k] = np.around(float(torch.triu(ops.ca_tm_matrix(x), diagonal=1).sum()) / (n * (n - 1) / 2), decimals=4) if n > 1 else 1.0
+    return out
+
+
+def _coverage_maxima(samples: torch.Tensor, ref: torch.Tensor, chunk_pairs=None):
+    """(per reference frame: max TM to any sample, per sample: max TM to any reference frame), device float64, over row chunks of the
+    sample x reference matrix with running maxima: the matrix itself is never held."""
+    rows = ops.rmsd_row_chunk(ref.shape[0], COVERAGE_CHUNK_PAIRS if chunk_pairs is None else chunk_pairs)
+    per_ref = torch.full((ref.shape[0],), -float("inf"), dtype=torch.float64, device=ref.device)
+    per_sample = torch.empty(samples.shape[0], dtype=torch.float64, device=ref.device)
+    for r0 in range(0, samples.shape[0], rows):
+        m = ops.ca_tm_matrix(samples[r0:r0 + rows], ref)
+        per_sample[r0:r0 + rows] = m.max(dim=1).values
+        per_ref = torch.maximum(per_ref, m.max(dim=0).values)
+    return per_ref, per_sample
+
+
+def coverage_tm(ca_coords_dict, ref_key="target", chunk_pairs=None):
+    """How well each ensemble covers the reference ensemble -> (recall, precision): recall[k] = mean over reference frames of the
+    maximum TM-score to any sample of k, precision[k] = mean over samples of k of the maximum TM-score to any reference frame
+    (higher is better; the reference's own entries are 1.0)."""
+    ref = _dev(ca_coords_dict[ref_key])
+    recall, precision = {}, {}
+    for k, v in ca_coords_dict.items():
+        if k == ref_key:
+            continue
+        per_ref, per_sample = _coverage_maxima(_dev(v), ref, chunk_pairs)
+        recall[k] = np.around(float(per_ref.mean()), decimals=4)
+        precision[k] = np.around(float(per_sample.mean()), decimals=4)
+    recall[ref_key] = precision[ref_key] = 1.0
+    return recall, precision
+
+
+def tm_superpose(coords, target):
+    """Every structure of ``coords`` [R, L, 3] moved onto ``target`` [L, 3] by the superposition that scored its TM-score (it favours
+    the well-matching part of the chain where ``superpose`` minimises the RMSD of all of it) -> (aligned float32 [R, L, 3], tm float64 [R])."""
+    x = _dev(coords)
+    tm, xform = ops.ca_tm_superpose(x, _dev(target)[0])
+    return ops.apply_xform(x, xform).cpu().numpy(), tm.cpu().numpy()

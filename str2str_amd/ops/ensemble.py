@@ -1,11 +1,13 @@
-"""Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD and superposition."""
+"""Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition."""
 from typing import Optional
 
 import torch
 
 from .binding import HipLibraryError, _check, _p, _req, _stream, load_library
 
-RMSD_LAUNCH_PAIRS = 2 ** 31 - 1   # s2s_ca_rmsd_matrix takes fewer than 2^31 pairs per call
+RMSD_LAUNCH_PAIRS = 2 ** 31 - 1   # s2s_ca_rmsd_matrix and s2s_ca_tm_matrix take fewer than 2^31 pairs per call
+TM_MAX_RES = 800                  # S2S_TM_MAX_RES: the chain length whose tiles fit the LDS of s2s_ca_tm_matrix
+TM_MAX_COLS = 4 * 65535           # structures of b per s2s_ca_tm_matrix call
 
 
 def ca_sample_stats(ca: torch.Tensor, clash_bar: float = 3.0, k_exclusion: int = 0):
@@ -117,3 +119,61 @@ def apply_xform(points: torch.Tensor, xform: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(points)
     _check(lib.s2s_apply_xform(_p(points), _p(xform), points.shape[0], points.shape[1], _p(out), _stream()), "s2s_apply_xform")
     return out
+
+
+def _tm_d0(d0) -> float:
+    """The C ABI's encoding: 0 selects the length formula.  An explicit d0 must be a positive finite number."""
+    if d0 is None:
+        return 0.0
+    d0 = float(d0)
+    if not 0.0 < d0 < float("inf"):
+        raise HipLibraryError(f"d0: expected a positive finite length in Angstrom (None = the formula of the chain length), got {d0}")
+    return d0
+
+
+def ca_tm_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, d0: Optional[float] = None, max_pairs: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """TM-score (residue i against residue i, normalised by the common length L, float64) of every pair of a [Ra, L, 3] and
+    b [Rb, L, 3] fp32 device tensors -> [Ra, Rb] fp64 in (0, 1].  ``b=None``: the self matrix of ``a`` (exactly symmetric).  ``d0``: the
+    distance scale in Angstrom, None = max(0.5, 1.24 cbrt(L - 15) - 1.8).  The superposition search is the fixed monotone reweighted
+    Kabsch iteration of include/str2str_hip.h: a certified lower bound of the optimum, a heuristic like the TMscore program's.
+    ``max_pairs`` bounds the pairs of one launch: rows are chunked, the result is bit for bit the same for any value."""
+    b = a if b is None else b
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
+        raise HipLibraryError(f"ca_tm_matrix: expected tensors, got {type(a).__name__} and {type(b).__name__}")
+    if a.ndim != 3 or b.ndim != 3 or a.shape[2] != 3 or b.shape[1:] != a.shape[1:] or a.shape[0] < 1 or b.shape[0] < 1 or a.shape[1] < 1:
+        raise HipLibraryError(f"ca_tm_matrix: coordinates {tuple(a.shape)} and {tuple(b.shape)}")
+    _req(a, name="a"); _req(b, name="b")
+    (n_a, L), n_b = a.shape[:2], b.shape[0]
+    if L > TM_MAX_RES or n_b > TM_MAX_COLS:
+        raise HipLibraryError(f"ca_tm_matrix: at most {TM_MAX_RES} residues and {TM_MAX_COLS} structures of b, got {L} and {n_b}")
+    d0 = _tm_d0(d0)
+    if out is None:
+        out = torch.empty(n_a, n_b, dtype=torch.float64, device=a.device)
+    elif _req(out, torch.float64, "out").shape != (n_a, n_b):
+        raise HipLibraryError(f"ca_tm_matrix: out {tuple(out.shape)} for {n_a} x {n_b} pairs")
+    rows = rmsd_row_chunk(n_b, max_pairs)
+    lib = load_library()
+    for r0 in range(0, n_a, rows):
+        n = min(rows, n_a - r0)
+        _check(lib.s2s_ca_tm_matrix(_p(a[r0:r0 + n]), n, _p(b), n_b, L, d0, _p(out[r0:r0 + n]), _stream()), "s2s_ca_tm_matrix")
+    return out
+
+
+def ca_tm_superpose(mobile: torch.Tensor, target: torch.Tensor, d0: Optional[float] = None):
+    """mobile [R, L, 3] onto target [L, 3] (fp32 device tensors) -> (tm [R] fp64: the ca_tm_matrix entries of the pairs, xform [R, 12]
+    fp64 in ca_superpose's layout: the superposition that scored each TM; apply_xform consumes it)."""
+    if not (isinstance(mobile, torch.Tensor) and isinstance(target, torch.Tensor)):
+        raise HipLibraryError(f"ca_tm_superpose: expected tensors, got {type(mobile).__name__} and {type(target).__name__}")
+    if mobile.ndim != 3 or mobile.shape[2] != 3 or target.shape != mobile.shape[1:] or mobile.shape[0] < 1 or mobile.shape[1] < 1:
+        raise HipLibraryError(f"ca_tm_superpose: mobile {tuple(mobile.shape)}, target {tuple(target.shape)}")
+    _req(mobile, name="mobile"); _req(target, name="target")
+    R, L = mobile.shape[:2]
+    if L > TM_MAX_RES:
+        raise HipLibraryError(f"ca_tm_superpose: at most {TM_MAX_RES} residues, got {L}")
+    d0 = _tm_d0(d0)
+    lib = load_library()
+    tm = torch.empty(R, dtype=torch.float64, device=mobile.device)
+    xform = torch.empty(R, 12, dtype=torch.float64, device=mobile.device)
+    _check(lib.s2s_ca_tm_superpose(_p(mobile), R, _p(target), L, d0, _p(tm), _p(xform), _stream()), "s2s_ca_tm_superpose")
+    return tm, xform
