@@ -16,9 +16,20 @@ x0 prediction itself.  Differences in HOW:
     on every rank from the same host generator state and sliced, so the union over ranks equals the
     single-process result sample for sample ("parity" RNG mode).  ``rng="device"`` instead draws
     nothing on the host inside the loop (throughput mode; different noise stream).
+
+Shape of the module: every driver (``forward_backward``: one chunk, ``forward_backward_chunks``: the chunks of one t_delta,
+``forward_backward_deltas`` / ``iter_forward_backward_deltas``: the t_deltas of a target) is an adapter over the same three steps:
+  * ``_batch_plan``: the reference's stream of (t_delta, chunk) entries, t_delta-major and chunk-minor, cut into BATCHES of consecutive
+    entries (several whole t_deltas | a run of chunks of one t_delta | one entry) by ``merge_delta_groups`` / ``merge_chunk_groups``;
+  * ``_draw_entries``: THE walk over the host noise stream -- per entry the whole chunk's start frames, then its 2 (n - 1) step
+    draws, burnt right there or (the last entry of a batch only) deferred into the loop;
+  * ``_sample_batch`` -> ``_denoise_pass``: THE loop, under the range guard, over one group of samples per t_delta of the batch;
+    a batch with one schedule takes the shared-row form (HIP-graph eligible), one with several the per-sample form.
+``denoise_loop`` (already expanded features, one schedule) and ``sample_mixed_lengths`` (padded rows) enter at the pass.
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import os
 from typing import Optional, Tuple
@@ -42,11 +53,11 @@ _GRAPH_MIN_STEPS = 16
 
 
 class _GraphedNet:
-    """One captured network evaluation on static input buffers (rigids_t, sc_ca_t, t_emb); outputs are static too."""
+    """One captured network evaluation on static input buffers (rigids_t, sc_ca_t, t_img); outputs are static too."""
 
     def __init__(self, net, feats):
         self.feats = dict(feats)
-        self.static = tuple(k for k in ("rigids_t", "sc_ca_t", "t_emb", "t_img") if k in feats)
+        self.static = tuple(k for k in ("rigids_t", "sc_ca_t", "t_img") if k in feats)
         for k in self.static:
             self.feats[k] = feats[k].clone()
         side = torch.cuda.Stream()
@@ -116,7 +127,7 @@ def _graph_key(net, feats, b, N):
     h = hashlib.sha1()
     for k in sorted(feats):
         v = feats[k]
-        if k in ("rigids_t", "sc_ca_t", "t_emb", "t_img", "t") or not torch.is_tensor(v):
+        if k in ("rigids_t", "sc_ca_t", "t_img", "t") or not torch.is_tensor(v):
             continue  # per-step inputs are copied into the static buffers at every replay
         h.update(k.encode()); h.update(str(tuple(v.shape)).encode()); h.update(v.detach().cpu().numpy().tobytes())
     tr = getattr(net, "translator", None)
@@ -130,7 +141,7 @@ def _graph_key(net, feats, b, N):
 
 def _maybe_graph(net, feats, b, N, trace, n_steps):
     mode = os.environ.get("S2S_HIP_GRAPH", "auto")
-    if mode == "0" or trace is not None or ops.KernelTimer.active is not None or "t_emb" not in feats:
+    if mode == "0" or trace is not None or ops.KernelTimer.active is not None:
         return None
     if mode != "1" and (b * N * N > _GRAPH_MAX_PAIRS or n_steps < _GRAPH_MIN_STEPS):
         return None
@@ -201,11 +212,20 @@ def denoise_loop(net, diffuser, feats: dict, rigids_t: torch.Tensor, ts, dt: flo
     The edge transitions -- the family whose demotion would cost 2x of the whole step -- are first given a BLOCK EXPONENT instead
     (``EdgeTransition.prescale_exp`` 0 -> 5 -> 10 -> 15: the kernel keeps its hidden activations as planes of 2^-e x the value, exact
     and at the same speed, include/str2str_hip.h) and only go to fp32 when 2^30 is not enough; ``net.range_prescale`` records it."""
-    kw = dict(min_t=min_t, noise_scale=noise_scale, probability_flow=probability_flow, self_conditioning=self_conditioning,
-              center_mode=center_mode, trace=trace)
-    return _range_guarded(net, lambda: _denoise_pass(net, diffuser, feats, rigids_t, ts, dt, host_noise=host_noise, **kw),
-                          rigids_t.device, host_draws=host_noise is not None, device_draws=host_noise is None and not probability_flow,
-                          trace=trace)
+    if float(ts[-1]) != min_t:
+        raise ValueError(f"the schedule ends at t = {float(ts[-1])}, not at min_t = {min_t}: its last evaluation is the sample")
+    return _guarded_pass(net, diffuser, [dict(rigids_t=rigids_t, ts=ts, dt=dt, feats=feats)], noise_scale=noise_scale,
+                         probability_flow=probability_flow, self_conditioning=self_conditioning, center_mode=center_mode,
+                         host_noise=host_noise, trace=trace)[0]
+
+
+def _guarded_pass(net, diffuser, groups, *, probability_flow: bool, host_noise, trace: Optional[list] = None, **kw):
+    """``_denoise_pass`` over ``groups`` under the range guard (``denoise_loop``) -> [(atom37, rigids7, psi)] per group."""
+    def run_pass():
+        return _denoise_pass(net, diffuser, groups, probability_flow=probability_flow, host_noise=host_noise, trace=trace, **kw)
+
+    return _range_guarded(net, run_pass, groups[0]["rigids_t"].device, host_draws=host_noise is not None,
+                          device_draws=host_noise is None and not probability_flow, trace=trace)[0]
 
 
 def _range_guarded(net, run_pass, device, *, host_draws: bool, device_draws: bool, trace: Optional[list] = None):
@@ -219,7 +239,7 @@ def _range_guarded(net, run_pass, device, *, host_draws: bool, device_draws: boo
         return out
     demoted = set(getattr(net, "range_fallback", None) or ())
     rng_state = torch.cuda.get_rng_state(device) if device_draws else None
-    # Host noise (parity mode) comes from the global CPU generator (forward_backward.host_noise): a replay re-draws it from the
+    # Host noise (parity mode) comes from the global CPU generator (_sample_batch.host_noise): a replay re-draws it from the
     # generator state saved here -- nothing is recorded (the draws of a long SDE trajectory at b = 128, N = 512 are ~0.6 GB), and
     # every pass leaves the generator where one completed pass leaves it.
     host_state = torch.get_rng_state() if host_draws else None
@@ -287,75 +307,125 @@ def _require_finite(rigids7, what):
                                   "overflows fp32 on this input (weights / checkpoint?)")
 
 
-def _denoise_pass(net, diffuser, feats: dict, rigids_t: torch.Tensor, ts, dt: float, *, min_t: float, noise_scale: float,
-                  probability_flow: bool, self_conditioning: bool, center_mode: int, host_noise, trace: Optional[list]):
-    """One pass of the loop in the network's current arithmetic (see ``denoise_loop``)."""
-    device = rigids_t.device
-    b, N = rigids_t.shape[:2]
-    feats = dict(feats)
-    # the masks as float32 device tensors ONCE per chunk: the network's per-chunk caches (embedder terms, mask terms) key on their identity
-    for k in ("residue_mask", "fixed_mask"):
-        feats[k] = feats[k].to(device).float().contiguous()
-    mask = feats["residue_mask"]
-    diffuse_mask = ((1 - feats["fixed_mask"]) * mask).contiguous()
-    t_all = torch.as_tensor(np.ascontiguousarray(ts, dtype=np.float64)).float()  # fl32(t), as `t * torch.ones(B)` gives
-    p8_all = diffuser.step_params(t_all).to(device)  # [n, 8]: t is uniform over the chunk
-    # timestep embeddings of the whole schedule, uploaded once (same host function the network would call per step)
-    temb_all = net.embedder.time_embed(t_all).to(device) if hasattr(getattr(net, "embedder", None), "time_embed") else None
-    # ... and their first-layer images (the embedder's only t-dependent arithmetic), for the whole schedule at once
-    timg_all = net.embedder.time_images(temb_all) if temb_all is not None and hasattr(net.embedder, "time_images") else None
-    keep_bb = getattr(net, "backbone_in_forward", None)
-    if keep_bb is not None:
+@contextlib.contextmanager
+def _backbone_deferred(net):
+    """The network's own backbone projection off inside the block (its result is unused in the loop; ``_denoise_pass`` projects once)."""
+    keep = getattr(net, "backbone_in_forward", None)
+    if keep is not None:
         net.backbone_in_forward = False
     try:
-        feats["rigids_t"] = rigids_t
-        feats["sc_ca_t"] = torch.zeros(b, N, 3, device=device)
-        feats["t"] = torch.full((b,), float(ts[0]), dtype=torch.float32)
-        if temb_all is not None:
-            feats["t_emb"] = temb_all[0]
-        if timg_all is not None:
-            feats["t_img"] = timg_all[0]
-        graphed = _maybe_graph(net, feats, b, N, trace, len(ts))
-        run = graphed if graphed is not None else (lambda f: _net_eval(net, f, trace is None))
-        if self_conditioning:
-            feats["sc_ca_t"] = run(feats)["rigids7"][..., 4:].clone()
-        final = None
-        for k, t in enumerate(ts):
-            feats["t"] = torch.full((b,), float(t), dtype=torch.float32)
-            if temb_all is not None:
-                feats["t_emb"] = temb_all[k]
-            if timg_all is not None:
-                feats["t_img"] = timg_all[k]
+        yield
+    finally:
+        if keep is not None:
+            net.backbone_in_forward = keep
+
+
+def _denoise_pass(net, diffuser, groups, *, noise_scale: float, probability_flow: bool, self_conditioning: bool, center_mode: int,
+                  host_noise, trace: Optional[list]):
+    """One pass of the loop in the network's current arithmetic (see ``denoise_loop``) over ``groups`` = [dict(rigids_t [b_k,N,7],
+    ts (descending, ending at min_t), dt, feats: ALREADY EXPANDED per-sample features [b_k, ...])] in output order: one group per
+    schedule (the t_deltas of the reference's inference block), ONE batch.  The trajectories are aligned at their END: group k
+    (n_k steps) joins at global step n_max - n_k, after its own self-conditioning evaluation on an empty ``sc_ca_t``, and the batch's
+    features are the concatenation of its members' -- so each sample sees exactly the evaluations of a run of its group alone (the
+    kernels are batch-invariant).  ``host_noise()`` is called once per global step that is followed by an SE(3) step.
+    -> ([(atom37, rigids7, psi)] per group, rigids7 of the whole batch)."""
+    device = groups[0]["rigids_t"].device
+    N = groups[0]["rigids_t"].shape[1]
+    emb = net.embedder
+    order = sorted(range(len(groups)), key=lambda k: -len(groups[k]["ts"]))     # join order (stable: equal lengths keep output order)
+    n_max = len(groups[order[0]]["ts"])
+    # THE choice of form, by the number of schedules in the batch.  One: the timestep image is one row [512] of the schedule's table
+    # for the whole batch, the step parameters one row expanded to [b, 8], dt a float, and the evaluation may be replayed from a HIP
+    # graph (``_maybe_graph``).  Several: every sample carries its own timestep image (``t_img`` [b, 512]), SE(3) step parameters
+    # and step size (s2s_se3_step dt_per_sample), gathered by its row ``idx`` of the concatenated tables; never captured.
+    per_sample = len(groups) > 1
+    timg, p8s, base, o = [], [], {}, 0
+    for k in order:
+        t_all = torch.as_tensor(np.ascontiguousarray(groups[k]["ts"], dtype=np.float64)).float()   # fl32(t), as `t * torch.ones(B)` gives
+        p8s.append(diffuser.step_params(t_all).to(device))   # [n_k, 8]: t is uniform over the group
+        # timestep embeddings of the whole schedule, uploaded once (same host function the network would call per step), and their
+        # first-layer images (the embedder's only t-dependent arithmetic) for the whole schedule at once
+        timg.append(emb.time_images(emb.time_embed(t_all).to(device)))
+        base[k] = o
+        o += len(t_all)
+    TIMG, P8 = (torch.cat(timg).contiguous(), torch.cat(p8s).contiguous()) if per_sample else (timg[0], p8s[0])
+    defer_psi = trace is None   # the psi blend is deferred to the last evaluation unless the steps are recorded
+
+    def eager(f):
+        return _net_eval(net, f, defer_psi)
+
+    with _backbone_deferred(net):
+        rig = sc = idx = dtv = feats = mask = diffuse_mask = graphed = None
+        members, run = [], eager
+        for g in range(n_max):
+            joining = [k for k in order if n_max - len(groups[k]["ts"]) == g]
+            for k in joining:
+                rk = groups[k]["rigids_t"]
+                bk = rk.shape[0]
+                fk = dict(groups[k]["feats"])
+                # the masks as float32 device tensors ONCE per batch composition: the network's per-chunk caches (embedder terms, mask
+                # terms) key on their identity
+                for m in ("residue_mask", "fixed_mask"):
+                    fk[m] = fk[m].to(device).float().contiguous()
+                # ("t" is not read: every sample's timestep enters through its t_img row)
+                fk.update(rigids_t=rk, sc_ca_t=torch.zeros(bk, N, 3, device=device), t=torch.zeros(bk), t_img=TIMG[base[k]])
+                if not per_sample:
+                    graphed = _maybe_graph(net, fk, bk, N, trace, n_max)
+                    run = graphed if graphed is not None else eager
+                sck = fk["sc_ca_t"]
+                if self_conditioning:      # the group's extra evaluation at its first t with an empty self-conditioning input, on its own
+                    sck = run(fk)["rigids7"][..., 4:].clone()
+                rig = rk if rig is None else torch.cat([rig, rk])
+                sc = sck if sc is None else torch.cat([sc, sck])
+                if per_sample:
+                    ik = torch.full((bk,), base[k], dtype=torch.int64, device=device)
+                    dk = torch.full((bk,), float(groups[k]["dt"]), dtype=torch.float64, device=device)
+                    idx = ik if idx is None else torch.cat([idx, ik])
+                    dtv = dk if dtv is None else torch.cat([dtv, dk])
+                members.append((k, bk, fk))
+            b = rig.shape[0]
+            if joining:
+                if len(members) == 1:
+                    feats = members[0][2]      # the very tensors of the group's own evaluation: the network's caches stay valid
+                else:
+                    feats = {key: torch.cat([f[key].to(device) for _, _, f in members]) for key in _REPEAT_KEYS if key in members[0][2]}
+                    feats["t"] = torch.zeros(b)
+                mask = feats["residue_mask"]
+                diffuse_mask = ((1 - feats["fixed_mask"]) * mask).contiguous()
+            feats["rigids_t"], feats["sc_ca_t"] = rig, sc
+            feats["t_img"] = TIMG.index_select(0, idx) if per_sample else TIMG[g]
             out = run(feats)
             x0_7 = out["rigids7"]
-            if t == min_t:
-                final = out
+            t = float(groups[order[0]]["ts"][g])     # (trace: the longest trajectory's t)
+            if g == n_max - 1:           # every trajectory's last evaluation (t == min_t): the x0 prediction is the sample
                 if trace is not None:
-                    trace.append(dict(t=t, rigids_t=feats["rigids_t"], sc_ca_t=feats["sc_ca_t"], x0=x0_7, psi=out["psi"]))
+                    trace.append(dict(t=t, rigids_t=rig, sc_ca_t=sc, x0=x0_7, psi=out["psi"]))
                 break
-            sc_in = feats["sc_ca_t"]
+            sc_in = sc
             if self_conditioning:
-                feats["sc_ca_t"] = x0_7[..., 4:].clone() if graphed is not None else x0_7[..., 4:]
+                sc = x0_7[..., 4:].clone() if graphed is not None else x0_7[..., 4:]   # (a replay overwrites the static output)
             z = host_noise() if host_noise is not None else None
             z_rot, z_trans = z if z is not None else (None, None)
             if not probability_flow and z_rot is None:
                 z_rot = torch.randn(b, N, 3, dtype=torch.float64, device=device)
                 z_trans = torch.randn(b, N, 3, dtype=torch.float64, device=device)
-            p8 = p8_all[k].expand(b, 8).contiguous()
-            nxt, rs, tsc = diffuser.step(x0_7, feats["rigids_t"], p8, dt, mask, diffuse_mask, center_trans=center_mode,
-                                         noise_scale=noise_scale, probability_flow=probability_flow, z_rot=z_rot,
-                                         z_trans=z_trans, want_scores=trace is not None)
+            p8, dt = (P8.index_select(0, idx), dtv) if per_sample else (P8[g].expand(b, 8).contiguous(), groups[0]["dt"])
+            nxt, rs, tsc = diffuser.step(x0_7, rig, p8, dt, mask, diffuse_mask, center_trans=center_mode, noise_scale=noise_scale,
+                                         probability_flow=probability_flow, z_rot=z_rot, z_trans=z_trans, want_scores=trace is not None)
             if trace is not None:
-                trace.append(dict(t=t, rigids_t=feats["rigids_t"], sc_ca_t=sc_in, x0=x0_7, psi=out["psi"], rot_score=rs,
-                                  trans_score=tsc, next7=nxt))
-            feats["rigids_t"] = nxt
-        if final.get("psi_deferred"):   # the blend with the input torsion under the fixed mask, once (DenoisingNet.blend_psi)
-            final = dict(final, psi=net.blend_psi(final["psi"], feats["torsion_angles_sin_cos"], feats["fixed_mask"]))
-        atom37 = compute_backbone(final["rigids"], final["psi"], aatype=feats.get("aatype"), _rigids7=final["rigids7"])[0]
-    finally:
-        if keep_bb is not None:
-            net.backbone_in_forward = keep_bb
-    return atom37, final["rigids7"], final["psi"]
+                trace.append(dict(t=t, rigids_t=rig, sc_ca_t=sc_in, x0=x0_7, psi=out["psi"], rot_score=rs, trans_score=tsc, next7=nxt))
+            rig = nxt
+            if per_sample:
+                idx = idx + 1
+        psi = out["psi"]
+        if out.get("psi_deferred"):   # the blend with the input torsion under the fixed mask, once (DenoisingNet.blend_psi)
+            psi = net.blend_psi(psi, feats["torsion_angles_sin_cos"], feats["fixed_mask"])
+        atom37 = compute_backbone(out["rigids"], psi, aatype=feats.get("aatype"), _rigids7=x0_7)[0]
+    samples, o = [None] * len(groups), 0
+    for k, bk, _ in members:
+        samples[k] = (atom37[o:o + bk], x0_7[o:o + bk], psi[o:o + bk])
+        o += bk
+    return samples, x0_7
 
 
 def _require_hip_device(device, net) -> torch.device:
@@ -415,11 +485,79 @@ def _burn_step_draws(B_total: int, N: int, n_draw_steps: int):
 def _skips_unused_draws(probability_flow: bool, B_total: int, N: int) -> bool:
     """Under the probability-flow ODE the reference's per-step draws are consumed, not used.  Where the host generator can be
     fast-forwarded over them (``_burn_step_draws``: milliseconds per chunk) that happens right behind the chunk's start frames;
-    otherwise they are drawn step by step inside the loop, behind the GPU work (``host_noise`` of the callers)."""
+    otherwise they are drawn step by step inside the loop, behind the GPU work (``_sample_batch.host_noise``)."""
     return probability_flow and ops.host_rng_can_discard(B_total * N * 3)
 
 
+def _chunk_rigids(gt_frames_4x4: torch.Tensor, bsz: int) -> Rigid:
+    """The ground-truth frames of one target [1, N, 4, 4] as a chunk of ``bsz`` replicas."""
+    return Rigid.from_tensor_4x4(gt_frames_4x4.repeat(bsz, *(1,) * (gt_frames_4x4.ndim - 1)))
+
+
+def _expand_features(batch: dict, b: int, device) -> dict:
+    """The per-sample features of one target (batch dimension 1) for ``b`` replicas, on the device."""
+    return {k: batch[k].to(device).repeat(b, *(1,) * (batch[k].ndim - 1)) for k in _REPEAT_KEYS if k in batch}
+
+
+def _draw_entries(diffuser, batch: dict, rig0, N: int, scheds, entries, *, rng: str, probability_flow: bool, device):
+    """THE walk over the host noise stream for one batch.  ``entries`` = [(i, chunk_size, lo, hi)]: consecutive (t_delta ``scheds[i]``
+    = (t_delta, n, dt, ts), replica chunk) entries of the reference's stream (t_delta-major, chunk-minor; diffusion_module.py:341-367),
+    (lo, hi) = this rank's slice of the chunk; ``rig0(chunk_size)`` = the chunk's ground-truth frames.  Per entry, in order: the WHOLE
+    chunk's start frames (``rng="host"``: also for an empty slice -- every generator stays in lock-step with the other ranks;
+    ``rng="device"``: an empty slice draws nothing, the host generator is never touched), then the two float64 draws per step of its
+    n - 1 steps -- burnt right behind the start frames, because the next entry's start frames come after them.  Only the LAST entry's
+    may be deferred: they ride in the loop, behind the GPU work, when its trajectory is the longest of the batch (so one draw pair goes
+    per global step from step 0) and the generator cannot be fast-forwarded over them (``_skips_unused_draws``; under the SDE they are
+    used, so never).  -> ({i: [start frames of the non-empty slices]}, deferred entry (chunk_size, lo, hi, steps) or None)."""
+    n_max = max(scheds[i][1] for i, _, _, _ in entries)
+    starts, tail = {}, None
+    for e, (i, bsz, lo, hi) in enumerate(entries):
+        if hi == lo and rng == "device":
+            continue
+        t_delta, n = scheds[i][:2]
+        r = _start_frames(diffuser, batch, rig0(bsz), t_delta, lo, hi, rng, device)
+        if rng == "host":
+            if e + 1 == len(entries) and n == n_max and not _skips_unused_draws(probability_flow, bsz, N):
+                tail = (bsz, lo, hi, n - 1)     # drawn for real: rides in the loop, behind the GPU (global step == its local step)
+            else:
+                _burn_step_draws(bsz, N, n - 1)
+        if r is not None:
+            starts.setdefault(i, []).append(r)
+    if not starts and tail is not None:     # nothing to sample on this rank: nothing reads the draws, the generator goes past them
+        _burn_step_draws(tail[0], N, tail[3])
+    return starts, tail
+
+
 @torch.no_grad()
+def _sample_batch(net, diffuser, batch: dict, rig0, N: int, scheds, entries, *, noise_scale: float, probability_flow: bool,
+                  self_conditioning: bool, device, rng: str, trace: Optional[list] = None) -> dict:
+    """One batch of the plan (``entries``, see ``_draw_entries``): its draws, then ONE guarded pass over one group of samples per
+    t_delta -> {i: (atom37, rigids7, psi)} for the t_deltas of the batch, this rank's replicas in replica order ({} when it has none)."""
+    starts, tail = _draw_entries(diffuser, batch, rig0, N, scheds, entries, rng=rng, probability_flow=probability_flow, device=device)
+    if not starts:
+        return {}
+
+    bsz, lo, hi = tail[:3] if tail is not None else (0, 0, 0)
+
+    def host_noise():
+        # the reference consumes two float64 normal draws of the whole chunk per step even under the probability-flow ODE
+        # (so3.py:360, r3.py:109): keep the host generator in lock-step for later chunks; the SDE uses this rank's slice of them
+        zr = torch.randn(bsz, N, 3, dtype=torch.float64)
+        zt = torch.randn(bsz, N, 3, dtype=torch.float64)
+        if probability_flow:
+            return None
+        return zr[lo:hi].to(device).contiguous(), zt[lo:hi].to(device).contiguous()
+
+    groups = []
+    for i, rs in starts.items():
+        rigids_t = torch.cat(rs, dim=0) if len(rs) > 1 else rs[0]
+        groups.append(dict(rigids_t=rigids_t, ts=scheds[i][3], dt=scheds[i][2], feats=_expand_features(batch, rigids_t.shape[0], device)))
+    samples = _guarded_pass(net, diffuser, groups, noise_scale=noise_scale, probability_flow=probability_flow,
+                            self_conditioning=self_conditioning, center_mode=1, host_noise=host_noise if tail is not None else None,
+                            trace=trace)
+    return dict(zip(starts, samples))
+
+
 def forward_backward(net, diffuser, batch: dict, rigids_0: Rigid, t_delta: float, *, num_timesteps: int,
                      min_t: float = 0.01, noise_scale: float = 1.0, probability_flow: bool = True,
                      self_conditioning: bool = True, device=None, shard: Tuple[int, int] = (0, 1),
@@ -434,37 +572,17 @@ def forward_backward(net, diffuser, batch: dict, rigids_0: Rigid, t_delta: float
     sample and every generator stays in lock-step for later chunks.  ``rng="device"`` (throughput mode) draws the
     forward-marginal and step noise on the device generator for the slice only."""
     device = _require_hip_device(device, net)
-    B_total = rigids_0.shape[0]
+    B_total, N = rigids_0.shape[0], rigids_0.shape[1]
     lo, hi = replica_slice if replica_slice is not None else shard_range(B_total, *shard)
     if not (0 <= lo <= hi <= B_total):
         raise ValueError(f"replica_slice {(lo, hi)} outside the chunk of {B_total} replicas")
-    b = hi - lo
     T, n, dt, ts = schedule(t_delta, num_timesteps, min_t)
-    N = rigids_0.shape[1]
-
-    rigids_t = _start_frames(diffuser, batch, rigids_0, t_delta, lo, hi, rng, device)
-    skip_ahead = rng == "host" and (rigids_t is None or _skips_unused_draws(probability_flow, B_total, N))
-    if skip_ahead:      # nothing reads the chunk's step draws: the generator goes straight to where they leave it
-        _burn_step_draws(B_total, N, len(ts) - 1)
-    if rigids_t is None:
+    out = _sample_batch(net, diffuser, batch, lambda bsz: rigids_0, N, [(t_delta, n, dt, ts)], [(0, B_total, lo, hi)],
+                        noise_scale=noise_scale, probability_flow=probability_flow, self_conditioning=self_conditioning, device=device,
+                        rng=rng, trace=trace)
+    if not out:
         return torch.zeros(0, N, 37, 3, device=device)
-    feats = {k: batch[k].to(device).repeat(b, *(1,) * (batch[k].ndim - 1)) for k in _REPEAT_KEYS if k in batch}
-
-    def host_noise():
-        # the reference consumes two float64 normal draws per step even under the probability-flow ODE
-        # (so3.py:360, r3.py:109): keep the host generator in lock-step for later chunks
-        zr = torch.randn(B_total, N, 3, dtype=torch.float64)
-        zt = torch.randn(B_total, N, 3, dtype=torch.float64)
-        if probability_flow:
-            return None
-        return zr[lo:hi].to(device).contiguous(), zt[lo:hi].to(device).contiguous()
-
-    atom37, r7, psi = denoise_loop(net, diffuser, feats, rigids_t, ts, dt, min_t=min_t, noise_scale=noise_scale,
-                                   probability_flow=probability_flow, self_conditioning=self_conditioning, center_mode=1,
-                                   host_noise=host_noise if rng == "host" and not skip_ahead else None, trace=trace)
-    if return_rigids:
-        return atom37, r7, psi
-    return atom37
+    return out[0] if return_rigids else out[0][0]
 
 
 _MERGE_MAX_PAIRS = 8 << 20   # a merged trajectory stays within the working set of BASELINE configs[1] (128 x 256^2 pairs, ~11 GB)
@@ -490,11 +608,35 @@ def merge_chunk_groups(chunks, N: int, *, mergeable: bool = True, max_pairs: int
     return groups
 
 
-@torch.no_grad()
+def merge_delta_groups(steps, b: int, N: int, max_pairs: int = None):
+    """Consecutive t_deltas (``steps[i]`` = their trajectory lengths) -> groups [[i, ...]] sampled as one growing batch each: a group
+    holds at most ``max_pairs`` pairs at its end (b replicas per t_delta).  ``S2S_MERGE_DELTAS=0``: one t_delta per group."""
+    max_pairs = _MERGE_MAX_PAIRS if max_pairs is None else max_pairs
+    per = max(1, b) * N * N
+    cap = 1 if os.environ.get("S2S_MERGE_DELTAS", "1") == "0" else max(1, max_pairs // per)
+    return [list(range(i, min(i + cap, len(steps)))) for i in range(0, len(steps), cap)]
+
+
+def _batch_plan(chunks, steps, N: int, *, merge_deltas: bool, merge_chunks: bool, max_pairs: int = None):
+    """The flat plan of a target: the stream of (t_delta i, chunk) entries, t_delta-major, cut into batches of consecutive entries ->
+    [(t_deltas [i, ...] that are complete after these batches, [entries [(i, chunk_size, lo, hi)] per batch])].  Several t_deltas
+    whose replicas fit the pair budget are ONE batch (``merge_delta_groups``); otherwise the chunks of a t_delta that fit it are
+    (``merge_chunk_groups``; ``merge_chunks=False``: one entry per batch)."""
+    b_rank = sum(hi - lo for _, lo, hi in chunks)
+    plan = []
+    for grp in (merge_delta_groups(steps, b_rank, N, max_pairs) if merge_deltas else [[i] for i in range(len(steps))]):
+        if len(grp) > 1:
+            plan.append((grp, [[(i, *c) for i in grp for c in chunks]]))
+        else:
+            plan.append((grp, [[(grp[0], *c) for c in cg] for cg in merge_chunk_groups(chunks, N, mergeable=merge_chunks, max_pairs=max_pairs)]))
+    return plan
+
+
 def forward_backward_chunks(net, diffuser, batch: dict, gt_frames_4x4: torch.Tensor, chunks, t_delta: float, *, num_timesteps: int,
                             min_t: float = 0.01, noise_scale: float = 1.0, probability_flow: bool = True,
                             self_conditioning: bool = True, device=None, rng: str = "host", max_pairs: int = None):
-    """All replica chunks of one (target, t_delta) -> atom37 [sum(hi - lo), N, 37, 3] in replica order.
+    """All replica chunks of one (target, t_delta) -> atom37 [sum(hi - lo), N, 37, 3] in replica order (``forward_backward_deltas``
+    of one t_delta).
 
     The reference samples ``n_replica`` replicas in chunks of ``replica_per_batch`` (diffusion_module.py:341-351), one trajectory per
     chunk; its default block (100 replicas in chunks of 64 + 36 on chains of 35 .. 80 residues) leaves the GPU launch-bound -- an
@@ -504,149 +646,9 @@ def forward_backward_chunks(net, diffuser, batch: dict, gt_frames_4x4: torch.Ten
     two float64 draws per step the reference consumes even under the ODE are consumed per chunk), and the chunks that fit a pair
     budget run as ONE trajectory: same samples, file for file, in fewer launches.  Under the SDE with host noise the per-step draws
     are part of the trajectory: one chunk per trajectory, as before.  ``chunks`` = ``rank_chunk_slices(...)`` of this rank."""
-    device = _require_hip_device(device, net)
-    N = gt_frames_4x4.shape[-3]
-    T, n, dt, ts = schedule(t_delta, num_timesteps, min_t)
-    kw = dict(num_timesteps=num_timesteps, min_t=min_t, noise_scale=noise_scale, probability_flow=probability_flow,
-              self_conditioning=self_conditioning, device=device, rng=rng)
-    rig0 = lambda bsz: Rigid.from_tensor_4x4(gt_frames_4x4.repeat(bsz, *(1,) * (gt_frames_4x4.ndim - 1)))  # noqa: E731
-    out = []
-    for group in merge_chunk_groups(chunks, N, mergeable=probability_flow or rng == "device", max_pairs=max_pairs):
-        if len(group) == 1:
-            bsz, lo, hi = group[0]
-            if hi > lo or rng == "host":   # an empty slice still advances the host generators in lock-step with the other ranks
-                out.append(forward_backward(net, diffuser, batch, rig0(bsz), float(t_delta), replica_slice=(lo, hi), **kw))
-            continue
-        starts, tail_burn = [], None
-        for i, (bsz, lo, hi) in enumerate(group):
-            if hi > lo or rng == "host":
-                r = _start_frames(diffuser, batch, rig0(bsz), float(t_delta), lo, hi, rng, device)
-                if rng == "host":
-                    if i + 1 < len(group) or _skips_unused_draws(probability_flow, bsz, N):
-                        _burn_step_draws(bsz, N, len(ts) - 1)   # the next chunk's start frames come after this chunk's step draws
-                    else:
-                        tail_burn = bsz                          # drawn for real: the last chunk's ride in the loop, behind the GPU
-                if r is not None:
-                    starts.append(r)
-        if not starts:
-            if tail_burn is not None:
-                _burn_step_draws(tail_burn, N, len(ts) - 1)
-            continue
-        rigids_t = torch.cat(starts, dim=0) if len(starts) > 1 else starts[0]
-        b = rigids_t.shape[0]
-        feats = {k: batch[k].to(device).repeat(b, *(1,) * (batch[k].ndim - 1)) for k in _REPEAT_KEYS if k in batch}
-
-        def host_noise(bsz=tail_burn):   # (a mergeable group in host mode runs the ODE: the draws are consumed, not used)
-            torch.randn(bsz, N, 3, dtype=torch.float64)
-            torch.randn(bsz, N, 3, dtype=torch.float64)
-            return None
-
-        out.append(denoise_loop(net, diffuser, feats, rigids_t, ts, dt, min_t=min_t, noise_scale=noise_scale,
-                                probability_flow=probability_flow, self_conditioning=self_conditioning, center_mode=1,
-                                host_noise=host_noise if tail_burn is not None else None)[0])
-    if not out:
-        return torch.zeros(0, N, 37, 3, device=device)
-    return torch.cat(out, dim=0) if len(out) > 1 else out[0]
-
-
-def _denoise_pass_deltas(net, diffuser, batch: dict, groups, *, min_t: float, noise_scale: float, probability_flow: bool,
-                         self_conditioning: bool, center_mode: int, host_noise, device):
-    """One pass over SEVERAL trajectories of one target with different schedules (the t_deltas of the reference's inference block)
-    as ONE growing batch.  ``groups`` = [dict(rigids_t [b_k,N,7], ts (descending), dt)] in output order.  The trajectories are
-    aligned at their END: group k (n_k steps) joins at global step n_max - n_k, after its own self-conditioning evaluation, and
-    every sample carries its own timestep image (``t_img`` [b,512]), SE(3) step parameters and step size (s2s_se3_step
-    dt_per_sample) -- so each sample sees exactly the evaluations of its single-t_delta run (the kernels are batch-invariant).
-    -> (atom37 per group, rigids7 of the whole batch, psi per group)."""
-    emb = net.embedder
-    order = sorted(range(len(groups)), key=lambda k: -len(groups[k]["ts"]))     # join order (stable: equal lengths keep output order)
-    n_max = len(groups[order[0]]["ts"])
-    N = groups[0]["rigids_t"].shape[1]
-    timg, p8s, base, o = [], [], {}, 0
-    for k in order:
-        t_all = torch.as_tensor(np.ascontiguousarray(groups[k]["ts"], dtype=np.float64)).float()   # fl32(t), as `t * torch.ones(B)` gives
-        p8s.append(diffuser.step_params(t_all).to(device))
-        timg.append(emb.time_images(emb.time_embed(t_all).to(device)))
-        base[k] = o
-        o += len(t_all)
-    TIMG, P8 = torch.cat(timg).contiguous(), torch.cat(p8s).contiguous()
-    one = {k: batch[k].to(device) for k in _REPEAT_KEYS if k in batch}
-
-    def expand(b):
-        f = {k: v.repeat(b, *(1,) * (v.ndim - 1)) for k, v in one.items()}
-        for k in ("residue_mask", "fixed_mask"):     # float32 device tensors once per batch composition (the network's caches key on them)
-            f[k] = f[k].float().contiguous()
-        return f
-
-    keep_bb = getattr(net, "backbone_in_forward", None)
-    if keep_bb is not None:
-        net.backbone_in_forward = False
-    try:
-        rig = sc = idx = dtv = feats = mask = diffuse_mask = None
-        members, final = [], None
-        for g in range(n_max):
-            joined = False
-            for k in order:
-                if n_max - len(groups[k]["ts"]) != g:
-                    continue
-                rk = groups[k]["rigids_t"]
-                bk = rk.shape[0]
-                sck = torch.zeros(bk, N, 3, device=device)
-                if self_conditioning:      # the group's extra evaluation at its first t with an empty self-conditioning input, on its own
-                    fk = expand(bk)
-                    fk.update(rigids_t=rk, sc_ca_t=sck, t=torch.full((bk,), float(groups[k]["ts"][0]), dtype=torch.float32),
-                              t_img=TIMG[base[k]])
-                    sck = _net_eval(net, fk, True)["rigids7"][..., 4:].clone()
-                ik = torch.full((bk,), base[k], dtype=torch.int64, device=device)
-                dk = torch.full((bk,), float(groups[k]["dt"]), dtype=torch.float64, device=device)
-                rig = rk if rig is None else torch.cat([rig, rk])
-                sc = sck if sc is None else torch.cat([sc, sck])
-                idx = ik if idx is None else torch.cat([idx, ik])
-                dtv = dk if dtv is None else torch.cat([dtv, dk])
-                members.append((k, bk))
-                joined = True
-            b = rig.shape[0]
-            if joined:
-                feats = expand(b)
-                mask = feats["residue_mask"]
-                diffuse_mask = ((1 - feats["fixed_mask"]) * mask).contiguous()
-                feats["t"] = torch.zeros(b)     # (not read: every sample's timestep enters through its t_img row)
-            feats["rigids_t"], feats["sc_ca_t"] = rig, sc
-            feats["t_img"] = TIMG.index_select(0, idx)
-            out = _net_eval(net, feats, True)
-            x0_7 = out["rigids7"]
-            if g == n_max - 1:           # every trajectory's last evaluation (t == min_t): the x0 prediction is the sample
-                final = out
-                break
-            if self_conditioning:
-                sc = x0_7[..., 4:]
-            z = host_noise() if host_noise is not None else None
-            z_rot, z_trans = z if z is not None else (None, None)
-            if not probability_flow and z_rot is None:
-                z_rot = torch.randn(b, N, 3, dtype=torch.float64, device=device)
-                z_trans = torch.randn(b, N, 3, dtype=torch.float64, device=device)
-            rig, _, _ = diffuser.step(x0_7, rig, P8.index_select(0, idx), dtv, mask, diffuse_mask, center_trans=center_mode,
-                                      noise_scale=noise_scale, probability_flow=probability_flow, z_rot=z_rot, z_trans=z_trans)
-            idx = idx + 1
-        if final.get("psi_deferred"):
-            final = dict(final, psi=net.blend_psi(final["psi"], feats["torsion_angles_sin_cos"], feats["fixed_mask"]))
-        atom37 = compute_backbone(final["rigids"], final["psi"], aatype=feats.get("aatype"), _rigids7=final["rigids7"])[0]
-    finally:
-        if keep_bb is not None:
-            net.backbone_in_forward = keep_bb
-    a_out, p_out, o = [None] * len(groups), [None] * len(groups), 0
-    for k, bk in members:
-        a_out[k], p_out[k] = atom37[o:o + bk], final["psi"][o:o + bk]
-        o += bk
-    return a_out, final["rigids7"], p_out
-
-
-def merge_delta_groups(steps, b: int, N: int, max_pairs: int = None):
-    """Consecutive t_deltas (``steps[i]`` = their trajectory lengths) -> groups [[i, ...]] sampled as one growing batch each: a group
-    holds at most ``max_pairs`` pairs at its end (b replicas per t_delta).  ``S2S_MERGE_DELTAS=0``: one t_delta per group."""
-    max_pairs = _MERGE_MAX_PAIRS if max_pairs is None else max_pairs
-    per = max(1, b) * N * N
-    cap = 1 if os.environ.get("S2S_MERGE_DELTAS", "1") == "0" else max(1, max_pairs // per)
-    return [list(range(i, min(i + cap, len(steps)))) for i in range(0, len(steps), cap)]
+    return forward_backward_deltas(net, diffuser, batch, gt_frames_4x4, chunks, [t_delta], num_timesteps=num_timesteps, min_t=min_t,
+                                   noise_scale=noise_scale, probability_flow=probability_flow, self_conditioning=self_conditioning,
+                                   device=device, rng=rng, max_pairs=max_pairs)[0]
 
 
 def forward_backward_deltas(net, diffuser, batch: dict, gt_frames_4x4: torch.Tensor, chunks, delta_range, **kw):
@@ -662,73 +664,36 @@ def forward_backward_deltas(net, diffuser, batch: dict, gt_frames_4x4: torch.Ten
 def iter_forward_backward_deltas(net, diffuser, batch: dict, gt_frames_4x4: torch.Tensor, chunks, delta_range, *, num_timesteps: int,
                                  min_t: float = 0.01, noise_scale: float = 1.0, probability_flow: bool = True,
                                  self_conditioning: bool = True, device=None, rng: str = "host", max_pairs: int = None):
-    """All t_deltas of one target (the outer loop of the reference's predict_step, diffusion_module.py:341-367) -> [atom37
-    [sum(hi - lo), N, 37, 3] per t_delta], each exactly what ``forward_backward_chunks`` returns for that t_delta.
+    """All t_deltas of one target (the outer loop of the reference's predict_step, diffusion_module.py:341-367) -> per group of
+    t_deltas (indices [i, ...] into ``delta_range``, [atom37 [sum(hi - lo), N, 37, 3] per t_delta]), as soon as the group is sampled.
 
     The reference's default block runs 10 t_deltas (0.25 .. 0.70 of 1000 timesteps: trajectories of 250 .. 700 steps) of 100 replicas
     one after the other; on chains of 35 .. 80 residues every network evaluation is then bound by the latency of its ~83 dependent
     launches, not by the GPU.  A replica's trajectory does not depend on its batch, and nothing in the network or in the SE(3) step
     couples the samples of a batch -- so the t_deltas whose replicas fit the pair budget run as ONE batch that GROWS: aligned at
     their common end (t = min_t), the longest trajectory starts alone and each shorter one joins when as many steps remain as it
-    has, with its own timestep image, step parameters and step size per sample (``_denoise_pass_deltas``).  4750 + 10 evaluations of
+    has, with its own timestep image, step parameters and step size per sample (``_denoise_pass``).  4750 + 10 evaluations of
     100 replicas become 700 + 10 of 100 .. 1000.  The host noise stream keeps the reference's order: start frames t_delta by t_delta,
     chunk by chunk, each chunk's (unused, under the ODE) per-step draws consumed before the next chunk's start frames -- the last
-    chunk's ride in the loop when its trajectory is the longest.  Under the SDE the per-step draws are part of a trajectory (host
-    noise: in the reference's order; device noise: a merged batch would draw them for the growing batch, i.e. other samples than one
-    t_delta at a time under the same seed): one t_delta at a time (``forward_backward_chunks``), as the reference does."""
+    chunk's ride in the loop when its trajectory is the longest (``_draw_entries``).  Under the SDE the per-step draws are part of a
+    trajectory (host noise: in the reference's order; device noise: a merged batch would draw them for the growing batch, i.e. other
+    samples than one t_delta at a time under the same seed): one t_delta at a time, as the reference does."""
     device = _require_hip_device(device, net)
-    delta_range = [float(t) for t in delta_range]
-    kw = dict(num_timesteps=num_timesteps, min_t=min_t, noise_scale=noise_scale, probability_flow=probability_flow,
-              self_conditioning=self_conditioning, device=device, rng=rng)
     N = gt_frames_4x4.shape[-3]
-    b_rank = sum(hi - lo for _, lo, hi in chunks)
-    mergeable = probability_flow and len(delta_range) > 1 and b_rank > 0 and all(t > 0 for t in delta_range) \
+    scheds = [(float(t),) + schedule(float(t), num_timesteps, min_t)[1:] for t in delta_range]    # (t_delta, n, dt, ts)
+    merge_deltas = probability_flow and len(scheds) > 1 and sum(hi - lo for _, lo, hi in chunks) > 0 and all(s[0] > 0 for s in scheds) \
         and hasattr(getattr(net, "embedder", None), "time_images")
-    sched = [schedule(t, num_timesteps, min_t) for t in delta_range]
-    plan = merge_delta_groups([s[1] for s in sched], b_rank, N, max_pairs) if mergeable else [[i] for i in range(len(delta_range))]
-    rig0 = lambda bsz: Rigid.from_tensor_4x4(gt_frames_4x4.repeat(bsz, *(1,) * (gt_frames_4x4.ndim - 1)))  # noqa: E731
-    for grp in plan:
-        if len(grp) == 1:
-            with torch.no_grad():   # (never yield inside the context: the caller would inherit the grad mode)
-                one = forward_backward_chunks(net, diffuser, batch, gt_frames_4x4, chunks, delta_range[grp[0]], max_pairs=max_pairs, **kw)
-            yield grp, [one]
-            continue
-        # start frames in the reference's order: t_delta by t_delta, chunk by chunk (host mode: + each chunk's step draws)
-        groups, tail = [], None
-        longest_last = all(sched[grp[-1]][1] >= sched[i][1] for i in grp)
-        for gi, i in enumerate(grp):
-            T, n, dt, ts = sched[i]
-            starts = []
-            for ci, (bsz, lo, hi) in enumerate(chunks):
-                with torch.no_grad():
-                    r = _start_frames(diffuser, batch, rig0(bsz), delta_range[i], lo, hi, rng, device)
-                if rng == "host":
-                    if gi + 1 == len(grp) and ci + 1 == len(chunks) and longest_last and not _skips_unused_draws(probability_flow, bsz, N):
-                        tail = (bsz, len(ts) - 1)      # drawn for real: rides in the loop, behind the GPU (global step == its local step)
-                    else:
-                        _burn_step_draws(bsz, N, len(ts) - 1)
-                if r is not None:
-                    starts.append(r)
-            groups.append(dict(rigids_t=torch.cat(starts) if len(starts) > 1 else starts[0], ts=ts, dt=dt))
-        left = [tail[1] if tail else 0]
-
-        def host_noise(left=left, bsz=tail[0] if tail else 0):
-            if left[0] > 0:
-                left[0] -= 1
-                torch.randn(bsz, N, 3, dtype=torch.float64)
-                torch.randn(bsz, N, 3, dtype=torch.float64)
-            return None
-
-        def run_pass(groups=groups, left=left, tail=tail, host_noise=host_noise):
-            left[0] = tail[1] if tail else 0
-            a, r7, _ = _denoise_pass_deltas(net, diffuser, batch, groups, min_t=min_t, noise_scale=noise_scale,
-                                            probability_flow=probability_flow, self_conditioning=self_conditioning, center_mode=1,
-                                            host_noise=host_noise if tail else None, device=device)
-            return a, r7
-
-        with torch.no_grad():
-            a37 = _range_guarded(net, run_pass, device, host_draws=tail is not None, device_draws=False)[0]
-        yield grp, list(a37)
+    plan = _batch_plan(chunks, [s[1] for s in scheds], N, merge_deltas=merge_deltas, merge_chunks=probability_flow or rng == "device",
+                       max_pairs=max_pairs)
+    for grp, batches in plan:
+        pieces = {i: [] for i in grp}
+        for entries in batches:   # (never yield inside torch.no_grad() -- ``_sample_batch`` -- the caller would inherit the grad mode)
+            done = _sample_batch(net, diffuser, batch, lambda bsz: _chunk_rigids(gt_frames_4x4, bsz), N, scheds, entries,
+                                 noise_scale=noise_scale, probability_flow=probability_flow, self_conditioning=self_conditioning,
+                                 device=device, rng=rng)
+            for i, sample in done.items():
+                pieces[i].append(sample[0])
+        yield grp, [(torch.cat(p, dim=0) if len(p) > 1 else p[0]) if p else torch.zeros(0, N, 37, 3, device=device) for p in pieces.values()]
 
 
 def forward_flops(n_res: int) -> float:
@@ -848,19 +813,8 @@ def sample_mixed_lengths(net, diffuser, targets, replicas: int, t_delta: float, 
                 gt4 = tg["rigidgroups_gt_frames"][..., 0, :, :]
                 if rigids_t_init is not None:
                     rt = rigids_t_init[ti][lo:hi].to(device).float()
-                elif rng == "device":
-                    if t_delta > 0:
-                        rt = diffuser.forward_marginal_device(gt4.to(device).float().repeat(b, 1, 1, 1), t_delta,
-                                                              tg["residue_mask"].to(device).float().repeat(b, 1))
-                    else:
-                        rt = diffuser.forward_marginal_device(None, None, shape=(b, L))
-                else:
-                    rig0 = Rigid.from_tensor_4x4(gt4.cpu().repeat(b, 1, 1, 1))
-                    if t_delta > 0:
-                        rt = diffuser.forward_marginal(rig0, t_delta * torch.ones(b), tg["residue_mask"].cpu().repeat(b, 1))["rigids_t"]
-                    else:
-                        rt = diffuser.sample_prior(shape=rig0.shape, device="cpu", as_tensor_7=True)["rigids_t"]
-                    rt = rt.to(device).float()
+                else:   # the block is its own chunk of the noise stream (no step draws: the ODE's are not consumed here)
+                    rt = _start_frames(diffuser, tg, _chunk_rigids(gt4, b), t_delta, 0, b, rng, device)
                 ident = torch.zeros(b, n_pad - L, 7, device=device)
                 ident[..., 0] = 1.0  # identity frames on the padding: finite everywhere, masked out of every result
                 r_t.append(torch.cat([rt, ident], dim=1))

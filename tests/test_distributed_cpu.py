@@ -1,12 +1,13 @@
 """The N>1 path on CPU: world_size-2 (and 3) gloo processes exercise what DiffusionLitModule.predict_step / bench.py do on
 RCCL: the WHOLE replica range of a (target, t_delta) sharded over the ranks, the reference's chunks walked per rank with
 the host generator in lock-step (also through chunks a rank does not sample), ONE gather per t_delta, rank-major order ==
-single-process MODEL order.  The network itself needs the GPU, so ``forward_backward`` is replaced by a stand-in with the
-REAL function's generator behaviour (tests/test_hip_parity.py::test_sharded_* covers the real sampler on the GPU)."""
+single-process MODEL order.  The network itself needs the GPU, so the sampler's start-frame draw and its pass are replaced by
+stand-ins with the REAL functions' generator behaviour (tests/test_hip_parity.py::test_sharded_* covers the real sampler on the GPU)."""
 import os
 import socket
 
 import numpy as np
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -46,27 +47,29 @@ def _fake_start_frames(diffuser, batch, rigids_0, t_delta, lo, hi, rng, device):
     return z[lo:hi] if hi > lo else None
 
 
-def _fake_denoise_loop(net, diffuser, feats, rigids_t, ts, dt, *, host_noise=None, **kw):
-    """A trajectory that returns its start: per step the host draws of the chunk are consumed when the caller hands them in."""
-    for _ in range(len(ts) - 1):
-        if host_noise is not None:
-            host_noise()
-    out = torch.zeros(rigids_t.shape[0], rigids_t.shape[1], 37, 3)
-    out[:, :, 1, :] = rigids_t
-    return out, None, None
-
-
-def _fake_pass_deltas(net, diffuser, batch, groups, *, host_noise=None, **kw):
-    """sampler._denoise_pass_deltas with trajectories that return their start: one host_noise() call per global step."""
+def _fake_pass(net, diffuser, groups, *, host_noise=None, **kw):
+    """sampler._denoise_pass with trajectories that return their start: one host_noise() call per global step when the caller hands
+    the deferred draws in."""
     for _ in range(max(len(g["ts"]) for g in groups) - 1):
         if host_noise is not None:
             host_noise()
-    outs = []
+    samples = []
     for g in groups:
         out = torch.zeros(g["rigids_t"].shape[0], g["rigids_t"].shape[1], 37, 3)
         out[:, :, 1, :] = g["rigids_t"]
-        outs.append(out)
-    return outs, torch.zeros(1), None
+        samples.append((out, None, None))
+    return samples, torch.zeros(1)
+
+
+def _fake_sampler(setattr_):
+    """The sampler's control flow (plan -> walk over the host noise stream -> batches, slices, host-generator lock-step) runs as
+    shipped; only the three functions that need the device are replaced (the range guard is transparent for a network in fp32)."""
+    from str2str_amd import sampler as SM
+
+    setattr_(SM, "_start_frames", _fake_start_frames)
+    setattr_(SM, "_denoise_pass", _fake_pass)
+    setattr_(SM, "_require_hip_device", lambda device, net: torch.device("cpu"))
+    return SM
 
 
 class _Net(torch.nn.Module):
@@ -74,6 +77,7 @@ class _Net(torch.nn.Module):
         super().__init__()
         self.w = torch.nn.Parameter(torch.zeros(1))
         self.embedder = type("E", (), {"self_conditioning": True, "time_images": None})()
+        self.arith = "f32"      # (exact arithmetic: the range guard runs the pass once and reads no device flag)
 
 
 def _predict(rank, world, port, n_replica, rpb, out_dir, q):
@@ -84,14 +88,7 @@ def _predict(rank, world, port, n_replica, rpb, out_dir, q):
     from str2str_amd.models import diffusion_module as DM
     from str2str_amd.synth import synth_chain
 
-    from str2str_amd import sampler as SM
-
-    # the sampler's control flow (chunks -> groups -> trajectories, slices, host-generator lock-step) runs as shipped; only the three
-    # functions that need the device are replaced
-    SM._start_frames, SM.denoise_loop = _fake_start_frames, _fake_denoise_loop
-    SM._denoise_pass_deltas = _fake_pass_deltas                       # (the t_deltas of a target as one batch: forward_backward_deltas)
-    SM._range_guarded = lambda net, run_pass, device, **kw: run_pass()
-    SM._require_hip_device = lambda device, net: torch.device("cpu")
+    _fake_sampler(setattr)
     inf = dict(n_replica=n_replica, replica_per_batch=rpb, delta_min=0.5, delta_max=0.6, delta_step=0.1, num_timesteps=4,
                noise_scale=1.0, probability_flow=True, self_conditioning=True, min_t=0.01, output_dir=out_dir, backward_only=False)
     model = DM.DiffusionLitModule(net=_Net(), diffuser=None, inference=inf)
@@ -144,6 +141,54 @@ def test_predict_step_multi_rank_files_equal_single_process(tmp_path):
             assert _run_predict(3, n_replica, rpb, str(tmp_path / f"w3_{n_replica}_deltawise")) == single
         finally:
             del os.environ["S2S_MERGE_DELTAS"]
+
+
+@pytest.mark.parametrize("probability_flow", [True, False])
+def test_host_noise_walk_equals_the_reference_stream(probability_flow, monkeypatch):
+    """The walk over the host noise stream (sampler._draw_entries behind every driver) against a literal restatement of the
+    reference's order (diffusion_module.py:341-367 there): t_delta by t_delta, chunk by chunk, the WHOLE chunk's start-frame draws (a
+    rank keeps its slice), then two float64 [chunk, N, 3] draws per step for n - 1 steps -- whatever is merged into one batch, burnt,
+    fast-forwarded or deferred into the loop, on every rank: same samples per t_delta, same generator state at the end."""
+    from str2str_amd.synth import synth_chain
+
+    SM = _fake_sampler(monkeypatch.setattr)
+    N, steps = 6, 20
+    batch = synth_chain(N)
+    gt4 = batch["rigidgroups_gt_frames"][..., 0, :, :]
+    net = _Net()
+    cases = 0
+    for fast in ("0", "1"):
+        for merge_chunks in ("0", "1"):
+            for merge_deltas in ("0", "1"):
+                monkeypatch.setenv("S2S_HOST_RNG_FAST", fast)
+                monkeypatch.setenv("S2S_MERGE_CHUNKS", merge_chunks)
+                monkeypatch.setenv("S2S_MERGE_DELTAS", merge_deltas)
+                for deltas in ([0.3, 0.5, 0.8], [0.8, 0.5, 0.3], [0.5, 0.8, 0.3], [0.5]):
+                    for n_replica, rpb, world in ((5, 2, 1), (5, 2, 2), (5, 2, 3), (1, 1, 2), (7, 3, 2)):
+                        for rank in range(world):
+                            chunks = SM.rank_chunk_slices(n_replica, rpb, rank, world)
+                            torch.manual_seed(17)
+                            want = []
+                            for t_delta in deltas:
+                                n = SM.schedule(t_delta, steps, 0.01)[1]
+                                mine = []
+                                for bsz, lo, hi in chunks:
+                                    z = torch.randn(bsz, N, 3)
+                                    mine.append(z[lo:hi])
+                                    for _ in range(2 * (n - 1)):
+                                        torch.randn(bsz, N, 3, dtype=torch.float64)
+                                want.append(torch.cat(mine))
+                            end = torch.get_rng_state()
+                            for max_pairs in (None, 2 * N * N, 3 * N * N, 6 * N * N, 1):
+                                torch.manual_seed(17)
+                                got = SM.forward_backward_deltas(net, None, batch, gt4, chunks, deltas, num_timesteps=steps, rng="host",
+                                                                 probability_flow=probability_flow, max_pairs=max_pairs)
+                                assert len(got) == len(want)
+                                for g, w in zip(got, want):
+                                    assert torch.equal(g[:, :, 1, :], w), (deltas, n_replica, rpb, world, rank, max_pairs, fast)
+                                assert torch.equal(torch.get_rng_state(), end), (deltas, n_replica, rpb, world, rank, max_pairs, fast)
+                                cases += 1
+    assert cases == 1600
 
 
 def _gather_worker(rank, world, port, total, q):

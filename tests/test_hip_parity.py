@@ -1385,6 +1385,21 @@ def test_merged_t_deltas_equal_one_at_a_time(net_smooth, diffuser, monkeypatch):
     torch.manual_seed(4)
     got = forward_backward_deltas(net_smooth, diffuser, feats, gt4, chunks, deltas[::-1], **kw)
     assert all(torch.equal(a.cpu(), b.cpu()) for a, b in zip(got, ref)) and torch.equal(torch.get_rng_state(), state_ref)
+    # the SDE with host noise (one chunk per batch, its step draws used inside the loop) through the chunk and t_delta drivers: the
+    # chunks sampled one by one in stream order under the same seed, by value and by generator state
+    from str2str_amd.common.rigid_utils import Rigid
+    from str2str_amd.sampler import forward_backward
+
+    kw = dict(num_timesteps=20, device=DEV, rng="host", probability_flow=False)
+    torch.manual_seed(8)
+    got = forward_backward_deltas(net_smooth, diffuser, feats, gt4, chunks, [0.3, 0.5], **kw)
+    state_got = torch.get_rng_state()
+    torch.manual_seed(8)
+    for d, g in zip([0.3, 0.5], got):
+        one = [forward_backward(net_smooth, diffuser, feats, Rigid.from_tensor_4x4(gt4.repeat(bsz, 1, 1, 1)), d, replica_slice=(lo, hi), **kw)
+               for bsz, lo, hi in chunks]
+        assert g.shape == (5, 20, 37, 3) and torch.equal(g, torch.cat(one))
+    assert torch.equal(torch.get_rng_state(), state_got)
 
 
 def test_sharded_sampler_equals_single(net_smooth, diffuser):
