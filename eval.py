@@ -3,7 +3,8 @@
 composer), instantiates datamodule / model / trainer from their `_target_`s, loads the checkpoint with the
 reference's key contract and runs ``trainer.predict``; when ``target_dir`` holds reference ensembles the samples are then
 scored (src/eval.py:47-99) with the device metrics of str2str_amd/metrics (validity, bonding validity, JS-PwD, JS-TICA, JS-Rg)
-into the reference's tab-separated ``metrics_<tag>_<mmdd-HH-MM>.csv``."""
+into the reference's tab-separated ``metrics_<tag>_<mmdd-HH-MM>.csv``.  ``+cluster_cutoff=<A>`` also clusters every sampled ensemble
+(GROMOS at that RMSD, on the device) into ``clusters/<target>.pdb`` and ``clusters_<tag>_<mmdd-HH-MM>.csv`` next to it."""
 import logging
 import os
 import sys
@@ -55,16 +56,34 @@ def metric_columns(extra_metrics=None):
     return ["val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"] + extra
 
 
-def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None):
+CLUSTER_COLUMNS = ("n_clusters", "top1_population", "top5_population", "n_singletons")
+
+
+def cluster_summary(sizes):
+    """One row of the clusters csv from the non-increasing cluster sizes: populations are fractions of the ensemble."""
+    import numpy as np
+
+    sizes = np.asarray(sizes, dtype=np.int64)
+    total = float(sizes.sum())
+    return {"n_clusters": int(len(sizes)), "top1_population": np.around(sizes[:1].sum() / total, decimals=4),
+            "top5_population": np.around(sizes[:5].sum() / total, decimals=4), "n_singletons": int((sizes == 1).sum())}
+
+
+def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None, cluster_cutoff=None):
     """reference src/eval.py:47-99: one row per target, one column per metric, plus the mean row.  ``extra_metrics``: names out of
-    EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's)."""
+    EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's).
+    ``cluster_cutoff`` (A; None: nothing of this happens): the ``pred`` ensemble of every target is clustered by ``metrics.cluster_rmsd``;
+    ``clusters/<target>.pdb`` receives the centres' MODELs, most populated first, and ``clusters_<tag>_<mmdd-HH-MM>.csv`` one row per
+    target (CLUSTER_COLUMNS), both next to the metrics csv."""
     columns = metric_columns(extra_metrics)
+    if cluster_cutoff is not None and not 0.0 < float(cluster_cutoff) < float("inf"):
+        raise ValueError(f"cluster_cutoff {cluster_cutoff}: expected a positive finite RMSD in Angstrom")
     from time import strftime
 
     import numpy as np
     import pandas as pd
 
-    from str2str_amd.common.pdb_utils import extract_backbone_coords
+    from str2str_amd.common.pdb_utils import extract_backbone_coords, select_pdb_models
     from str2str_amd.metrics import metrics
 
     if target_dir is None or not os.path.isdir(target_dir):
@@ -82,6 +101,7 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
            "tm_precision": lambda ca: metrics.coverage_tm(ca, ref_key="target")[1]}
     fns = {k: fns[k] for k in columns}
     eval_res = {k: {} for k in fns}
+    clusters = {}
     for target in targets:
         pred_file = os.path.join(pred_dir, f"{target}.pdb")
         if not os.path.isfile(pred_file):
@@ -95,9 +115,16 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
                 eval_res[name][target] = float("nan")
                 continue
             eval_res[name][target] = res[0]["pred"] if name == "js_tica" else res["pred"]
+        if cluster_cutoff is not None:
+            res = metrics.cluster_rmsd(ca["pred"], float(cluster_cutoff))
+            select_pdb_models(pred_file, res.centres, os.path.join(output_dir, "clusters", f"{target}.pdb"))
+            clusters[target] = cluster_summary(res.sizes)
     df = pd.DataFrame.from_dict(eval_res)
     df.loc["mean"] = np.around(df.mean(), decimals=4)
     df.to_csv(os.path.join(output_dir, f"metrics_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
+    if cluster_cutoff is not None:
+        pd.DataFrame.from_dict(clusters, orient="index", columns=list(CLUSTER_COLUMNS)).to_csv(
+            os.path.join(output_dir, f"clusters_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
     return df.loc["mean"]
 
 
@@ -106,7 +133,7 @@ def evaluate(cfg):
     if pred_dir and os.path.isdir(pred_dir):
         log.info(f"Found pre-computed prediction directory {pred_dir}.")
         return evaluate_prediction(pred_dir, target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"),
-                                   extra_metrics=cfg.get("extra_metrics"))
+                                   extra_metrics=cfg.get("extra_metrics"), cluster_cutoff=cfg.get("cluster_cutoff"))
     log.info(f"Instantiating datamodule <{cfg.data['_target_']}>")
     datamodule = C.instantiate(cfg.data)
     log.info(f"Instantiating model <{cfg.model['_target_']}>")
@@ -133,7 +160,7 @@ def evaluate(cfg):
     pred_dir = trainer.predict(model=model, dataloaders=dataloaders, ckpt_path=ckpt_path)[-1]
     log.info(f"Samples written under {pred_dir}.")
     if int(os.environ.get("RANK", "0")) == 0 and cfg.get("target_dir"):
-        log.info(f"metrics: {dict(evaluate_prediction(pred_dir, target_dir=cfg.get('target_dir'), tag=cfg.get('task_name'), extra_metrics=cfg.get('extra_metrics')))}")
+        log.info(f"metrics: {dict(evaluate_prediction(pred_dir, target_dir=cfg.get('target_dir'), tag=cfg.get('task_name'), extra_metrics=cfg.get('extra_metrics'), cluster_cutoff=cfg.get('cluster_cutoff')))}")
     return pred_dir
 
 

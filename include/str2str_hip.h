@@ -449,6 +449,29 @@ int s2s_ca_tm_matrix(const float* a, int n_a, const float* b, int n_b, int n_res
 int s2s_ca_tm_superpose(const float* mobile, int n_mobile, const float* target, int n_res, double d0, double* tm, double* xform12,
                         void* stream);
 
+/* ---- Threshold clustering of an ensemble (csrc/ensemble_cluster.hip; no counterpart in the reference) ----
+ * The GROMOS algorithm (Daura et al. 1999, `gmx cluster -method gromos`) on a symmetric neighbour relation i ~ j (i ~ i always): until no
+ * structure is live, the live structure with the most live neighbours (the lowest index among equals) becomes the centre of the next
+ * cluster, its live neighbours (itself included) form the cluster and stop being live.  Cluster ids are in order of extraction, sizes are
+ * non-increasing.
+ * Bit layout: adj [n, W] 64-bit words, W = ceil(n / 64); bit (j % 64) of word (j / 64) of row i, little-endian, is i ~ j. */
+#define S2S_CLUSTER_MAX_N 65536   /* structures: 512 MB of neighbour bits, and one live word per thread of the single picking workgroup */
+
+/* values [n_rows, n] float64: rows row0 .. row0 + n_rows - 1 of an n x n matrix -> those rows of adj and their popcounts deg [n] (the
+ * other rows of both are left alone).  i ~ j iff values <= cutoff (at_least == 0: distances) or values >= cutoff (at_least != 0:
+ * similarities); the diagonal bit is always set, bits of columns >= n are always clear, NaN is never a neighbour. */
+int s2s_cluster_adjacency(const double* values, int n_rows, int row0, int n, double cutoff, int at_least, unsigned long long* adj,
+                          int* deg, void* stream);
+
+/* Enqueues n_rounds rounds (pick + update, two launches each) of the greedy loop on the stream; init != 0 first marks all n structures
+ * live.  deg [n] (the row popcounts) is consumed: it holds the LIVE neighbour counts as the loop goes.  labels [n], centres [n], sizes [n]
+ * are filled as clusters are extracted; state [3] int: {live structures, clusters so far, size of the last round's cluster (0: the round
+ * had nothing to do)}.  live_ws, members_ws: W words each, caller-owned, kept between calls.  A round with nothing live is a
+ * no-op, so the result does not depend on n_rounds per call: the caller repeats (init = 0) until state[0] reads 0.  Once the largest live
+ * count is 1 all live structures become singleton clusters, in index order, in that one round. */
+int s2s_cluster_gromos(const unsigned long long* adj, int* deg, int n, int init, int n_rounds, int* labels, int* centres, int* sizes,
+                       int* state, unsigned long long* live_ws, unsigned long long* members_ws, void* stream);
+
 /* ---- PDB text at the exit of the path (HOST pointers, host code; byte-identical to the reference's writers) ---- */
 
 /* protein.to_pdb per model (src/common/protein.py:152-234) over atom37 [n_models, n_res, 37, 3] float32 HOST coordinates with

@@ -164,6 +164,47 @@ def merge_pdbfiles(input, output_file: str, verbose: bool = True) -> None:
         print(f"Merged {len(files)} PDB files into {output_file} with {model_number} models.")
 
 
+def select_pdb_models(src: str, indices, dst: str) -> str:
+    """The chosen MODELs (0-based ``indices``, in the order given; repeats allowed) of the multi-MODEL PDB file ``src`` written to
+    ``dst``, renumbered MODEL 1..K.  The record lines between a MODEL and its ENDMDL are the source's own bytes; the framing is
+    ``atom37_to_pdb``'s (80-column MODEL / ENDMDL lines, one bare END).  A file without MODEL records is one model."""
+    with open(src, "rb") as fh:
+        lines = fh.read().splitlines(keepends=True)
+    models, cur, framed = [], None, False
+    for ln in lines:
+        if ln.startswith(b"MODEL"):
+            framed, cur = True, []
+        elif ln.startswith(b"ENDMDL"):
+            if cur is not None:
+                models.append(cur)
+            cur = None
+        elif ln.startswith(b"END") or ln.startswith(b"MASTER"):
+            continue
+        elif framed:
+            if cur is not None:
+                cur.append(ln)
+        elif ln.startswith((b"ATOM", b"HETATM", b"TER", b"ANISOU")):
+            cur = [] if cur is None else cur
+            cur.append(ln)
+    if cur:                                    # no MODEL records at all, or a last model without its ENDMDL
+        models.append(cur)
+    indices = [int(i) for i in indices]
+    bad = [i for i in indices if not 0 <= i < len(models)]
+    if bad:
+        raise IndexError(f"select_pdb_models: {src} has {len(models)} models, asked for {bad}")
+    d = os.path.dirname(dst)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(dst, "wb") as fo:
+        for k, i in enumerate(indices):
+            fo.write(f"MODEL     {k + 1}".ljust(80).encode() + b"\n")
+            for ln in models[i]:
+                fo.write(ln if ln.endswith(b"\n") else ln + b"\n")
+            fo.write(b"ENDMDL".ljust(80) + b"\n")
+        fo.write(b"END")
+    return dst
+
+
 _AMINO_ACIDS = frozenset("ALA ARG ASN ASP CYS GLN GLU GLY HIS ILE LEU LYS MET PHE PRO SER THR TRP TYR VAL".split())
 # Peptide-linking components of the CCD that occur in experimental / reference structures (biotite's filter_amino_acids, which the
 # reference's reader applies, accepts every such component, as ATOM or HETATM records): the common modified residues with the

@@ -14,9 +14,14 @@ Not in the reference (its paper's diversity figures came from external tools): m
 ``pairwise_rmsd``, ``diversity_rmsd``, ``coverage_rmsd``, ``superpose``, ``rmsf`` -- on csrc/ensemble_rmsd.hip.  Proper rotations only
 (a mirror image is not superposable), float64 arithmetic on the float32 coordinates, optional per-RESIDUE weights.  Its length-normalised
 companion, the TM-score under the identity correspondence -- ``tm_d0``, ``pairwise_tm``, ``diversity_tm``, ``coverage_tm``,
-``tm_superpose`` -- runs on csrc/ensemble_tm.hip.
+``tm_superpose`` -- runs on csrc/ensemble_tm.hip.  Which states an ensemble visits: ``cluster_rmsd``, ``cluster_tm``,
+``cluster_from_matrix`` (GROMOS clustering at a cutoff, csrc/ensemble_cluster.hip) threshold those matrices chunk by chunk into packed
+neighbour bits and cluster them on the device; only labels, centres and sizes come back.
 """
 from __future__ import annotations
+
+import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -293,3 +298,65 @@ def tm_superpose(coords, target):
     x = _dev(coords)
     tm, xform = ops.ca_tm_superpose(x, _dev(target)[0])
     return ops.apply_xform(x, xform).cpu().numpy(), tm.cpu().numpy()
+
+
+# ---- clustering at a cutoff (csrc/ensemble_cluster.hip) ----------------------------------------------------------------------------
+class ClusterResult(NamedTuple):
+    """GROMOS clusters of R structures, most populated first: ``labels`` [R] (the cluster of every structure), ``centres`` [K] (the index
+    of every cluster's centre), ``sizes`` [K] (non-increasing), numpy int32."""
+    labels: np.ndarray
+    centres: np.ndarray
+    sizes: np.ndarray
+
+
+def _cluster_chunks(n: int, rows: int, chunk, cutoff: float, at_least: bool) -> ClusterResult:
+    """``chunk(r0, r1)`` -> rows r0 .. r1 - 1 of the n x n matrix (device float64), thresholded into the neighbour bits as they come:
+    one chunk of the matrix is alive at a time."""
+    adj = deg = None
+    for r0 in range(0, n, rows):
+        adj, deg = ops.cluster_adjacency(chunk(r0, min(r0 + rows, n)), cutoff, at_least, r0, adj, deg)
+    return ClusterResult(*(t.cpu().numpy() for t in ops.cluster_gromos(adj, deg)))
+
+
+def _chunk_rows(n: int, chunk_pairs) -> int:
+    return ops.rmsd_row_chunk(n, COVERAGE_CHUNK_PAIRS if chunk_pairs is None else chunk_pairs)
+
+
+def cluster_rmsd(coords, cutoff: float, weights=None, chunk_pairs=None) -> ClusterResult:
+    """GROMOS clustering (Daura et al. 1999; ``gmx cluster -method gromos``) of an ensemble [R, L, 3] under the minimum RMSD of
+    ``pairwise_rmsd``: i and j are neighbours iff rmsd(i, j) <= ``cutoff`` (A).  The structure with the most live neighbours (the lowest
+    index among equals) is the next centre, it and its live neighbours form the cluster and leave, until none is left.  The float64 matrix
+    is walked in row chunks of ``chunk_pairs`` pairs and never held (R x R / 8 bytes of bits are); the result does not depend on it."""
+    cutoff = float(cutoff)
+    if not 0.0 < cutoff < math.inf:
+        raise ValueError(f"cluster_rmsd: cutoff must be a positive finite RMSD in Angstrom, got {cutoff}")
+    x = _dev(coords)
+    n = x.shape[0]
+    return _cluster_chunks(n, _chunk_rows(n, chunk_pairs), lambda r0, r1: ops.ca_rmsd_matrix(x[r0:r1], x, weights), cutoff, False)
+
+
+def cluster_tm(coords, cutoff: float, d0=None) -> ClusterResult:
+    """``cluster_rmsd`` under the TM-score of ``pairwise_tm``: i and j are neighbours iff tm(i, j) >= ``cutoff``, 0 < cutoff <= 1."""
+    cutoff = float(cutoff)
+    if not 0.0 < cutoff <= 1.0:
+        raise ValueError(f"cluster_tm: cutoff must be a TM-score in (0, 1], got {cutoff}")
+    x = _dev(coords)
+    n = x.shape[0]
+    return _cluster_chunks(n, _chunk_rows(n, None), lambda r0, r1: ops.ca_tm_matrix(x[r0:r1], x, d0), cutoff, True)
+
+
+def cluster_from_matrix(values, cutoff: float, at_least: bool = False) -> ClusterResult:
+    """GROMOS clustering of a symmetric [R, R] matrix of one's own (device tensor or numpy array): neighbours are the pairs with
+    ``values <= cutoff`` (distances), or ``values >= cutoff`` with ``at_least`` (similarities).  NaN is never a neighbour."""
+    cutoff = float(cutoff)
+    if math.isnan(cutoff):
+        raise ValueError("cluster_from_matrix: cutoff is NaN")
+    v = values if torch.is_tensor(values) else np.asarray(values, dtype=np.float64)
+    if v.ndim != 2 or v.shape[0] != v.shape[1] or v.shape[0] < 1:
+        raise ValueError(f"cluster_from_matrix: expected a square matrix, got {tuple(v.shape)}")
+    same = (v == v.T) | ((v != v) & (v.T != v.T))           # (NaN in both places counts as equal)
+    if not bool(same.all()):
+        raise ValueError("cluster_from_matrix: the matrix is not symmetric")
+    v = torch.as_tensor(v).to("cuda", torch.float64).contiguous()
+    n = v.shape[0]
+    return _cluster_chunks(n, n, lambda r0, r1: v[r0:r1], cutoff, bool(at_least))

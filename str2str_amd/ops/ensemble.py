@@ -8,6 +8,8 @@ from .binding import HipLibraryError, _check, _p, _req, _stream, load_library
 RMSD_LAUNCH_PAIRS = 2 ** 31 - 1   # s2s_ca_rmsd_matrix and s2s_ca_tm_matrix take fewer than 2^31 pairs per call
 TM_MAX_RES = 800                  # S2S_TM_MAX_RES: the chain length whose tiles fit the LDS of s2s_ca_tm_matrix
 TM_MAX_COLS = 4 * 65535           # structures of b per s2s_ca_tm_matrix call
+CLUSTER_MAX_N = 65536             # S2S_CLUSTER_MAX_N: structures per clustering (512 MB of neighbour bits)
+CLUSTER_ROUNDS_PER_SYNC = 32      # rounds of the greedy loop enqueued between two readbacks of its state
 
 
 def ca_sample_stats(ca: torch.Tensor, clash_bar: float = 3.0, k_exclusion: int = 0):
@@ -177,3 +179,59 @@ def ca_tm_superpose(mobile: torch.Tensor, target: torch.Tensor, d0: Optional[flo
     xform = torch.empty(R, 12, dtype=torch.float64, device=mobile.device)
     _check(lib.s2s_ca_tm_superpose(_p(mobile), R, _p(target), L, d0, _p(tm), _p(xform), _stream()), "s2s_ca_tm_superpose")
     return tm, xform
+
+
+def cluster_adjacency(values: torch.Tensor, cutoff: float, at_least: bool = False, row0: int = 0, adj: Optional[torch.Tensor] = None,
+                      deg: Optional[torch.Tensor] = None):
+    """Rows ``row0 ..`` of an n x n matrix, values [n_rows, n] fp64 device tensor -> (adj [n, ceil(n / 64)] int64: the packed neighbour
+    bits, bit j % 64 of word j // 64 of row i is ``values[i, j] <= cutoff`` (``>=`` with ``at_least``: similarities), deg [n] int32: the
+    popcount of every row).  The diagonal is always set, bits past n are clear, NaN is never a neighbour.  ``adj`` / ``deg``: the buffers
+    an earlier row chunk filled (the other rows are left alone); None allocates them."""
+    lib = load_library()
+    _req(values, torch.float64, "values")
+    if values.ndim != 2 or values.shape[0] < 1 or values.shape[1] < 1:
+        raise HipLibraryError(f"cluster_adjacency: values {tuple(values.shape)}")
+    n_rows, n = values.shape
+    if n > CLUSTER_MAX_N:
+        raise HipLibraryError(f"cluster_adjacency: at most {CLUSTER_MAX_N} structures, got {n}")
+    if not 0 <= row0 <= n - n_rows:
+        raise HipLibraryError(f"cluster_adjacency: rows {row0} .. {row0 + n_rows - 1} of a {n} x {n} matrix")
+    W = -(-n // 64)
+    adj = torch.zeros(n, W, dtype=torch.int64, device=values.device) if adj is None else _req(adj, torch.int64, "adj")
+    deg = torch.zeros(n, dtype=torch.int32, device=values.device) if deg is None else _req(deg, torch.int32, "deg")
+    if adj.shape != (n, W) or deg.shape != (n,):
+        raise HipLibraryError(f"cluster_adjacency: adj {tuple(adj.shape)}, deg {tuple(deg.shape)} for {n} structures")
+    _check(lib.s2s_cluster_adjacency(_p(values), n_rows, int(row0), n, float(cutoff), int(bool(at_least)), _p(adj), _p(deg), _stream()),
+           "s2s_cluster_adjacency")
+    return adj, deg
+
+
+def cluster_gromos(adj: torch.Tensor, deg: torch.Tensor, rounds_per_sync: int = CLUSTER_ROUNDS_PER_SYNC):
+    """GROMOS clustering of the neighbour bits of ``cluster_adjacency`` (symmetric, diagonal set) -> device int32 (labels [n]: the cluster
+    of every structure, ids in order of extraction; centres [K]; sizes [K], non-increasing).  The centre of a cluster is the live
+    structure with the most live neighbours, the lowest index among equals.  ``rounds_per_sync`` rounds are enqueued between two
+    readbacks of the live count; the result does not depend on it.  ``adj`` and ``deg`` are left as they are."""
+    lib = load_library()
+    _req(adj, torch.int64, "adj"); _req(deg, torch.int32, "deg")
+    n = deg.numel()
+    if adj.ndim != 2 or deg.ndim != 1 or n < 1 or adj.shape != (n, -(-n // 64)):
+        raise HipLibraryError(f"cluster_gromos: adj {tuple(adj.shape)}, deg {tuple(deg.shape)}")
+    if n > CLUSTER_MAX_N:
+        raise HipLibraryError(f"cluster_gromos: at most {CLUSTER_MAX_N} structures, got {n}")
+    if int(rounds_per_sync) < 1:
+        raise HipLibraryError(f"cluster_gromos: rounds_per_sync {rounds_per_sync}")
+    dev = adj.device
+    live_deg = deg.clone()                                   # the loop counts its live neighbours down in place
+    labels, centres, sizes = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    state = torch.empty(3, dtype=torch.int32, device=dev)
+    live, members = (torch.empty(adj.shape[1], dtype=torch.int64, device=dev) for _ in range(2))
+    init, enqueued = 1, 0
+    while True:
+        _check(lib.s2s_cluster_gromos(_p(adj), _p(live_deg), n, init, int(rounds_per_sync), _p(labels), _p(centres), _p(sizes), _p(state),
+                                      _p(live), _p(members), _stream()), "s2s_cluster_gromos")
+        init, enqueued = 0, enqueued + int(rounds_per_sync)
+        n_live, n_clusters = state[:2].tolist()
+        if n_live == 0:
+            return labels, centres[:n_clusters], sizes[:n_clusters]
+        if enqueued >= n:                                    # every round with something live removes at least one structure
+            raise HipLibraryError(f"cluster_gromos: {n_live} of {n} structures still live after {enqueued} rounds")
