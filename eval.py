@@ -43,8 +43,8 @@ def load_model_checkpoint(model, ckpt_path):
     raise ValueError(f"ckpt_path {ckpt_path} is not a valid checkpoint file.")
 
 
-# optional columns: minimum RMSD under optimal superposition, TM-score under the identity correspondence
-EXTRA_METRICS = ("div_rmsd", "rmsd_recall", "rmsd_precision", "div_tm", "tm_recall", "tm_precision")
+# optional columns: minimum RMSD under optimal superposition, TM-score under the identity correspondence, CA-lDDT (no superposition)
+EXTRA_METRICS = ("div_rmsd", "rmsd_recall", "rmsd_precision", "div_tm", "tm_recall", "tm_precision", "div_lddt", "lddt_recall", "lddt_precision")
 
 
 def metric_columns(extra_metrics=None):
@@ -98,7 +98,9 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
            "div_rmsd": metrics.diversity_rmsd, "rmsd_recall": lambda ca: metrics.coverage_rmsd(ca, ref_key="target")[0],
            "rmsd_precision": lambda ca: metrics.coverage_rmsd(ca, ref_key="target")[1],
            "div_tm": metrics.diversity_tm, "tm_recall": lambda ca: metrics.coverage_tm(ca, ref_key="target")[0],
-           "tm_precision": lambda ca: metrics.coverage_tm(ca, ref_key="target")[1]}
+           "tm_precision": lambda ca: metrics.coverage_tm(ca, ref_key="target")[1],
+           "div_lddt": metrics.diversity_lddt, "lddt_recall": lambda ca: metrics.coverage_lddt(ca, ref_key="target")[0],
+           "lddt_precision": lambda ca: metrics.coverage_lddt(ca, ref_key="target")[1]}
     fns = {k: fns[k] for k in columns}
     eval_res = {k: {} for k in fns}
     clusters = {}

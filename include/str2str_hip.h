@@ -449,6 +449,35 @@ int s2s_ca_tm_matrix(const float* a, int n_a, const float* b, int n_b, int n_res
 int s2s_ca_tm_superpose(const float* mobile, int n_mobile, const float* target, int n_res, double d0, double* tm, double* xform12,
                         void* stream);
 
+/* ---- lDDT: the superposition-free local distance difference test on CA atoms (csrc/ensemble_lddt.hip; the reference's own definition,
+ * src/models/loss.py:384-460, is its training-time `lddt` / `lddt_ca`; Mariani et al. 2013) ----
+ * For a reference structure a and a model b (n_res residues, residue i matched to residue i), d_x(i, j) = |x_i - x_j|:
+ *   P(a)      = {(i, j) ordered : |i - j| >= min_seq_sep, d_a(i, j) < cutoff}          (the environment comes from the FIRST argument)
+ *   hits      = sum over (i, j) in P(a) of #{t in {0.5, 1, 2, 4} : |d_a(i, j) - d_b(i, j)| < t}
+ *   lDDT(a->b) = hits / (4 |P(a)|),  1.0 when P(a) is empty (the limit of the reference's eps / eps; it covers n_res = 1).
+ * Per residue the sums run over the pairs of a fixed i; a residue without an included partner scores 1.0.  Not symmetric.
+ * Arithmetic: the float32 coordinates are widened to float64 and every distance is float64.  d_a is a square root; d_b is never formed:
+ * |d_a - d_b| < t is evaluated as d_b^2 < (d_a + t)^2 and (d_a - t < 0 or d_b^2 > (d_a - t)^2).  hits and |P| are integers and the score is one
+ * float64 division of them, so a value does not depend on the launch it is computed in.  A comparison with NaN is false: such a pair is
+ * neither included nor hit.  The reference's defaults are cutoff = 15.0 A and min_seq_sep = 1 (i != j).
+ * workspace (both entry points): caller-owned scratch, 8-byte aligned, of at least S2S_LDDT_WORKSPACE_BYTES(n_a, n_res) bytes (n_a = 1 for the
+ * per-residue form): per reference structure the list of its included pairs i > j -- c = 2 ceil(n_res (n_res - 1) / 4) slots of a float64
+ * d_a and an int32 (i << 16 | j) -- its length, and the partner count of every residue.  Nothing survives the call. */
+#define S2S_LDDT_MAX_RES 1024   /* a tile of 8 models stays in LDS as float32: 96 B per residue */
+#define S2S_LDDT_LIST_SLOTS(n_res) (((long long)(n_res) * ((long long)(n_res) - 1) / 2 + 1) / 2 * 2)
+#define S2S_LDDT_WORKSPACE_BYTES(n_a, n_res) ((long long)(n_a) * (12 * S2S_LDDT_LIST_SLOTS(n_res) + 8 + 4 * (long long)(n_res)))
+
+/* Every structure of a [n_a, n_res, 3] as the reference of every structure of b [n_b, n_res, 3] -> lddt [n_a, n_b] float64 in [0, 1].
+ * cutoff positive and finite, min_seq_sep >= 1, n_res <= S2S_LDDT_MAX_RES, n_a * n_b < 2^31 per call (the binding chunks rows).  b == a is
+ * allowed and not special-cased: the diagonal is exactly 1.0 because every pair of a structure hits under all four thresholds. */
+int s2s_ca_lddt_matrix(const float* a, int n_a, const float* b, int n_b, int n_res, double cutoff, int min_seq_sep, double* lddt,
+                       void* workspace, long long workspace_bytes, void* stream);
+
+/* model [n_model, n_res, 3] against the reference target [n_res, 3] -> per_res [n_model, n_res] and total [n_model] float64; total is bit for
+ * bit the s2s_ca_lddt_matrix entry of (target, model). */
+int s2s_ca_lddt_per_residue(const float* model, int n_model, const float* target, int n_res, double cutoff, int min_seq_sep,
+                            double* per_res, double* total, void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- Threshold clustering of an ensemble (csrc/ensemble_cluster.hip; no counterpart in the reference) ----
  * The GROMOS algorithm (Daura et al. 1999, `gmx cluster -method gromos`) on a symmetric neighbour relation i ~ j (i ~ i always): until no
  * structure is live, the live structure with the most live neighbours (the lowest index among equals) becomes the centre of the next

@@ -34,6 +34,7 @@ UNITS = {
     "ensemble_rmsd.hip": [],   # float64 throughout; contraction stays on (an fma only removes a rounding)
     "ensemble_tm.hip": [],     # (as above)
     "ensemble_cluster.hip": [],   # integer and float64 comparisons only
+    "ensemble_lddt.hip": [],      # float64 distances against squared bounds, integer sums
     # the MFMA chains are fully unrolled on purpose (accumulator tiles must be statically indexed)
     "pair_mlp.hip": ["-mllvm", "-pragma-unroll-threshold=10000000"],
     # (no SLP vectorisation in the split-f16 pair kernels: hipcc packs the LayerNorm / epilogue arithmetic into v_pk_*_f32, and a packed

@@ -14,7 +14,10 @@ Not in the reference (its paper's diversity figures came from external tools): m
 ``pairwise_rmsd``, ``diversity_rmsd``, ``coverage_rmsd``, ``superpose``, ``rmsf`` -- on csrc/ensemble_rmsd.hip.  Proper rotations only
 (a mirror image is not superposable), float64 arithmetic on the float32 coordinates, optional per-RESIDUE weights.  Its length-normalised
 companion, the TM-score under the identity correspondence -- ``tm_d0``, ``pairwise_tm``, ``diversity_tm``, ``coverage_tm``,
-``tm_superpose`` -- runs on csrc/ensemble_tm.hip.  Which states an ensemble visits: ``cluster_rmsd``, ``cluster_tm``,
+``tm_superpose`` -- runs on csrc/ensemble_tm.hip.  Where one global superposition is the wrong tool (a hinge, a floppy terminus, a
+disordered loop) the CA-lDDT needs none: ``pairwise_lddt``, ``lddt`` (per model or per residue), ``diversity_lddt``, ``coverage_lddt``,
+``cluster_lddt`` on csrc/ensemble_lddt.hip -- the definition of the reference's own ``lddt`` (src/models/loss.py:384-460), float64
+distances, integer counts; the first argument is the reference whose environment is scored, so the matrix is not symmetric.  Which states an ensemble visits: ``cluster_rmsd``, ``cluster_tm``, ``cluster_lddt``,
 ``cluster_from_matrix`` (GROMOS clustering at a cutoff, csrc/ensemble_cluster.hip) threshold those matrices chunk by chunk into packed
 neighbour bits and cluster them on the device; only labels, centres and sizes come back.
 """
@@ -300,6 +303,62 @@ def tm_superpose(coords, target):
     return ops.apply_xform(x, xform).cpu().numpy(), tm.cpu().numpy()
 
 
+# ---- lDDT: no superposition (csrc/ensemble_lddt.hip; the definition of src/models/loss.py:384-460) -------------------------------------
+def pairwise_lddt(a, b=None, cutoff=15.0, min_seq_sep=1) -> np.ndarray:
+    """CA-lDDT of every structure of ``b`` [Rb, L, 3] (default: ``a`` itself) in the environment of every structure of ``a`` [Ra, L, 3]
+    -> float64 [Ra, Rb] in [0, 1].  Entry (i, j): of the pairs of residues of ``a[i]`` closer than ``cutoff`` A and at least ``min_seq_sep``
+    apart in sequence, the mean fraction of the thresholds 0.5 / 1 / 2 / 4 A within which ``b[j]`` keeps the distance.  Not symmetric."""
+    return ops.ca_lddt_matrix(_dev(a), None if b is None else _dev(b), cutoff, min_seq_sep).cpu().numpy()
+
+
+def lddt(coords, target, per_residue=False) -> np.ndarray:
+    """CA-lDDT of every structure of ``coords`` [R, L, 3] against the reference ``target`` [L, 3] -> float64 [R], or with ``per_residue``
+    [R, L] (1.0 for a residue the target gives no partner), the reference's ``lddt(..., per_residue=)`` at cutoff 15 A."""
+    per_res, total = ops.ca_lddt_per_residue(_dev(coords), _dev(target)[0])
+    return (per_res if per_residue else total).cpu().numpy()
+
+
+def diversity_lddt(ca_coords_dict):
+    """Ensemble diversity: the mean lDDT over the ordered pairs i != j of each ensemble (1.0 for a single structure).  LOWER means more
+    diverse, the sense of ``diversity_tm``."""
+    out = {}
+    for k, v in ca_coords_dict.items():
+        x = _dev(v)
+        n = x.shape[0]
+        # (the diagonal is exactly 1.0)
+        out[k] = np.around((float(ops.ca_lddt_matrix(x).sum()) - n) / (n * (n - 1)), decimals=4) if n > 1 else 1.0
+    return out
+
+
+def _coverage_lddt_maxima(ref: torch.Tensor, samples: torch.Tensor, chunk_pairs=None):
+    """(per reference frame: max lDDT of any sample in its environment, per sample: max lDDT in the environment of any reference frame),
+    device float64, over row chunks of the reference x sample matrix with running maxima, as ``_coverage_maxima``."""
+    rows = ops.rmsd_row_chunk(samples.shape[0], COVERAGE_CHUNK_PAIRS if chunk_pairs is None else chunk_pairs)
+    per_ref = torch.empty(ref.shape[0], dtype=torch.float64, device=ref.device)
+    per_sample = torch.full((samples.shape[0],), -float("inf"), dtype=torch.float64, device=ref.device)
+    for r0 in range(0, ref.shape[0], rows):
+        m = ops.ca_lddt_matrix(ref[r0:r0 + rows], samples)
+        per_ref[r0:r0 + rows] = m.max(dim=1).values
+        per_sample = torch.maximum(per_sample, m.max(dim=0).values)
+    return per_ref, per_sample
+
+
+def coverage_lddt(ca_coords_dict, ref_key="target", chunk_pairs=None):
+    """How well each ensemble covers the reference ensemble -> (recall, precision), the reference ensemble's frames being the lDDT
+    references: recall[k] = mean over reference frames of the best lDDT any sample of k reaches in that frame's environment, precision[k]
+    = mean over samples of k of its best lDDT in any reference frame's environment (higher is better; the reference's own entries are 1.0)."""
+    ref = _dev(ca_coords_dict[ref_key])
+    recall, precision = {}, {}
+    for k, v in ca_coords_dict.items():
+        if k == ref_key:
+            continue
+        per_ref, per_sample = _coverage_lddt_maxima(ref, _dev(v), chunk_pairs)
+        recall[k] = np.around(float(per_ref.mean()), decimals=4)
+        precision[k] = np.around(float(per_sample.mean()), decimals=4)
+    recall[ref_key] = precision[ref_key] = 1.0
+    return recall, precision
+
+
 # ---- clustering at a cutoff (csrc/ensemble_cluster.hip) ----------------------------------------------------------------------------
 class ClusterResult(NamedTuple):
     """GROMOS clusters of R structures, most populated first: ``labels`` [R] (the cluster of every structure), ``centres`` [K] (the index
@@ -343,6 +402,19 @@ def cluster_tm(coords, cutoff: float, d0=None) -> ClusterResult:
     x = _dev(coords)
     n = x.shape[0]
     return _cluster_chunks(n, _chunk_rows(n, None), lambda r0, r1: ops.ca_tm_matrix(x[r0:r1], x, d0), cutoff, True)
+
+
+def cluster_lddt(coords, cutoff: float) -> ClusterResult:
+    """``cluster_rmsd`` under the symmetrised lDDT min(lddt(i -> j), lddt(j -> i)): i and j are neighbours iff each keeps the other's local
+    distances to ``cutoff``, 0 < cutoff <= 1.  Rows r0 .. r1 of the matrix and of its transpose come from two launches; an entry is the
+    same integer division wherever it is computed, so the relation is exactly symmetric."""
+    cutoff = float(cutoff)
+    if not 0.0 < cutoff <= 1.0:
+        raise ValueError(f"cluster_lddt: cutoff must be an lDDT in (0, 1], got {cutoff}")
+    x = _dev(coords)
+    n = x.shape[0]
+    return _cluster_chunks(n, _chunk_rows(n, None), lambda r0, r1: torch.minimum(ops.ca_lddt_matrix(x[r0:r1], x), ops.ca_lddt_matrix(x, x[r0:r1]).T),
+                           cutoff, True)
 
 
 def cluster_from_matrix(values, cutoff: float, at_least: bool = False) -> ClusterResult:

@@ -1,4 +1,4 @@
-"""Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition."""
+"""Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition, lDDT, clustering."""
 from typing import Optional
 
 import torch
@@ -8,6 +8,8 @@ from .binding import HipLibraryError, _check, _p, _req, _stream, load_library
 RMSD_LAUNCH_PAIRS = 2 ** 31 - 1   # s2s_ca_rmsd_matrix and s2s_ca_tm_matrix take fewer than 2^31 pairs per call
 TM_MAX_RES = 800                  # S2S_TM_MAX_RES: the chain length whose tiles fit the LDS of s2s_ca_tm_matrix
 TM_MAX_COLS = 4 * 65535           # structures of b per s2s_ca_tm_matrix call
+LDDT_MAX_RES = 1024               # S2S_LDDT_MAX_RES: the chain length whose tile of models fits the LDS of s2s_ca_lddt_matrix
+LDDT_WORKSPACE_BYTES = 256 << 20  # budget of the pair lists of one s2s_ca_lddt_matrix launch: rows of a are chunked to stay under it
 CLUSTER_MAX_N = 65536             # S2S_CLUSTER_MAX_N: structures per clustering (512 MB of neighbour bits)
 CLUSTER_ROUNDS_PER_SYNC = 32      # rounds of the greedy loop enqueued between two readbacks of its state
 
@@ -179,6 +181,72 @@ def ca_tm_superpose(mobile: torch.Tensor, target: torch.Tensor, d0: Optional[flo
     xform = torch.empty(R, 12, dtype=torch.float64, device=mobile.device)
     _check(lib.s2s_ca_tm_superpose(_p(mobile), R, _p(target), L, d0, _p(tm), _p(xform), _stream()), "s2s_ca_tm_superpose")
     return tm, xform
+
+
+def lddt_workspace_bytes(n_a: int, n_res: int) -> int:
+    """S2S_LDDT_WORKSPACE_BYTES: the scratch of one s2s_ca_lddt_matrix call with ``n_a`` reference structures of ``n_res`` residues."""
+    slots = (n_res * (n_res - 1) // 2 + 1) // 2 * 2
+    return n_a * (12 * slots + 8 + 4 * n_res)
+
+
+def _lddt_args(what: str, L: int, cutoff, min_seq_sep):
+    cutoff = float(cutoff)
+    if not 0.0 < cutoff < float("inf"):
+        raise HipLibraryError(f"{what}: cutoff must be a positive finite distance in Angstrom, got {cutoff}")
+    if isinstance(min_seq_sep, bool) or int(min_seq_sep) != min_seq_sep or min_seq_sep < 1:
+        raise HipLibraryError(f"{what}: min_seq_sep must be an integer >= 1, got {min_seq_sep}")
+    if L > LDDT_MAX_RES:
+        raise HipLibraryError(f"{what}: at most {LDDT_MAX_RES} residues, got {L}")
+    return cutoff, int(min_seq_sep)
+
+
+def ca_lddt_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, cutoff: float = 15.0, min_seq_sep: int = 1,
+                   max_pairs: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """CA-lDDT (include/str2str_hip.h: no superposition, residue i against residue i, float64) of every structure of b [Rb, L, 3] scored
+    in the environment of every structure of a [Ra, L, 3], fp32 device tensors -> [Ra, Rb] fp64 in [0, 1].  NOT symmetric: ``a[i]`` is the
+    reference, its pairs closer than ``cutoff`` and at least ``min_seq_sep`` apart in sequence are the ones scored.  ``b=None``: ``a``
+    against itself (the diagonal is exactly 1).  Rows of ``a`` are chunked so that the pair lists of one launch stay within
+    LDDT_WORKSPACE_BYTES and the pairs within ``max_pairs``; every entry is one division of two integers, bit for bit the same for any
+    chunking."""
+    b = a if b is None else b
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
+        raise HipLibraryError(f"ca_lddt_matrix: expected tensors, got {type(a).__name__} and {type(b).__name__}")
+    if a.ndim != 3 or b.ndim != 3 or a.shape[2] != 3 or b.shape[1:] != a.shape[1:] or a.shape[0] < 1 or b.shape[0] < 1 or a.shape[1] < 1:
+        raise HipLibraryError(f"ca_lddt_matrix: coordinates {tuple(a.shape)} and {tuple(b.shape)}")
+    (n_a, L), n_b = a.shape[:2], b.shape[0]
+    cutoff, min_seq_sep = _lddt_args("ca_lddt_matrix", L, cutoff, min_seq_sep)
+    _req(a, name="a"); _req(b, name="b")
+    if out is None:
+        out = torch.empty(n_a, n_b, dtype=torch.float64, device=a.device)
+    elif _req(out, torch.float64, "out").shape != (n_a, n_b):
+        raise HipLibraryError(f"ca_lddt_matrix: out {tuple(out.shape)} for {n_a} x {n_b} pairs")
+    rows = min(rmsd_row_chunk(n_b, max_pairs), max(1, LDDT_WORKSPACE_BYTES // lddt_workspace_bytes(1, L)), n_a)
+    lib = load_library()
+    ws = torch.empty(lddt_workspace_bytes(rows, L) // 8 + 1, dtype=torch.int64, device=a.device)
+    for r0 in range(0, n_a, rows):
+        n = min(rows, n_a - r0)
+        _check(lib.s2s_ca_lddt_matrix(_p(a[r0:r0 + n]), n, _p(b), n_b, L, cutoff, min_seq_sep, _p(out[r0:r0 + n]), _p(ws), ws.numel() * 8,
+                                      _stream()), "s2s_ca_lddt_matrix")
+    return out
+
+
+def ca_lddt_per_residue(model: torch.Tensor, target: torch.Tensor, cutoff: float = 15.0, min_seq_sep: int = 1):
+    """model [R, L, 3] scored in the environment of the reference target [L, 3] (fp32 device tensors) -> (per_res [R, L] fp64: the lDDT of
+    every residue, 1.0 where the target gives it no partner; total [R] fp64: bit for bit ``ca_lddt_matrix(target[None], model)[0]``)."""
+    if not (isinstance(model, torch.Tensor) and isinstance(target, torch.Tensor)):
+        raise HipLibraryError(f"ca_lddt_per_residue: expected tensors, got {type(model).__name__} and {type(target).__name__}")
+    if model.ndim != 3 or model.shape[2] != 3 or target.shape != model.shape[1:] or model.shape[0] < 1 or model.shape[1] < 1:
+        raise HipLibraryError(f"ca_lddt_per_residue: model {tuple(model.shape)}, target {tuple(target.shape)}")
+    R, L = model.shape[:2]
+    cutoff, min_seq_sep = _lddt_args("ca_lddt_per_residue", L, cutoff, min_seq_sep)
+    _req(model, name="model"); _req(target, name="target")
+    lib = load_library()
+    per_res = torch.empty(R, L, dtype=torch.float64, device=model.device)
+    total = torch.empty(R, dtype=torch.float64, device=model.device)
+    ws = torch.empty(lddt_workspace_bytes(1, L) // 8 + 1, dtype=torch.int64, device=model.device)
+    _check(lib.s2s_ca_lddt_per_residue(_p(model), R, _p(target), L, cutoff, min_seq_sep, _p(per_res), _p(total), _p(ws), ws.numel() * 8,
+                                       _stream()), "s2s_ca_lddt_per_residue")
+    return per_res, total
 
 
 def cluster_adjacency(values: torch.Tensor, cutoff: float, at_least: bool = False, row0: int = 0, adj: Optional[torch.Tensor] = None,
