@@ -2,7 +2,8 @@
 (reference: src/eval.py:102-173).  Composes configs/eval.yaml (hydra if installed, otherwise the built-in
 composer), instantiates datamodule / model / trainer from their `_target_`s, loads the checkpoint with the
 reference's key contract and runs ``trainer.predict``; when ``target_dir`` holds reference ensembles the samples are then
-scored (src/eval.py:47-99) with the device metrics of str2str_amd/metrics (validity, bonding validity, JS-PwD, JS-TICA, JS-Rg)
+scored (src/eval.py:47-99) with the device metrics of str2str_amd/metrics (validity, bonding validity, JS-PwD, JS-TICA, JS-Rg;
+``+extra_metrics=[...]`` adds columns out of EXTRA_METRICS, the backbone violations of the samples among them)
 into the reference's tab-separated ``metrics_<tag>_<mmdd-HH-MM>.csv``.  ``+cluster_cutoff=<A>`` also clusters every sampled ensemble
 (GROMOS at that RMSD, on the device) into ``clusters/<target>.pdb`` and ``clusters_<tag>_<mmdd-HH-MM>.csv`` next to it."""
 import logging
@@ -43,8 +44,10 @@ def load_model_checkpoint(model, ckpt_path):
     raise ValueError(f"ckpt_path {ckpt_path} is not a valid checkpoint file.")
 
 
-# optional columns: minimum RMSD under optimal superposition, TM-score under the identity correspondence, CA-lDDT (no superposition)
-EXTRA_METRICS = ("div_rmsd", "rmsd_recall", "rmsd_precision", "div_tm", "tm_recall", "tm_precision", "div_lddt", "lddt_recall", "lddt_precision")
+# optional columns: the violations of the full backbone (peptide geometry, clashes); minimum RMSD under optimal superposition, TM-score under
+# the identity correspondence, CA-lDDT (no superposition)
+BACKBONE_METRICS = ("val_bb_bond", "val_bb_clash", "viol_per_residue")
+EXTRA_METRICS = BACKBONE_METRICS + ("div_rmsd", "rmsd_recall", "rmsd_precision", "div_tm", "tm_recall", "tm_precision", "div_lddt", "lddt_recall", "lddt_precision")
 
 
 def metric_columns(extra_metrics=None):
@@ -83,7 +86,7 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     import numpy as np
     import pandas as pd
 
-    from str2str_amd.common.pdb_utils import extract_backbone_coords, select_pdb_models
+    from str2str_amd.common.pdb_utils import extract_backbone_atoms, extract_backbone_coords, select_pdb_models
     from str2str_amd.metrics import metrics
 
     if target_dir is None or not os.path.isdir(target_dir):
@@ -101,7 +104,7 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
            "tm_precision": lambda ca: metrics.coverage_tm(ca, ref_key="target")[1],
            "div_lddt": metrics.diversity_lddt, "lddt_recall": lambda ca: metrics.coverage_lddt(ca, ref_key="target")[0],
            "lddt_precision": lambda ca: metrics.coverage_lddt(ca, ref_key="target")[1]}
-    fns = {k: fns[k] for k in columns}
+    fns = {k: fns.get(k) for k in columns}
     eval_res = {k: {} for k in fns}
     clusters = {}
     for target in targets:
@@ -109,9 +112,18 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
         if not os.path.isfile(pred_file):
             continue
         ca = {"target": extract_backbone_coords(os.path.join(target_dir, f"{target}.pdb")), "pred": extract_backbone_coords(pred_file)}
+        backbone = None                        # the sampled N, CA, C, O, CB: read only when a column asks for them
         for name, fn in fns.items():
             try:
-                res = fn(ca, ref_key="target") if name.startswith("js_") else fn(ca)
+                if name in BACKBONE_METRICS:
+                    if backbone is None:
+                        atoms, aatype, residue_index = extract_backbone_atoms(pred_file)
+                        bond, clash = metrics.backbone_validity({"pred": atoms}, aatype, residue_index)
+                        backbone = {"val_bb_bond": bond, "val_bb_clash": clash,
+                                    "viol_per_residue": metrics.violation_rate({"pred": atoms}, aatype, residue_index)}
+                    res = backbone[name]
+                else:
+                    res = fn(ca, ref_key="target") if name.startswith("js_") else fn(ca)
             except (ValueError, NotImplementedError) as e:   # e.g. fewer reference frames than the TICA lag time: the other columns stand
                 log.warning(f"{name} on {target}: {e}")
                 eval_res[name][target] = float("nan")

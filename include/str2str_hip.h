@@ -478,6 +478,44 @@ int s2s_ca_lddt_matrix(const float* a, int n_a, const float* b, int n_b, int n_r
 int s2s_ca_lddt_per_residue(const float* model, int n_model, const float* target, int n_res, double cutoff, int min_seq_sep,
                             double* per_res, double* total, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- Backbone violations: is the sampled backbone chemically possible?  (csrc/ensemble_violations.hip; the definition is the reference's
+ * find_structural_violations / compute_violation_metrics, src/models/loss.py:714-1017, 1237-1314 -- the AlphaFold structural-violation terms --
+ * restricted to the five atoms the sampler writes) ----
+ * Per structure of atoms [n, n_res, 5, 3] (atom14 slots N, CA, C, O, CB), with atom_exists [n_res, 5] (bytes, != 0: the atom exists; GLY has
+ * no CB), aatype [n_res] (the reference's residue order: PRO = 14) and residue_index [n_res] shared by the n structures:
+ *  1. Connections k -> k + 1 (between_residue_bond_loss), eps = 1e-6 inside every square root, t = tolerance_factor:
+ *       c_n = sqrt(eps + |C_k - N_k+1|^2),  e_cn = sqrt(eps + (c_n - g)^2), g / sigma = 1.329 / 0.014, or 1.341 / 0.016 when k + 1 is PRO;
+ *       e_cacn = sqrt(eps + (cos(CA_k - C_k, N_k+1 - C_k) + 0.4473)^2), e_cnca = sqrt(eps + (cos(C_k - N_k+1, CA_k+1 - N_k+1) + 0.5203)^2),
+ *       the vectors divided by their sqrt(eps + |.|^2) lengths;  loss = max(e - t w, 0) and violated = e > t w with w = sigma, 0.014, 0.0353.
+ *     The width of the CA-C-N term is the C-N bond length's 0.014, not the 0.0311 of the cosine: the reference's own choice (loss.py:809), kept.
+ *     A term counts where residue_index[k + 1] - residue_index[k] == 1 and its atoms exist (C_k, N_k+1; + CA_k; + CA_k+1).
+ *     losses[., 0 .. 2] = sum of the counted losses / (number counted + 1e-6); per_residue_loss[., r] = half the UNMASKED loss sum
+ *     (the three losses, whether counted or not) of the connections r - 1 -> r and r -> r + 1; bond_mask[., r] = 1 if either connection is violated.
+ *  2. Clashes (between_residue_clash_loss): the pairs of existing atoms of residues with residue_index[i] < residue_index[j], except C_i - N_j
+ *     where residue_index[j] == residue_index[i] + 1.  d = sqrt(1e-10 + |.|^2), bound = r_a + r_b - clash_tolerance with r = 1.7 (C),
+ *     1.55 (N), 1.52 (O).  A pair clashes iff d < bound, its loss is max(bound - d, 0).  losses[., 3] = sum / (1e-6 + number of pairs);
+ *     clash_atom_mask[., r, a] = 1 if the atom is in a clashing pair; n_clash_pairs = the number of clashing pairs.
+ *  3. fractions[., 0 .. 3] (compute_violation_metrics; masked_mean's eps 1e-4): residues with bond_mask / (1e-4 + n_res); residues with a
+ *     clashing atom / (1e-4 + n_res); residues with either / (1e-4 + n_res); connections without a gap whose CA atoms exist and whose
+ *     sqrt(1e-6 + |CA_k - CA_k+1|^2) - 3.80209737096 > 1.5, over (1e-4 + the number of such connections).
+ * Left out: the reference's within-residue term (its bounds table is not in its tree, and inside a residue the backbone is an ideal rigid
+ * group by construction), the disulfide exemption (no SG), side-chain slots, gradients.  The reference's defaults: tolerance_factor = 12,
+ * clash_tolerance = 1.5.
+ * Arithmetic: the float32 coordinates are widened and everything is float64, one rounding per operation (no contraction).  A residue pair is
+ * expanded into its atom pairs only if d(CA_i, CA_j) < rho_i + rho_j + (3.4 - clash_tolerance), rho = the largest distance of a residue's
+ * existing atoms from its CA: a pair that fails cannot hold a clash, for any coordinates, so no output depends on this.  Every float64 sum
+ * is formed in an order that depends on n_res alone, so a structure's outputs do not depend on the launch it is computed in.  A comparison
+ * with NaN is false. */
+#define S2S_VIOL_MAX_RES 1024   /* the structure's atoms stay in LDS as float64: 144 B per residue with the per-residue state */
+
+/* No scratch.  n >= 1, 1 <= n_res <= S2S_VIOL_MAX_RES, both tolerances finite; otherwise hipErrorInvalidValue before any launch.
+ * losses [n, 4] and fractions [n, 4] float64 in the order above, per_residue_loss [n, n_res] float64, bond_mask [n, n_res] and
+ * clash_atom_mask [n, n_res, 5] bytes, n_clash_pairs [n] int. */
+int s2s_backbone_violations(const float* atoms, int n, int n_res, const unsigned char* atom_exists, const int* aatype,
+                            const int* residue_index, double tolerance_factor, double clash_tolerance, double* losses, double* fractions,
+                            double* per_residue_loss, unsigned char* bond_mask, unsigned char* clash_atom_mask, int* n_clash_pairs,
+                            void* stream);
+
 /* ---- Threshold clustering of an ensemble (csrc/ensemble_cluster.hip; no counterpart in the reference) ----
  * The GROMOS algorithm (Daura et al. 1999, `gmx cluster -method gromos`) on a symmetric neighbour relation i ~ j (i ~ i always): until no
  * structure is live, the live structure with the most live neighbours (the lowest index among equals) becomes the centre of the next

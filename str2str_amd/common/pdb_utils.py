@@ -260,3 +260,62 @@ def extract_backbone_coords(input_path: str, max_n_model: Optional[int] = None) 
     if max_n_model is not None and len(coords) > max_n_model > 0:
         coords = coords[:max_n_model]
     return coords
+
+
+_BACKBONE_SLOTS = {" N  ": 0, " CA ": 1, " C  ": 2, " O  ": 3, " CB ": 4}     # atom14 order of the five atoms the sampler writes
+
+
+def extract_backbone_atoms(input_path: str, max_n_model: Optional[int] = None):
+    """(atoms [n_models, L, 5, 3] float32 in atom14 slot order N, CA, C, O, CB; aatype [L] int64 in the residue order of
+    ``residue_constants.restypes``; residue_index [L] int64: the resSeq numbers) of a (multi-MODEL) PDB file.  The rules of
+    ``extract_backbone_coords``: ATOM and HETATM records of the standard and the common modified amino acids (a modified residue counts as
+    the standard one it derives from), the first alternate location of every atom, a C-alpha of an unknown residue is an error.  A GLY has no
+    CB (its slot is zero); any other missing N, CA, C, O or CB raises ValueError naming the residue."""
+    from . import residue_constants as rc
+
+    assert os.path.exists(input_path), f"File {input_path} does not exist."
+    if not input_path.endswith(".pdb"):
+        raise ValueError(f"Unrecognized input path {input_path}.")
+    models, cur = [], {}                       # per model: {(chain id, resSeq + iCode): [residue name, {slot: xyz}]} in file order
+
+    def close(cur):
+        names, xyz = [], np.zeros((len(cur), 5, 3), dtype=np.float32)
+        for r, (key, (name, found)) in enumerate(cur.items()):
+            std = name if name in _AMINO_ACIDS else _MODIFIED_AMINO_ACIDS[name]
+            need = [s for s in range(5) if not (s == 4 and std == "GLY")]
+            missing = [a.strip() for a, s in _BACKBONE_SLOTS.items() if s in need and s not in found]
+            if missing:
+                raise ValueError(f"{input_path}: model {len(models) + 1}: residue {name} {key[0]}{key[1].strip()} has no {', '.join(missing)}")
+            for s in need:
+                xyz[r, s] = found[s]
+            names.append((std, key))
+        return names, xyz
+
+    with open(input_path) as fh:
+        for ln in fh:
+            if ln.startswith(("ATOM", "HETATM")):
+                known = ln[17:20] in _AMINO_ACIDS or ln[17:20] in _MODIFIED_AMINO_ACIDS
+                if not known:
+                    if ln[12:16] == " CA ":
+                        raise ValueError(f"{input_path}: C-alpha of unknown residue {ln[17:20]!r} {ln[21]}{ln[22:27].strip()}: "
+                                         "not one of the standard or common modified amino acids (extend _MODIFIED_AMINO_ACIDS)")
+                    continue                   # water, ligands, ions
+                entry = cur.setdefault((ln[21], ln[22:27]), [ln[17:20], {}])
+                slot = _BACKBONE_SLOTS.get(ln[12:16])
+                if slot is not None and slot not in entry[1]:       # later altlocs of an atom already taken are skipped
+                    entry[1][slot] = (float(ln[30:38]), float(ln[38:46]), float(ln[46:54]))
+            elif ln.startswith("ENDMDL"):
+                models.append(close(cur)); cur = {}
+    if cur:
+        models.append(close(cur))
+    if not models:
+        raise ValueError(f"{input_path}: no amino-acid residues")
+    names = models[0][0]
+    if any(m[0] != names for m in models[1:]):
+        raise ValueError(f"{input_path}: the models do not hold the same residues (a truncated last model?)")
+    atoms = np.stack([m[1] for m in models])
+    aatype = np.array([rc.restype_order[rc.restype_3to1[std]] for std, _ in names], dtype=np.int64)
+    residue_index = np.array([int(key[1][:4]) for _, key in names], dtype=np.int64)
+    if max_n_model is not None and len(atoms) > max_n_model > 0:
+        atoms = atoms[:max_n_model]
+    return atoms, aatype, residue_index

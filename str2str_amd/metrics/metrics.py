@@ -19,7 +19,10 @@ disordered loop) the CA-lDDT needs none: ``pairwise_lddt``, ``lddt`` (per model 
 ``cluster_lddt`` on csrc/ensemble_lddt.hip -- the definition of the reference's own ``lddt`` (src/models/loss.py:384-460), float64
 distances, integer counts; the first argument is the reference whose environment is scored, so the matrix is not symmetric.  Which states an ensemble visits: ``cluster_rmsd``, ``cluster_tm``, ``cluster_lddt``,
 ``cluster_from_matrix`` (GROMOS clustering at a cutoff, csrc/ensemble_cluster.hip) threshold those matrices chunk by chunk into packed
-neighbour bits and cluster them on the device; only labels, centres and sizes come back.
+neighbour bits and cluster them on the device; only labels, centres and sizes come back.  All of these compare structures with each
+other; ``backbone_violations`` (csrc/ensemble_violations.hip) looks inside each one: the reference's between-residue bond, angle and clash
+terms (src/models/loss.py:714-1017, 1237-1314) on the full backbone the sampler writes, with ``backbone_validity`` and ``violation_rate``
+as its dict-in / dict-out companions.
 """
 from __future__ import annotations
 
@@ -357,6 +360,82 @@ def coverage_lddt(ca_coords_dict, ref_key="target", chunk_pairs=None):
         precision[k] = np.around(float(per_sample.mean()), decimals=4)
     recall[ref_key] = precision[ref_key] = 1.0
     return recall, precision
+
+
+# ---- backbone violations: inside each structure (csrc/ensemble_violations.hip; the definition of src/models/loss.py:714-1017, 1237-1314) ----
+GLY = 7                                       # aatype of glycine in the reference's residue order: no CB
+ATOM37_BACKBONE = (0, 1, 2, 4, 3)             # atom37 slots of N, CA, C, O, CB (atom14 slots 0 .. 4)
+
+
+class BackboneViolations(NamedTuple):
+    """Per structure of an ensemble [R, L, 5, 3]: the four flat-bottom loss means and the four fractions of the reference's
+    ``find_structural_violations`` / ``compute_violation_metrics`` (float64 [R]), the per-residue connection loss (float64 [R, L]),
+    ``bond_mask`` [R, L] (a residue at a violated connection), ``clash_atom_mask`` [R, L, 5] (N, CA, C, O, CB in a clashing pair), both
+    bool, and ``n_clash_pairs`` [R] int32."""
+    c_n_loss_mean: np.ndarray
+    ca_c_n_loss_mean: np.ndarray
+    c_n_ca_loss_mean: np.ndarray
+    clashes_mean_loss: np.ndarray
+    violations_between_residue_bond: np.ndarray
+    violations_between_residue_clash: np.ndarray
+    violations_per_residue: np.ndarray
+    violations_extreme_ca_ca_distance: np.ndarray
+    per_residue_loss_sum: np.ndarray
+    bond_mask: np.ndarray
+    clash_atom_mask: np.ndarray
+    n_clash_pairs: np.ndarray
+
+
+def _backbone_dev(atoms) -> torch.Tensor:
+    """[R, L, 5, 3] atom14 order, or [R, L, 37, 3] atom37 as the sampler returns it (one structure without the leading axis) -> device
+    float32 [R, L, 5, 3]."""
+    t = atoms if torch.is_tensor(atoms) else torch.as_tensor(np.asarray(atoms))
+    if t.ndim == 3:
+        t = t[None]
+    if t.ndim != 4 or t.shape[-1] != 3 or t.shape[-2] not in (5, 37):
+        raise ValueError(f"backbone atoms should be [R, L, 5, 3] (N, CA, C, O, CB) or [R, L, 37, 3] (atom37), got {tuple(t.shape)}")
+    if t.shape[-2] == 37:
+        t = t[:, :, list(ATOM37_BACKBONE)]
+    return t.to("cuda", torch.float32).contiguous()
+
+
+def backbone_violations(atoms, aatype=None, residue_index=None, tolerance_factor=12.0, clash_tolerance=1.5, max_structures=None) -> BackboneViolations:
+    """Is every backbone of the ensemble chemically possible?  The reference's structural-violation terms between residues (bond length and
+    the two angles at every peptide bond, clashes of the van der Waals spheres, extreme CA-CA steps; include/str2str_hip.h has the
+    formulas) of ``atoms`` [R, L, 5, 3] or atom37 [R, L, 37, 3], for the one sequence ``aatype`` [L] (default: all ALA; a GLY has no CB)
+    numbered ``residue_index`` [L] (default: 0 .. L - 1; a jump in the numbers is a chain break).  The tolerances are the reference's
+    defaults."""
+    x = _backbone_dev(atoms)
+    L = x.shape[1]
+    aatype = np.zeros(L, dtype=np.int64) if aatype is None else np.asarray(aatype.cpu() if torch.is_tensor(aatype) else aatype).reshape(-1)
+    residue_index = np.arange(L) if residue_index is None else np.asarray(residue_index.cpu() if torch.is_tensor(residue_index) else residue_index).reshape(-1)
+    if aatype.shape != (L,) or residue_index.shape != (L,):
+        raise ValueError(f"backbone_violations: aatype {aatype.shape} and residue_index {residue_index.shape} for {L} residues")
+    exists = np.ones((L, 5), dtype=np.uint8)
+    exists[aatype == GLY, 4] = 0
+    losses, fractions, per_res, bond_mask, clash_mask, n_pairs = ops.backbone_violations(x, exists, aatype, residue_index, tolerance_factor,
+                                                                                         clash_tolerance, max_structures)
+    losses, fractions = losses.cpu().numpy(), fractions.cpu().numpy()
+    return BackboneViolations(*losses.T, *fractions.T, per_res.cpu().numpy(), bond_mask.cpu().numpy().astype(bool),
+                              clash_mask.cpu().numpy().astype(bool), n_pairs.cpu().numpy())
+
+
+def backbone_validity(atoms_dict, aatype=None, residue_index=None):
+    """The full-backbone companions of ``validity`` / ``bonding_validity`` -> (val_bb_bond, val_bb_clash): per ensemble the share of
+    structures without a violated connection, and without a clash."""
+    bond, clash = {}, {}
+    for k, v in atoms_dict.items():
+        res = backbone_violations(v, aatype, residue_index)
+        bond[k] = np.around(1.0 - float(res.bond_mask.any(axis=1).mean()), decimals=4)
+        clash[k] = np.around(1.0 - float((res.n_clash_pairs > 0).mean()), decimals=4)
+    return bond, clash
+
+
+def violation_rate(atoms_dict, aatype=None, residue_index=None):
+    """Per ensemble the mean over its structures of ``violations_per_residue``: the fraction of residues at a violated connection or with
+    a clashing atom."""
+    return {k: np.around(float(backbone_violations(v, aatype, residue_index).violations_per_residue.mean()), decimals=4)
+            for k, v in atoms_dict.items()}
 
 
 # ---- clustering at a cutoff (csrc/ensemble_cluster.hip) ----------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-"""Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition, lDDT, clustering."""
+"""Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition, lDDT, clustering,
+backbone violations."""
 from typing import Optional
 
 import torch
@@ -10,6 +11,8 @@ TM_MAX_RES = 800                  # S2S_TM_MAX_RES: the chain length whose tiles
 TM_MAX_COLS = 4 * 65535           # structures of b per s2s_ca_tm_matrix call
 LDDT_MAX_RES = 1024               # S2S_LDDT_MAX_RES: the chain length whose tile of models fits the LDS of s2s_ca_lddt_matrix
 LDDT_WORKSPACE_BYTES = 256 << 20  # budget of the pair lists of one s2s_ca_lddt_matrix launch: rows of a are chunked to stay under it
+VIOL_MAX_RES = 1024               # S2S_VIOL_MAX_RES: the chain length whose atoms fit the LDS of s2s_backbone_violations as float64
+VIOL_MAX_STRUCTURES = 1 << 20     # structures per s2s_backbone_violations launch, unless max_structures says less
 CLUSTER_MAX_N = 65536             # S2S_CLUSTER_MAX_N: structures per clustering (512 MB of neighbour bits)
 CLUSTER_ROUNDS_PER_SYNC = 32      # rounds of the greedy loop enqueued between two readbacks of its state
 
@@ -247,6 +250,60 @@ def ca_lddt_per_residue(model: torch.Tensor, target: torch.Tensor, cutoff: float
     _check(lib.s2s_ca_lddt_per_residue(_p(model), R, _p(target), L, cutoff, min_seq_sep, _p(per_res), _p(total), _p(ws), ws.numel() * 8,
                                        _stream()), "s2s_ca_lddt_per_residue")
     return per_res, total
+
+
+def _viol_small(what: str, v, shape, dtype) -> torch.Tensor:
+    """A per-sequence input of backbone_violations (a few KB; tensor, array or list), checked, as a contiguous tensor of the C ABI's type."""
+    t = torch.as_tensor(v)
+    if t.shape != shape or t.is_floating_point() or t.is_complex():
+        raise HipLibraryError(f"backbone_violations: {what}: expected integers of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    if dtype == torch.uint8:
+        return (t != 0).to(torch.uint8).contiguous()
+    if t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) > 2 ** 31 - 1):
+        raise HipLibraryError(f"backbone_violations: {what} does not fit 32 bits")
+    return t.to(dtype).contiguous()
+
+
+def backbone_violations(atoms: torch.Tensor, atom_exists, aatype, residue_index, tolerance_factor: float = 12.0, clash_tolerance: float = 1.5,
+                        max_structures: Optional[int] = None):
+    """The structural violations of include/str2str_hip.h (the reference's between-residue bond, angle and clash terms and its extreme
+    CA-CA steps) of every structure of atoms [R, L, 5, 3] fp32 device tensor, atom14 slots N, CA, C, O, CB.  ``atom_exists`` [L, 5]
+    (non-zero: the atom exists), ``aatype`` [L] (the reference's residue order) and ``residue_index`` [L] belong to the one sequence of the
+    ensemble.  -> device tensors (losses [R, 4] fp64: C-N, CA-C-N, C-N-CA, clash means; fractions [R, 4] fp64: residues with a violated
+    connection, with a clashing atom, with either, extreme CA-CA steps; per_residue_loss [R, L] fp64; bond_mask [R, L] uint8;
+    clash_atom_mask [R, L, 5] uint8; n_clash_pairs [R] int32).  ``max_structures`` bounds the structures of one launch; a structure's
+    results are bit for bit the same for any value."""
+    if not isinstance(atoms, torch.Tensor):
+        raise HipLibraryError(f"backbone_violations: expected a tensor, got {type(atoms).__name__}")
+    if atoms.ndim != 4 or atoms.shape[2:] != (5, 3) or atoms.shape[0] < 1 or atoms.shape[1] < 1:
+        raise HipLibraryError(f"backbone_violations: atoms {tuple(atoms.shape)}, expected [R, L, 5, 3]")
+    R, L = atoms.shape[:2]
+    if L > VIOL_MAX_RES:
+        raise HipLibraryError(f"backbone_violations: at most {VIOL_MAX_RES} residues, got {L}")
+    tolerance_factor, clash_tolerance = float(tolerance_factor), float(clash_tolerance)
+    if not (abs(tolerance_factor) < float("inf") and abs(clash_tolerance) < float("inf")):
+        raise HipLibraryError(f"backbone_violations: tolerances must be finite, got {tolerance_factor} and {clash_tolerance}")
+    if max_structures is not None and (isinstance(max_structures, bool) or int(max_structures) != max_structures or max_structures < 1):
+        raise HipLibraryError(f"backbone_violations: max_structures must be an integer >= 1, got {max_structures}")
+    exists = _viol_small("atom_exists", atom_exists, (L, 5), torch.uint8)
+    aatype = _viol_small("aatype", aatype, (L,), torch.int32)
+    residue_index = _viol_small("residue_index", residue_index, (L,), torch.int32)
+    _req(atoms, name="atoms")
+    dev = atoms.device
+    exists, aatype, residue_index = exists.to(dev), aatype.to(dev), residue_index.to(dev)
+    lib = load_library()
+    losses, fractions = (torch.empty(R, 4, dtype=torch.float64, device=dev) for _ in range(2))
+    per_res = torch.empty(R, L, dtype=torch.float64, device=dev)
+    bond_mask = torch.empty(R, L, dtype=torch.uint8, device=dev)
+    clash_mask = torch.empty(R, L, 5, dtype=torch.uint8, device=dev)
+    n_pairs = torch.empty(R, dtype=torch.int32, device=dev)
+    rows = VIOL_MAX_STRUCTURES if max_structures is None else min(int(max_structures), VIOL_MAX_STRUCTURES)
+    for r0 in range(0, R, rows):
+        n = min(rows, R - r0)
+        _check(lib.s2s_backbone_violations(_p(atoms[r0:r0 + n]), n, L, _p(exists), _p(aatype), _p(residue_index), tolerance_factor, clash_tolerance,
+                                           _p(losses[r0:r0 + n]), _p(fractions[r0:r0 + n]), _p(per_res[r0:r0 + n]), _p(bond_mask[r0:r0 + n]),
+                                           _p(clash_mask[r0:r0 + n]), _p(n_pairs[r0:r0 + n]), _stream()), "s2s_backbone_violations")
+    return losses, fractions, per_res, bond_mask, clash_mask, n_pairs
 
 
 def cluster_adjacency(values: torch.Tensor, cutoff: float, at_least: bool = False, row0: int = 0, adj: Optional[torch.Tensor] = None,

@@ -1,0 +1,241 @@
+"""Backbone violations on the device (csrc/ensemble_violations.hip) against the float64 numpy restatement of their definition in
+tests/ref_violations.py.
+
+Every case here is a parity input: tests/test_ensemble_violations_cpu.py asserts that its nearest comparison (an atom pair's distance against
+its bound, a connection error against its width, a CA-CA excess against 1.5 A) is at least 1e-10 from flipping, and the kernel forms every
+term as the yardstick does, in float64 with one rounding per operation.  Masks, counts and the fractions made of them are therefore equal.  A
+loss mean is a sum of n_terms non-negative terms, formed in another fixed order on either side: it may differ by at most
+n_terms 2^-52 max(1, |value|), the a-priori bound of such a sum.
+"""
+import functools
+import glob
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ref_violations as ref
+import violations_cases as cases
+from conftest import ROOT, golden, record_margin
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+ULP = 2.0 ** -52
+
+
+def _dev(x):
+    return torch.as_tensor(np.asarray(x)).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(L, R):
+    """(atoms, atom_exists, aatype, residue_index, the yardstick's outputs) of one shape, computed once."""
+    atoms, exists, aatype, ri = cases.ensemble(L, R)
+    want = ref.ensemble(atoms, exists, aatype, ri)
+    for v in want.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return atoms, exists, aatype, ri, want
+
+
+def _held(got, want, where=""):
+    """A BackboneViolations against the yardstick's dict: integers and their fractions equal, sums within the a-priori bound."""
+    for k in ("bond_mask", "clash_atom_mask", "n_clash_pairs"):
+        g = getattr(got, k)
+        assert g.shape == want[k].shape and (g == want[k]).all(), (where, k)
+    for k in ref.FRACTIONS:
+        assert (getattr(got, k) == want[k]).all(), (where, k)
+    for k in ref.LOSSES:
+        n = want["n_terms"][k]
+        g, w = getattr(got, k), want[k]
+        bound = n * ULP * np.maximum(1.0, np.abs(w))
+        err = float((np.abs(g - w) / np.maximum(1.0, np.abs(w))).max())
+        print(f"{where} {k}: n_terms {n}, max error {err:.3e} of {n * ULP:.3e}")
+        record_margin("ensemble_violations_loss_mean_per_term_ulp", err / ULP / max(n, 1), 1.0)
+        assert (np.abs(g - w) <= bound).all(), (where, k, err)
+    err = float((np.abs(got.per_residue_loss_sum - want["per_residue_loss_sum"]) / np.maximum(1.0, np.abs(want["per_residue_loss_sum"]))).max())
+    record_margin("ensemble_violations_per_residue_loss_ulp", err / ULP, 6.0)
+    assert err <= 6 * ULP, (where, err)                        # two connections of three terms each
+
+
+@pytest.mark.parametrize("L,R", cases.SHAPES)
+def test_violations_against_float64_reference(L, R):
+    from str2str_amd.metrics import metrics
+
+    atoms, exists, aatype, ri, want = reference(L, R)
+    assert ref.margin(atoms, exists, aatype, ri) >= ref.MARGIN
+    if L >= 2 and R >= 3:                                      # no residue pair passes the prefilter / every pair does
+        ext, com = (ref.prefilter_survivors(atoms[k], exists, ri) for k in (cases.EXTENDED, cases.COMPACT))
+        assert ext[0] == 0 and com[0] == com[1] == L * (L - 1) // 2
+        assert want["n_clash_pairs"][cases.EXTENDED] == 0 and want["n_clash_pairs"][cases.COMPACT] == want["n_terms"]["clashes_mean_loss"]
+    got = metrics.backbone_violations(atoms, aatype, ri)
+    assert got.c_n_loss_mean.dtype == np.float64 and got.bond_mask.dtype == bool and got.n_clash_pairs.dtype == np.int32
+    assert got.per_residue_loss_sum.shape == (R, L) and got.clash_atom_mask.shape == (R, L, 5)
+    _held(got, want, f"L={L} R={R}")
+    if L == 1:
+        assert all((getattr(got, k) == 0.0).all() for k in ref.LOSSES + ref.FRACTIONS) and not got.bond_mask.any() and not got.clash_atom_mask.any()
+
+
+def test_other_tolerances_and_a_general_atom_mask():
+    from str2str_amd import ops
+
+    atoms, exists, aatype, ri, _ = reference(31, 9)
+    rng = np.random.default_rng(4)
+    holes = exists & (rng.random(exists.shape) > 0.15)         # any atom may be missing, the CA too
+    numbers = ri.copy()
+    numbers[5:9] = numbers[5:9][::-1]                          # not monotonic, and one number twice
+    numbers[20] = numbers[19]
+    for ex, nums, tol, clash in ((exists, ri, 4.0, 1.2), (holes, ri, 12.0, 1.5), (exists, numbers, 12.0, 1.5), (holes, numbers, 7.5, 0.9)):
+        assert ref.margin(atoms, ex, aatype, nums, tol, clash) >= ref.MARGIN
+        want = ref.ensemble(atoms, ex, aatype, nums, tol, clash)
+        out = ops.backbone_violations(_dev(atoms), ex, aatype, nums, tol, clash)
+        assert all(t.is_cuda for t in out) and [t.dtype for t in out] == [torch.float64] * 3 + [torch.uint8] * 2 + [torch.int32]
+        losses, fractions, per_res, bond_mask, clash_mask, n_pairs = (t.cpu().numpy() for t in out)
+        assert (bond_mask.astype(bool) == want["bond_mask"]).all() and (clash_mask.astype(bool) == want["clash_atom_mask"]).all()
+        assert (n_pairs == want["n_clash_pairs"]).all()
+        for q, k in enumerate(ref.FRACTIONS):
+            assert (fractions[:, q] == want[k]).all(), k
+        for q, k in enumerate(ref.LOSSES):
+            assert (np.abs(losses[:, q] - want[k]) <= want["n_terms"][k] * ULP * np.maximum(1.0, np.abs(want[k]))).all(), k
+        assert np.abs(per_res - want["per_residue_loss_sum"]).max() <= 6 * ULP * max(1.0, np.abs(per_res).max())
+
+
+@pytest.mark.parametrize("tag", ("ideal12", "ideal40", "stretched", "o_n", "hairpin"))
+def test_fixture_cases_against_the_reference_masks(tag):
+    """The reference's own masks (float32, tests/golden/violations.npz) through the device; the losses to the reference's precision."""
+    from str2str_amd.metrics import metrics
+
+    g = golden("violations.npz")
+    atoms, exists, aatype, ri = cases.fixture_cases()[tag]
+    got = metrics.backbone_violations(atoms, aatype, ri)
+    assert (got.bond_mask[0] == g[f"{tag}_bond_mask"]).all() and (got.clash_atom_mask[0] == g[f"{tag}_clash_atom_mask"]).all()
+    for k in ref.LOSSES + ref.FRACTIONS + ("per_residue_loss_sum",):
+        want = g[f"{tag}_{k}"].astype(np.float64)
+        assert (np.abs(getattr(got, k)[0] - want) <= 5e-7 * np.maximum(1.0, np.abs(want))).all(), k
+
+
+def test_chunking_and_repeats_are_bit_identical():
+    from str2str_amd import ops
+
+    atoms, exists, aatype, ri, _ = reference(65, 17)
+    x = _dev(atoms)
+    whole = ops.backbone_violations(x, exists, aatype, ri)
+    again = ops.backbone_violations(x, exists, aatype, ri)
+    assert all(torch.equal(a, b) for a, b in zip(whole, again))
+    for max_structures in (1, 5, 17):
+        part = ops.backbone_violations(x, exists, aatype, ri, max_structures=max_structures)
+        assert all(torch.equal(a, b) for a, b in zip(whole, part)), max_structures
+    # a structure's results do not depend on its neighbours in the launch
+    alone = ops.backbone_violations(x[3:4].contiguous(), exists, aatype, ri)
+    assert all(torch.equal(a[3:4], b) for a, b in zip(whole, alone))
+
+
+def test_atom37_input_equals_atom14_input():
+    from str2str_amd.metrics import metrics
+
+    atoms, exists, aatype, ri, want = reference(13, 17)
+    atom37 = np.zeros((17, 13, 37, 3), dtype=np.float32)
+    atom37[:, :, list(metrics.ATOM37_BACKBONE)] = atoms        # N, CA, C, CB, O, ...: the sampler's layout
+    a, b = metrics.backbone_violations(atoms, aatype, ri), metrics.backbone_violations(_dev(atom37), aatype, ri)
+    assert all((u == v).all() for u, v in zip(a, b))
+    _held(b, want, "atom37")
+    one = metrics.backbone_violations(atoms[4], aatype, ri)     # a single structure without the leading axis
+    assert all((u[4:5] == v).all() for u, v in zip(a, one))
+    # the defaults: all ALA (every CB exists), numbered 0 .. L - 1 (no break)
+    plain = metrics.backbone_violations(atoms)
+    w = ref.ensemble(atoms, np.ones((13, 5), dtype=bool), np.zeros(13, dtype=np.int64), np.arange(13))
+    if ref.margin(atoms, np.ones((13, 5), dtype=bool), np.zeros(13, dtype=np.int64), np.arange(13)) >= ref.MARGIN:
+        _held(plain, w, "defaults")
+
+
+def test_validity_and_rate_metrics():
+    from str2str_amd.metrics import metrics
+
+    t_atoms, _, aatype, ri, t_want = reference(31, 9)
+    p_atoms = cases.ensemble(31, 9)[0][::-1][:6].copy()         # another mix of the same sequence's members
+    p_want = ref.ensemble(p_atoms, ref.exists_from_aatype(aatype), aatype, ri)
+    assert ref.margin(p_atoms, ref.exists_from_aatype(aatype), aatype, ri) >= ref.MARGIN
+    both = {"target": t_atoms, "pred": p_atoms}
+    bond, clash = metrics.backbone_validity(both, aatype, ri)
+    rate = metrics.violation_rate(both, aatype, ri)
+    for k, w in (("target", t_want), ("pred", p_want)):
+        assert bond[k] == np.around(1.0 - w["bond_mask"].any(1).mean(), decimals=4)
+        assert clash[k] == np.around(1.0 - (w["n_clash_pairs"] > 0).mean(), decimals=4)
+        assert rate[k] == np.around(w["violations_per_residue"].mean(), decimals=4)
+        assert 0.0 < bond[k] < 1.0 and 0.0 < clash[k] < 1.0 and 0.0 < rate[k] < 1.0
+
+
+def _eval_entry():
+    spec = importlib.util.spec_from_file_location("s2s_eval_entry_violations", os.path.join(ROOT, "eval.py"))
+    entry = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(entry)
+    return entry
+
+
+def test_eval_backbone_columns(tmp_path):
+    """Two targets written with the project's own writer; the three columns hold the yardstick's values for what the reader returns, and a
+    run without them gives the five columns of before."""
+    from str2str_amd.common.pdb_utils import atom37_to_pdb, extract_backbone_atoms
+    from str2str_amd.metrics import metrics
+
+    entry = _eval_entry()
+    target_dir = tmp_path / "targets"
+    target_dir.mkdir()
+    five = ["val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"]
+    extra = ["val_bb_bond", "val_bb_clash", "viol_per_residue"]
+    ensembles = {}
+    for name, (L, R) in (("one", (31, 9)), ("two", (13, 17))):
+        atoms, _, aatype, ri, _ = reference(L, R)
+        atom37 = np.zeros((R, L, 37, 3), dtype=np.float32)
+        atom37[:, :, list(metrics.ATOM37_BACKBONE)] = atoms + 10.0   # (away from the origin: the writer takes an atom at 0, 0, 0 for absent)
+        atom37[:, aatype == ref.GLY, 3] = 0.0                  # the writer leaves a GLY's CB out
+        ensembles[name] = (atom37, aatype, ri)
+        atom37_to_pdb(str(target_dir / f"{name}.pdb"), atom37[:3], aatype=aatype, residue_index=ri)
+    for sub, names in (("plain", None), ("extra", extra)):
+        pred_dir = tmp_path / sub / "samples" / "all"
+        pred_dir.mkdir(parents=True)
+        for name, (atom37, aatype, ri) in ensembles.items():
+            atom37_to_pdb(str(pred_dir / f"{name}.pdb"), atom37, aatype=aatype, residue_index=ri)
+        entry.evaluate_prediction(str(pred_dir), str(target_dir), tag="t", extra_metrics=names)
+        files = glob.glob(str(tmp_path / sub / "metrics_t_*.csv"))
+        assert len(files) == 1
+        rows = {r[0]: r[1:] for r in (ln.rstrip("\n").split("\t") for ln in open(files[0]))}
+        assert rows[""] == five + (names or []) and set(rows) == {"", "one", "two", "mean"}
+        if not names:
+            plain = rows
+            continue
+        assert {k: v[:5] for k, v in rows.items()} == plain      # the five columns of a run without the new ones
+        for name in ensembles:
+            atoms, aatype, ri = extract_backbone_atoms(str(pred_dir / f"{name}.pdb"))      # coordinates at the PDB's three decimals
+            assert ref.margin(atoms, ref.exists_from_aatype(aatype), aatype, ri) >= ref.MARGIN
+            w = ref.ensemble(atoms, ref.exists_from_aatype(aatype), aatype, ri)
+            want = [np.around(1.0 - w["bond_mask"].any(1).mean(), decimals=4), np.around(1.0 - (w["n_clash_pairs"] > 0).mean(), decimals=4),
+                    np.around(w["violations_per_residue"].mean(), decimals=4)]
+            assert [float(v) for v in rows[name][5:]] == [float(v) for v in want], name
+
+
+def test_sampler_output_goes_straight_into_the_metric(tmp_path):
+    """4 replicas x 24 residues x 5 steps from the synthetic chain through forward_backward: the atom37 device tensor into the metric, against
+    the yardstick on the same coordinates.  Seed 42 (the first tried) has the margin asserted below."""
+    from str2str_amd.common.rigid_utils import Rigid
+    from str2str_amd.factory import build_diffuser, build_synthetic_net
+    from str2str_amd.metrics import metrics
+    from str2str_amd.sampler import forward_backward
+    from str2str_amd.synth import synth_chain
+
+    feats = synth_chain(24)
+    net = build_synthetic_net(seed=0, sigma_final=0.002, device="cuda:0")
+    rig0 = Rigid.from_tensor_4x4(feats["rigidgroups_gt_frames"][..., 0, :, :].repeat(4, 1, 1, 1))
+    torch.manual_seed(42)
+    atom37 = forward_backward(net, build_diffuser(str(tmp_path)), feats, rig0, 1.0, num_timesteps=5, device="cuda:0")
+    assert atom37.is_cuda and atom37.shape == (4, 24, 37, 3) and atom37.dtype == torch.float32
+    x = atom37[:, :, list(metrics.ATOM37_BACKBONE)].cpu().numpy()
+    aatype = feats["aatype"].reshape(-1).cpu().numpy()
+    exists, numbers = ref.exists_from_aatype(aatype), np.arange(24)
+    m = ref.margin(x, exists, aatype, numbers)
+    print(f"sampler output: margin {m:.3e}")
+    assert m >= ref.MARGIN
+    _held(metrics.backbone_violations(atom37, aatype), ref.ensemble(x, exists, aatype, numbers), "sampler")
