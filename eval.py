@@ -5,7 +5,10 @@ reference's key contract and runs ``trainer.predict``; when ``target_dir`` holds
 scored (src/eval.py:47-99) with the device metrics of str2str_amd/metrics (validity, bonding validity, JS-PwD, JS-TICA, JS-Rg;
 ``+extra_metrics=[...]`` adds columns out of EXTRA_METRICS, the backbone violations of the samples among them)
 into the reference's tab-separated ``metrics_<tag>_<mmdd-HH-MM>.csv``.  ``+cluster_cutoff=<A>`` also clusters every sampled ensemble
-(GROMOS at that RMSD, on the device) into ``clusters/<target>.pdb`` and ``clusters_<tag>_<mmdd-HH-MM>.csv`` next to it."""
+(GROMOS at that RMSD, on the device) into ``clusters/<target>.pdb`` and ``clusters_<tag>_<mmdd-HH-MM>.csv`` next to it.
+``+secondary_structure=true`` also assigns Kabsch & Sander's states to the sampled and the target ensembles (on the device) and writes
+``ss_<tag>_<mmdd-HH-MM>.csv`` (helix and strand content, their distance from the target's, the Ramachandran JS distance) and the
+per-residue propensities ``secondary_structure/<target>.csv``."""
 import logging
 import os
 import sys
@@ -72,13 +75,57 @@ def cluster_summary(sizes):
             "top5_population": np.around(sizes[:5].sum() / total, decimals=4), "n_singletons": int((sizes == 1).sum())}
 
 
-def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None, cluster_cutoff=None):
+SS_COLUMNS = ("ss_helix", "ss_strand", "ss_helix_target", "ss_strand_target", "ss_mae", "js_rama")
+SS_CLASSES = ("helix", "strand", "other")
+
+
+def secondary_structure_switch(value) -> bool:
+    """``+secondary_structure=...`` as a bool: absent, null and false leave everything as it was."""
+    if value is None or isinstance(value, bool):
+        return bool(value)
+    if isinstance(value, str) and value.strip().lower() in ("true", "false", "1", "0", "yes", "no"):
+        return value.strip().lower() in ("true", "1", "yes")
+    raise ValueError(f"secondary_structure {value!r}: expected true or false")
+
+
+def secondary_structure_row(pred_file, target_file, log=log):
+    """One row of the ss csv (SS_COLUMNS) and the per-residue propensities {"pred": [L, 3], "target": [L, 3] or None} of one target.  A
+    target without a full backbone (a CA trace) leaves NaN in the columns that need it."""
+    import numpy as np
+
+    from str2str_amd.common.pdb_utils import extract_backbone_atoms
+    from str2str_amd.metrics import metrics
+
+    atoms, aatype, residue_index = extract_backbone_atoms(pred_file)
+    both = {"pred": atoms}
+    try:
+        t_atoms, t_aatype, t_index = extract_backbone_atoms(target_file)
+        if t_atoms.shape[1] != atoms.shape[1]:
+            raise ValueError(f"{t_atoms.shape[1]} residues for the samples' {atoms.shape[1]}")
+        both["target"] = t_atoms
+    except ValueError as e:
+        log.warning(f"secondary structure of the target {target_file}: {e}")
+    row = dict.fromkeys(SS_COLUMNS, float("nan"))
+    prop = metrics.ss_propensity(both, aatype, residue_index)
+    row["ss_helix"], row["ss_strand"] = (np.around(float(prop["pred"][:, q].mean()), decimals=4) for q in (0, 1))
+    if "target" in both:
+        row["ss_helix_target"], row["ss_strand_target"] = (np.around(float(prop["target"][:, q].mean()), decimals=4) for q in (0, 1))
+        row["ss_mae"] = np.around(float((0.5 * np.abs(prop["pred"] - prop["target"]).sum(1)).mean()), decimals=4)
+        row["js_rama"] = metrics.js_rama(both, ref_key="target", residue_index=residue_index)["pred"]
+    return row, {"pred": prop["pred"], "target": prop.get("target")}, residue_index
+
+
+def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None, cluster_cutoff=None,
+                        secondary_structure=None):
     """reference src/eval.py:47-99: one row per target, one column per metric, plus the mean row.  ``extra_metrics``: names out of
     EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's).
     ``cluster_cutoff`` (A; None: nothing of this happens): the ``pred`` ensemble of every target is clustered by ``metrics.cluster_rmsd``;
     ``clusters/<target>.pdb`` receives the centres' MODELs, most populated first, and ``clusters_<tag>_<mmdd-HH-MM>.csv`` one row per
-    target (CLUSTER_COLUMNS), both next to the metrics csv."""
+    target (CLUSTER_COLUMNS), both next to the metrics csv.  ``secondary_structure`` (true; otherwise nothing of this happens): the
+    states of the ``pred`` and the ``target`` ensemble of every target; ``ss_<tag>_<mmdd-HH-MM>.csv`` receives one row per target
+    (SS_COLUMNS) and ``secondary_structure/<target>.csv`` the per-residue propensities of both."""
     columns = metric_columns(extra_metrics)
+    secondary_structure = secondary_structure_switch(secondary_structure)
     if cluster_cutoff is not None and not 0.0 < float(cluster_cutoff) < float("inf"):
         raise ValueError(f"cluster_cutoff {cluster_cutoff}: expected a positive finite RMSD in Angstrom")
     from time import strftime
@@ -106,7 +153,7 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
            "lddt_precision": lambda ca: metrics.coverage_lddt(ca, ref_key="target")[1]}
     fns = {k: fns.get(k) for k in columns}
     eval_res = {k: {} for k in fns}
-    clusters = {}
+    clusters, ss_rows = {}, {}
     for target in targets:
         pred_file = os.path.join(pred_dir, f"{target}.pdb")
         if not os.path.isfile(pred_file):
@@ -133,12 +180,23 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
             res = metrics.cluster_rmsd(ca["pred"], float(cluster_cutoff))
             select_pdb_models(pred_file, res.centres, os.path.join(output_dir, "clusters", f"{target}.pdb"))
             clusters[target] = cluster_summary(res.sizes)
+        if secondary_structure:
+            ss_rows[target], prop, numbers = secondary_structure_row(pred_file, os.path.join(target_dir, f"{target}.pdb"))
+            table = {"residue_index": numbers}
+            for k in ("pred", "target"):
+                for q, c in enumerate(SS_CLASSES):
+                    table[f"{k}_{c}"] = np.full(len(numbers), np.nan) if prop[k] is None else np.around(prop[k][:, q], decimals=4)
+            os.makedirs(os.path.join(output_dir, "secondary_structure"), exist_ok=True)
+            pd.DataFrame(table).to_csv(os.path.join(output_dir, "secondary_structure", f"{target}.csv"), index=False, sep="\t")
     df = pd.DataFrame.from_dict(eval_res)
     df.loc["mean"] = np.around(df.mean(), decimals=4)
     df.to_csv(os.path.join(output_dir, f"metrics_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
     if cluster_cutoff is not None:
         pd.DataFrame.from_dict(clusters, orient="index", columns=list(CLUSTER_COLUMNS)).to_csv(
             os.path.join(output_dir, f"clusters_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
+    if secondary_structure:
+        pd.DataFrame.from_dict(ss_rows, orient="index", columns=list(SS_COLUMNS)).to_csv(
+            os.path.join(output_dir, f"ss_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
     return df.loc["mean"]
 
 
@@ -147,7 +205,8 @@ def evaluate(cfg):
     if pred_dir and os.path.isdir(pred_dir):
         log.info(f"Found pre-computed prediction directory {pred_dir}.")
         return evaluate_prediction(pred_dir, target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"),
-                                   extra_metrics=cfg.get("extra_metrics"), cluster_cutoff=cfg.get("cluster_cutoff"))
+                                   extra_metrics=cfg.get("extra_metrics"), cluster_cutoff=cfg.get("cluster_cutoff"),
+                                   secondary_structure=cfg.get("secondary_structure"))
     log.info(f"Instantiating datamodule <{cfg.data['_target_']}>")
     datamodule = C.instantiate(cfg.data)
     log.info(f"Instantiating model <{cfg.model['_target_']}>")
@@ -174,7 +233,7 @@ def evaluate(cfg):
     pred_dir = trainer.predict(model=model, dataloaders=dataloaders, ckpt_path=ckpt_path)[-1]
     log.info(f"Samples written under {pred_dir}.")
     if int(os.environ.get("RANK", "0")) == 0 and cfg.get("target_dir"):
-        log.info(f"metrics: {dict(evaluate_prediction(pred_dir, target_dir=cfg.get('target_dir'), tag=cfg.get('task_name'), extra_metrics=cfg.get('extra_metrics'), cluster_cutoff=cfg.get('cluster_cutoff')))}")
+        log.info(f"metrics: {dict(evaluate_prediction(pred_dir, target_dir=cfg.get('target_dir'), tag=cfg.get('task_name'), extra_metrics=cfg.get('extra_metrics'), cluster_cutoff=cfg.get('cluster_cutoff'), secondary_structure=cfg.get('secondary_structure')))}")
     return pred_dir
 
 

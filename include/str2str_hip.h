@@ -516,6 +516,47 @@ int s2s_backbone_violations(const float* atoms, int n, int n_res, const unsigned
                             double* per_residue_loss, unsigned char* bond_mask, unsigned char* clash_atom_mask, int* n_clash_pairs,
                             void* stream);
 
+/* ---- Secondary structure and backbone torsions: what is each conformation?  (csrc/ensemble_ss.hip; Kabsch & Sander, Biopolymers 22
+ * (1983) 2577; no counterpart in the reference beyond its torsion angles) ----
+ * Per structure of atoms [n, n_res, 5, 3] (atom14 slots N, CA, C, O, CB; CB is not used), with aatype [n_res] (the reference's residue
+ * order: PRO = 14) and residue_index [n_res] shared by the n structures.  Indices i, j are positions 0 .. L - 1 in the chain, L = n_res.
+ *  Connection and segments.  Residue j is connected iff residue_index[j] == residue_index[j - 1] + 1 (residue 0 never is).  Segments are
+ *     the maximal runs of connected residues; a range a .. b is unbroken iff residues a + 1 .. b are connected.
+ *  Amide hydrogen.  Residue j has one iff it is connected and not PRO:  H_j = N_j + (C_j-1 - O_j-1) / |C_j-1 - O_j-1|.
+ *  Energy of C=O of i accepting N-H of j:  E(i -> j) = 27.888 (((1 / r(O_i, N_j) + 1 / r(C_i, H_j)) - 1 / r(O_i, H_j)) - 1 / r(C_i, N_j))
+ *     kcal/mol; if any of the four distances is below 0.5 A, E = -9.9 (DSSP's rule).
+ *  H-bond.  hb(i -> j) iff j has H, j != i, j != i + 1, |CA_i - CA_j| < 9.0 and E(i -> j) < -0.5.  The 9.0 A test is DSSP's own prefilter
+ *     and part of the definition.  DEPARTURE 1 from the DSSP program: the threshold alone decides; there is no bookkeeping of the two
+ *     best bonds per group.
+ *  n-turn, n = 3, 4, 5.  turn_n(i) iff i + n < L, i .. i + n is unbroken and hb(i -> i + n).
+ *  Bridge, for 1 <= i, j <= L - 2, |i - j| >= 3, i - 1 .. i + 1 and j - 1 .. j + 1 unbroken:
+ *     par(i, j)  = [hb(i - 1 -> j) and hb(j -> i + 1)] or [hb(j - 1 -> i) and hb(i -> j + 1)];
+ *     anti(i, j) = [hb(i -> j) and hb(j -> i)] or [hb(i - 1 -> j + 1) and hb(j - 1 -> i + 1)].
+ *  Ladder.  i is in a ladder iff for some j: par(i, j) and (par(i + 1, j + 1) or par(i - 1, j - 1)), or
+ *     anti(i, j) and (anti(i + 1, j - 1) or anti(i - 1, j + 1)).  DEPARTURE 2: the beta-bulge rule, which merges two ladders across a
+ *     short gap, is left out.
+ *  Bend at i, for 2 <= i <= L - 3 with i - 2 .. i + 2 unbroken, iff cos(CA_i - CA_i-2, CA_i+2 - CA_i) < cos 70 degrees.
+ *  States.  From '-', in this order:  1. 'B' for a residue in any bridge, then 'E' over it for a residue in a ladder;  2. 'H' on i .. i + 3
+ *     wherever turn_4(i - 1) and turn_4(i), unconditionally;  3. 'G' on i .. i + 2 wherever turn_3(i - 1) and turn_3(i) and all three
+ *     residues are '-' or 'G';  4. 'I' on i .. i + 4 wherever turn_5(i - 1) and turn_5(i) and all five are '-' or 'I';  5. 'T' on
+ *     i + 1 .. i + n - 1 of every n-turn where the residue is still '-';  6. 'S' at a bend where the residue is still '-'.  Steps 3 and 4
+ *     only add the letter they tolerate, so each is decided against the state after the step before it.
+ *  N-H -> O column.  hb_energy[j] = the lowest E(i -> j) over the acceptors i that pass everything but the energy test (j has H, j != i,
+ *     j != i + 1, |CA_i - CA_j| < 9.0), hb_partner[j] that i, the lowest among equals; 0.0 and -1 when there is none.
+ *  Torsions in radians in (-pi, pi], IUPAC sign, dihedral(p0, p1, p2, p3) = atan2(|b2| b1 . (b2 x b3), (b1 x b2) . (b2 x b3)) with
+ *     b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2:  phi_i = (C_i-1, N_i, CA_i, C_i), psi_i = (N_i, CA_i, C_i, N_i+1),
+ *     omega_i = (CA_i-1, C_i-1, N_i, CA_i), stored at residue i (the reference's "pre-omega").  phi_i and omega_i are defined iff i is
+ *     connected, psi_i iff i + 1 is; an undefined angle is 0.0.
+ * Arithmetic: the float32 coordinates are widened and everything is float64, one rounding per operation (no contraction); a distance is
+ * sqrt((dx dx + dy dy) + dz dz).  A comparison with NaN is false.  A structure's outputs depend on its own coordinates alone. */
+#define S2S_SS_MAX_RES 704   /* four atoms and H as float64 planes plus the bond relation, L x ceil(L / 64) words: 150 KiB of LDS */
+
+/* No scratch.  n >= 1, 1 <= n_res <= S2S_SS_MAX_RES; otherwise hipErrorInvalidValue before any launch.  ss [n, n_res] bytes (the ASCII
+ * letters - B E H G I T S), n_hbonds [n] int (the pairs with hb(i -> j)), hb_energy [n, n_res] float64, hb_partner [n, n_res] int,
+ * torsions [n, n_res, 3] float64 (phi, psi, omega). */
+int s2s_secondary_structure(const float* atoms, int n, int n_res, const int* aatype, const int* residue_index, unsigned char* ss,
+                            int* n_hbonds, double* hb_energy, int* hb_partner, double* torsions, void* stream);
+
 /* ---- Threshold clustering of an ensemble (csrc/ensemble_cluster.hip; no counterpart in the reference) ----
  * The GROMOS algorithm (Daura et al. 1999, `gmx cluster -method gromos`) on a symmetric neighbour relation i ~ j (i ~ i always): until no
  * structure is live, the live structure with the most live neighbours (the lowest index among equals) becomes the centre of the next

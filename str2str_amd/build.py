@@ -36,6 +36,7 @@ UNITS = {
     "ensemble_cluster.hip": [],   # integer and float64 comparisons only
     "ensemble_lddt.hip": [],      # float64 distances against squared bounds, integer sums
     "ensemble_violations.hip": ["-ffp-contract=off"],   # every float64 term rounds like the numpy yardstick's
+    "ensemble_ss.hip": ["-ffp-contract=off"],           # (as above: energies and cosines decide letters)
     # the MFMA chains are fully unrolled on purpose (accumulator tiles must be statically indexed)
     "pair_mlp.hip": ["-mllvm", "-pragma-unroll-threshold=10000000"],
     # (no SLP vectorisation in the split-f16 pair kernels: hipcc packs the LayerNorm / epilogue arithmetic into v_pk_*_f32, and a packed

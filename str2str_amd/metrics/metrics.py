@@ -22,7 +22,9 @@ distances, integer counts; the first argument is the reference whose environment
 neighbour bits and cluster them on the device; only labels, centres and sizes come back.  All of these compare structures with each
 other; ``backbone_violations`` (csrc/ensemble_violations.hip) looks inside each one: the reference's between-residue bond, angle and clash
 terms (src/models/loss.py:714-1017, 1237-1314) on the full backbone the sampler writes, with ``backbone_validity`` and ``violation_rate``
-as its dict-in / dict-out companions.
+as its dict-in / dict-out companions.  What a conformation is: ``secondary_structure`` (csrc/ensemble_ss.hip) assigns Kabsch & Sander's
+eight states from the backbone hydrogen bonds and ``backbone_torsions`` gives phi, psi, omega; ``ss_propensity``, ``ss_content``,
+``ss_mae`` and ``js_rama`` are the ensemble summaries built on them.
 """
 from __future__ import annotations
 
@@ -436,6 +438,104 @@ def violation_rate(atoms_dict, aatype=None, residue_index=None):
     a clashing atom."""
     return {k: np.around(float(backbone_violations(v, aatype, residue_index).violations_per_residue.mean()), decimals=4)
             for k, v in atoms_dict.items()}
+
+
+# ---- secondary structure and backbone torsions (csrc/ensemble_ss.hip; Kabsch & Sander 1983, include/str2str_hip.h has the definition) ----
+HELIX_STATES, STRAND_STATES = (b"H", b"G", b"I"), (b"E", b"B")
+
+
+class SecondaryStructure(NamedTuple):
+    """Per structure of an ensemble [R, L, 5, 3]: ``ss`` [R, L] numpy 'S1' (- B E H G I T S), ``n_hbonds`` [R] int32 (backbone hydrogen
+    bonds), and DSSP's N-H -> O column: ``hbond_energy`` [R, L] float64 (kcal/mol) and ``hbond_partner`` [R, L] int32, the best acceptor
+    of every amide hydrogen (0.0 and -1 where there is none)."""
+    ss: np.ndarray
+    n_hbonds: np.ndarray
+    hbond_energy: np.ndarray
+    hbond_partner: np.ndarray
+
+
+def _sequence_arrays(fn, L, aatype, residue_index):
+    """The defaults of the per-sequence arguments: all ALA, numbered 0 .. L - 1."""
+    aatype = np.zeros(L, dtype=np.int64) if aatype is None else np.asarray(aatype.cpu() if torch.is_tensor(aatype) else aatype).reshape(-1)
+    residue_index = np.arange(L) if residue_index is None else np.asarray(residue_index.cpu() if torch.is_tensor(residue_index) else residue_index).reshape(-1)
+    if aatype.shape != (L,) or residue_index.shape != (L,):
+        raise ValueError(f"{fn}: aatype {aatype.shape} and residue_index {residue_index.shape} for {L} residues")
+    return aatype, residue_index
+
+
+def secondary_structure(atoms, aatype=None, residue_index=None, max_structures=None) -> SecondaryStructure:
+    """What is every conformation of the ensemble?  Kabsch & Sander's assignment (hydrogen-bond energy below -0.5 kcal/mol, n-turns,
+    bridges, ladders, bends; the energy threshold alone makes a bond and beta-bulges are not merged: include/str2str_hip.h) of ``atoms``
+    [R, L, 5, 3] or atom37 [R, L, 37, 3], for the one sequence ``aatype`` [L] (default: all ALA; a PRO has no amide hydrogen) numbered
+    ``residue_index`` [L] (default: 0 .. L - 1; a jump in the numbers is a chain break)."""
+    x = _backbone_dev(atoms)
+    aatype, residue_index = _sequence_arrays("secondary_structure", x.shape[1], aatype, residue_index)
+    ss, n_hbonds, energy, partner, _ = ops.secondary_structure(x, aatype, residue_index, max_structures)
+    return SecondaryStructure(ss.cpu().numpy().view("S1"), n_hbonds.cpu().numpy(), energy.cpu().numpy(), partner.cpu().numpy())
+
+
+def ss_strings(result) -> list:
+    """One string of state letters per structure of a ``SecondaryStructure`` (or of its ``ss`` array)."""
+    ss = np.atleast_2d(result.ss if isinstance(result, SecondaryStructure) else result)
+    return [row.tobytes().decode("ascii") for row in ss]
+
+
+def backbone_torsions(atoms, residue_index=None):
+    """-> (angles float64 [R, L, 3]: phi, psi, omega in radians in (-pi, pi], IUPAC sign, omega_i being the bond before residue i;
+    mask bool [L, 3]: phi and omega are defined where residue i follows i - 1 in the numbering, psi where i + 1 follows i; an undefined
+    angle is 0.0)."""
+    x = _backbone_dev(atoms)
+    L = x.shape[1]
+    _, residue_index = _sequence_arrays("backbone_torsions", L, None, residue_index)
+    angles = ops.secondary_structure(x, np.zeros(L, dtype=np.int64), residue_index)[4].cpu().numpy()
+    conn = np.zeros(L, dtype=bool)
+    conn[1:] = residue_index[1:].astype(np.int64) == residue_index[:-1].astype(np.int64) + 1
+    return angles, np.stack([conn, np.append(conn[1:], False), conn], axis=1)
+
+
+def _propensity(ss: np.ndarray) -> np.ndarray:
+    """ss 'S1' [R, L] -> float64 [L, 3]: the fractions of the structures in which a residue is helix, strand, other."""
+    helix, strand = np.isin(ss, HELIX_STATES), np.isin(ss, STRAND_STATES)
+    return np.stack([helix.mean(0), strand.mean(0), (~helix & ~strand).mean(0)], axis=1)
+
+
+def ss_propensity(atoms_dict, aatype=None, residue_index=None):
+    """Per ensemble the per-residue fractions of helix (H, G, I), strand (E, B) and other -> {k: float64 [L, 3]}."""
+    return {k: _propensity(secondary_structure(v, aatype, residue_index).ss) for k, v in atoms_dict.items()}
+
+
+def ss_content(atoms_dict, aatype=None, residue_index=None):
+    """-> (helix, strand): per ensemble the mean fraction of residues in helix (H, G, I) and in strand (E, B)."""
+    prop = ss_propensity(atoms_dict, aatype, residue_index)
+    return ({k: np.around(float(p[:, 0].mean()), decimals=4) for k, p in prop.items()},
+            {k: np.around(float(p[:, 1].mean()), decimals=4) for k, p in prop.items()})
+
+
+def ss_mae(atoms_dict, ref_key="target", aatype=None, residue_index=None):
+    """Per ensemble the mean over the residues of half the L1 distance of its (helix, strand, other) propensities from the reference
+    ensemble's: 0 for equal propensities, 1 where every residue is in another class."""
+    prop = ss_propensity(atoms_dict, aatype, residue_index)
+    out = {k: np.around(float((0.5 * np.abs(p - prop[ref_key]).sum(1)).mean()), decimals=4) for k, p in prop.items() if k != ref_key}
+    out[ref_key] = 0.0
+    return out
+
+
+def _rama_histogram(angles: np.ndarray, mask: np.ndarray, n_bins: int) -> np.ndarray:
+    """The phi / psi histogram over [-pi, pi)^2 of every structure's residues with both angles defined, flattened, with PSEUDO_C."""
+    both = mask[:, 0] & mask[:, 1]
+    phi, psi = angles[:, both, 0].reshape(-1), angles[:, both, 1].reshape(-1)
+    wrap = lambda a: np.where(a >= math.pi, a - 2.0 * math.pi, a)   # noqa: E731  (pi itself belongs to the first bin)
+    h = np.histogram2d(wrap(phi), wrap(psi), bins=n_bins, range=((-math.pi, math.pi), (-math.pi, math.pi)))[0]
+    return h.reshape(-1) + PSEUDO_C
+
+
+def js_rama(atoms_dict, ref_key="target", n_bins=36, residue_index=None):
+    """Jensen-Shannon distance of the Ramachandran (phi, psi) histograms, n_bins x n_bins over [-pi, pi)^2, pooled over all structures
+    and all residues with both angles defined.  The angles come from the device; the histogram tail is numpy, as for ``js_rg``."""
+    binned = {k: _rama_histogram(*backbone_torsions(v, residue_index), n_bins) for k, v in atoms_dict.items()}
+    out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
+    out[ref_key] = 0.0
+    return out
 
 
 # ---- clustering at a cutoff (csrc/ensemble_cluster.hip) ----------------------------------------------------------------------------

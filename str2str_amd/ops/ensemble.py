@@ -1,5 +1,5 @@
 """Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition, lDDT, clustering,
-backbone violations."""
+backbone violations, secondary structure and torsions."""
 from typing import Optional
 
 import torch
@@ -13,6 +13,8 @@ LDDT_MAX_RES = 1024               # S2S_LDDT_MAX_RES: the chain length whose til
 LDDT_WORKSPACE_BYTES = 256 << 20  # budget of the pair lists of one s2s_ca_lddt_matrix launch: rows of a are chunked to stay under it
 VIOL_MAX_RES = 1024               # S2S_VIOL_MAX_RES: the chain length whose atoms fit the LDS of s2s_backbone_violations as float64
 VIOL_MAX_STRUCTURES = 1 << 20     # structures per s2s_backbone_violations launch, unless max_structures says less
+SS_MAX_RES = 704                  # S2S_SS_MAX_RES: the chain length whose atoms and bond relation fit the LDS of s2s_secondary_structure
+SS_MAX_STRUCTURES = 1 << 20       # structures per s2s_secondary_structure launch, unless max_structures says less
 CLUSTER_MAX_N = 65536             # S2S_CLUSTER_MAX_N: structures per clustering (512 MB of neighbour bits)
 CLUSTER_ROUNDS_PER_SYNC = 32      # rounds of the greedy loop enqueued between two readbacks of its state
 
@@ -252,15 +254,15 @@ def ca_lddt_per_residue(model: torch.Tensor, target: torch.Tensor, cutoff: float
     return per_res, total
 
 
-def _viol_small(what: str, v, shape, dtype) -> torch.Tensor:
-    """A per-sequence input of backbone_violations (a few KB; tensor, array or list), checked, as a contiguous tensor of the C ABI's type."""
+def _viol_small(what: str, v, shape, dtype, fn: str = "backbone_violations") -> torch.Tensor:
+    """A per-sequence input of ``fn`` (a few KB; tensor, array or list), checked, as a contiguous tensor of the C ABI's type."""
     t = torch.as_tensor(v)
     if t.shape != shape or t.is_floating_point() or t.is_complex():
-        raise HipLibraryError(f"backbone_violations: {what}: expected integers of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+        raise HipLibraryError(f"{fn}: {what}: expected integers of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
     if dtype == torch.uint8:
         return (t != 0).to(torch.uint8).contiguous()
     if t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) > 2 ** 31 - 1):
-        raise HipLibraryError(f"backbone_violations: {what} does not fit 32 bits")
+        raise HipLibraryError(f"{fn}: {what} does not fit 32 bits")
     return t.to(dtype).contiguous()
 
 
@@ -304,6 +306,43 @@ def backbone_violations(atoms: torch.Tensor, atom_exists, aatype, residue_index,
                                            _p(losses[r0:r0 + n]), _p(fractions[r0:r0 + n]), _p(per_res[r0:r0 + n]), _p(bond_mask[r0:r0 + n]),
                                            _p(clash_mask[r0:r0 + n]), _p(n_pairs[r0:r0 + n]), _stream()), "s2s_backbone_violations")
     return losses, fractions, per_res, bond_mask, clash_mask, n_pairs
+
+
+def secondary_structure(atoms: torch.Tensor, aatype, residue_index, max_structures: Optional[int] = None):
+    """The secondary structure and the backbone torsions of include/str2str_hip.h (Kabsch & Sander's hydrogen bonds, turns, bridges,
+    ladders and bends; phi, psi, omega) of every structure of atoms [R, L, 5, 3] fp32 device tensor, atom14 slots N, CA, C, O, CB.
+    ``aatype`` [L] (the reference's residue order; a PRO has no amide hydrogen) and ``residue_index`` [L] (a jump in the numbers is a chain
+    break) belong to the one sequence of the ensemble.  -> device tensors (ss [R, L] uint8: the ASCII letters - B E H G I T S; n_hbonds [R]
+    int32; hb_energy [R, L] fp64 and hb_partner [R, L] int32: the best acceptor of every N-H, 0.0 and -1 where there is none; torsions
+    [R, L, 3] fp64: phi, psi, omega in radians, 0.0 where undefined).  ``max_structures`` bounds the structures of one launch; a
+    structure's results are bit for bit the same for any value."""
+    if not isinstance(atoms, torch.Tensor):
+        raise HipLibraryError(f"secondary_structure: expected a tensor, got {type(atoms).__name__}")
+    if atoms.ndim != 4 or atoms.shape[2:] != (5, 3) or atoms.shape[0] < 1 or atoms.shape[1] < 1:
+        raise HipLibraryError(f"secondary_structure: atoms {tuple(atoms.shape)}, expected [R, L, 5, 3]")
+    R, L = atoms.shape[:2]
+    if L > SS_MAX_RES:
+        raise HipLibraryError(f"secondary_structure: at most {SS_MAX_RES} residues, got {L}")
+    if max_structures is not None and (isinstance(max_structures, bool) or int(max_structures) != max_structures or max_structures < 1):
+        raise HipLibraryError(f"secondary_structure: max_structures must be an integer >= 1, got {max_structures}")
+    aatype = _viol_small("aatype", aatype, (L,), torch.int32, "secondary_structure")
+    residue_index = _viol_small("residue_index", residue_index, (L,), torch.int32, "secondary_structure")
+    _req(atoms, name="atoms")
+    dev = atoms.device
+    aatype, residue_index = aatype.to(dev), residue_index.to(dev)
+    lib = load_library()
+    ss = torch.empty(R, L, dtype=torch.uint8, device=dev)
+    n_hbonds = torch.empty(R, dtype=torch.int32, device=dev)
+    hb_energy = torch.empty(R, L, dtype=torch.float64, device=dev)
+    hb_partner = torch.empty(R, L, dtype=torch.int32, device=dev)
+    torsions = torch.empty(R, L, 3, dtype=torch.float64, device=dev)
+    rows = SS_MAX_STRUCTURES if max_structures is None else min(int(max_structures), SS_MAX_STRUCTURES)
+    for r0 in range(0, R, rows):
+        n = min(rows, R - r0)
+        _check(lib.s2s_secondary_structure(_p(atoms[r0:r0 + n]), n, L, _p(aatype), _p(residue_index), _p(ss[r0:r0 + n]), _p(n_hbonds[r0:r0 + n]),
+                                           _p(hb_energy[r0:r0 + n]), _p(hb_partner[r0:r0 + n]), _p(torsions[r0:r0 + n]), _stream()),
+               "s2s_secondary_structure")
+    return ss, n_hbonds, hb_energy, hb_partner, torsions
 
 
 def cluster_adjacency(values: torch.Tensor, cutoff: float, at_least: bool = False, row0: int = 0, adj: Optional[torch.Tensor] = None,
