@@ -145,37 +145,35 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     tag = tag if tag is not None else "dev"
     fns = {"val_clash": metrics.validity, "val_bond": metrics.bonding_validity, "js_pwd": metrics.js_pwd, "js_rg": metrics.js_rg,
            "js_tica": metrics.js_tica,   # the reference's five columns, in its order (src/eval.py:64-70)
-           "div_rmsd": metrics.diversity_rmsd, "rmsd_recall": lambda ca: metrics.coverage_rmsd(ca, ref_key="target")[0],
-           "rmsd_precision": lambda ca: metrics.coverage_rmsd(ca, ref_key="target")[1],
-           "div_tm": metrics.diversity_tm, "tm_recall": lambda ca: metrics.coverage_tm(ca, ref_key="target")[0],
-           "tm_precision": lambda ca: metrics.coverage_tm(ca, ref_key="target")[1],
-           "div_lddt": metrics.diversity_lddt, "lddt_recall": lambda ca: metrics.coverage_lddt(ca, ref_key="target")[0],
-           "lddt_precision": lambda ca: metrics.coverage_lddt(ca, ref_key="target")[1]}
-    fns = {k: fns.get(k) for k in columns}
-    eval_res = {k: {} for k in fns}
+           "div_rmsd": metrics.diversity_rmsd, "div_tm": metrics.diversity_tm, "div_lddt": metrics.diversity_lddt}
+    coverage = {"rmsd": metrics.coverage_rmsd, "tm": metrics.coverage_tm, "lddt": metrics.coverage_lddt}
+    eval_res = {k: {} for k in columns}
     clusters, ss_rows = {}, {}
     for target in targets:
         pred_file = os.path.join(pred_dir, f"{target}.pdb")
         if not os.path.isfile(pred_file):
             continue
         ca = {"target": extract_backbone_coords(os.path.join(target_dir, f"{target}.pdb")), "pred": extract_backbone_coords(pred_file)}
-        backbone = None                        # the sampled N, CA, C, O, CB: read only when a column asks for them
-        for name, fn in fns.items():
+        shared = {}                            # what several columns read: computed once per target, when the first of them asks
+        for name in columns:
+            family, _, part = name.rpartition("_")
             try:
-                if name in BACKBONE_METRICS:
-                    if backbone is None:
-                        atoms, aatype, residue_index = extract_backbone_atoms(pred_file)
-                        bond, clash = metrics.backbone_validity({"pred": atoms}, aatype, residue_index)
-                        backbone = {"val_bb_bond": bond, "val_bb_clash": clash,
-                                    "viol_per_residue": metrics.violation_rate({"pred": atoms}, aatype, residue_index)}
-                    res = backbone[name]
+                if name in BACKBONE_METRICS:           # the violations of the sampled N, CA, C, O, CB
+                    if "backbone" not in shared:
+                        v = metrics.backbone_violations(*extract_backbone_atoms(pred_file))
+                        shared["backbone"] = dict(zip(BACKBONE_METRICS, (*metrics.validity_of_violations(v), metrics.rate_of_violations(v))))
+                    value = shared["backbone"][name]
+                elif family in coverage:               # <family>_recall and <family>_precision
+                    if family not in shared:
+                        shared[family] = dict(zip(("recall", "precision"), coverage[family](ca, ref_key="target")))
+                    value = shared[family][part]["pred"]
                 else:
-                    res = fn(ca, ref_key="target") if name.startswith("js_") else fn(ca)
+                    res = fns[name](ca, ref_key="target") if name.startswith("js_") else fns[name](ca)
+                    value = res[0]["pred"] if name == "js_tica" else res["pred"]
             except (ValueError, NotImplementedError) as e:   # e.g. fewer reference frames than the TICA lag time: the other columns stand
                 log.warning(f"{name} on {target}: {e}")
-                eval_res[name][target] = float("nan")
-                continue
-            eval_res[name][target] = res[0]["pred"] if name == "js_tica" else res["pred"]
+                value = float("nan")
+            eval_res[name][target] = value
         if cluster_cutoff is not None:
             res = metrics.cluster_rmsd(ca["pred"], float(cluster_cutoff))
             select_pdb_models(pred_file, res.centres, os.path.join(output_dir, "clusters", f"{target}.pdb"))
@@ -202,11 +200,11 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
 
 def evaluate(cfg):
     pred_dir = cfg.get("pred_dir")
+    scoring = dict(target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"), extra_metrics=cfg.get("extra_metrics"),
+                   cluster_cutoff=cfg.get("cluster_cutoff"), secondary_structure=cfg.get("secondary_structure"))
     if pred_dir and os.path.isdir(pred_dir):
         log.info(f"Found pre-computed prediction directory {pred_dir}.")
-        return evaluate_prediction(pred_dir, target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"),
-                                   extra_metrics=cfg.get("extra_metrics"), cluster_cutoff=cfg.get("cluster_cutoff"),
-                                   secondary_structure=cfg.get("secondary_structure"))
+        return evaluate_prediction(pred_dir, **scoring)
     log.info(f"Instantiating datamodule <{cfg.data['_target_']}>")
     datamodule = C.instantiate(cfg.data)
     log.info(f"Instantiating model <{cfg.model['_target_']}>")
@@ -233,7 +231,7 @@ def evaluate(cfg):
     pred_dir = trainer.predict(model=model, dataloaders=dataloaders, ckpt_path=ckpt_path)[-1]
     log.info(f"Samples written under {pred_dir}.")
     if int(os.environ.get("RANK", "0")) == 0 and cfg.get("target_dir"):
-        log.info(f"metrics: {dict(evaluate_prediction(pred_dir, target_dir=cfg.get('target_dir'), tag=cfg.get('task_name'), extra_metrics=cfg.get('extra_metrics'), cluster_cutoff=cfg.get('cluster_cutoff'), secondary_structure=cfg.get('secondary_structure')))}")
+        log.info(f"metrics: {dict(evaluate_prediction(pred_dir, **scoring))}")
     return pred_dir
 
 

@@ -9,10 +9,12 @@
 // the host may enqueue any number of rounds between two readbacks of the state.
 #include <hip/hip_runtime.h>
 
+#include "ensemble_common.h"
 #include "str2str_hip.h"
 
 namespace {
 
+using ensemble::wave_sum;
 using u64 = unsigned long long;
 constexpr int PICK_THREADS = 1024;                  // one workgroup; one thread per word of a row in the prefix sum
 constexpr int MAX_N = S2S_CLUSTER_MAX_N;            // 64 * PICK_THREADS
@@ -33,11 +35,6 @@ __global__ void __launch_bounds__(256) adjacency_kernel(const double* __restrict
     }
     const u64 word = __ballot(near);
     if ((threadIdx.x & 63) == 0) adj[(long long)(row0 + r) * W + w] = word;
-}
-
-__device__ inline int wave_sum(int v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // One wave per row of the chunk: deg[row] = number of set bits of the row.

@@ -19,6 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "ensemble_common.h"
 #include "str2str_hip.h"
 
 namespace {
@@ -178,14 +179,8 @@ int launch_score(const float* b, int n_b, int L, int n_a, const Lists& lists, do
     refs = refs < 1 ? 1 : refs > MAX_REFS_PER_WG ? MAX_REFS_PER_WG : refs;
     const long long blocks = tiles * (((long long)n_a + refs - 1) / refs);
     const size_t lds = (size_t)TB * L * 12 + WAVES * TB * 4 + (PER_RES ? (size_t)TB * L * 4 : 0);
-    if (lds > 64 * 1024) {   // above the default limit of dynamic LDS
-        const hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&lddt_score_kernel<TB, PER_RES>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (rc != hipSuccess) return (int)rc;
-    }
-    hipLaunchKernelGGL((lddt_score_kernel<TB, PER_RES>), dim3((unsigned)blocks), dim3(THREADS), lds, st, b, n_b, L, n_a, (int)refs, lists, lddt,
-                       per_res);
-    return (int)hipGetLastError();
+    return ensemble::launch_dynamic_lds(lddt_score_kernel<TB, PER_RES>, dim3((unsigned)blocks), dim3(THREADS), lds, st, b, n_b, L, n_a, (int)refs,
+                                        lists, lddt, per_res);
 }
 
 template <bool PER_RES>

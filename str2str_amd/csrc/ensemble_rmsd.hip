@@ -18,19 +18,16 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "ensemble_common.h"
 #include "kabsch_f64.h"
 #include "str2str_hip.h"
 
 namespace {
 
 using namespace kabsch;
+using ensemble::wave_sum;
 
 typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // Prepass, one wave per structure slot (slots n .. 16 ceil(n/16) - 1 and residues L .. Lp - 1 are zero padding): weighted centroid, G, and
 // sqrt(w_i) (x_i - x-bar) as float64 in blocks of 16 structures, out[(blk * Lp + i) * 48 + 16 c + s].  The SAME scaled coordinates serve
@@ -193,10 +190,7 @@ extern "C" int s2s_ca_rmsd_matrix(const float* a, int n_a, const float* b, int n
     const bool whole = a == b && n_a == n_b;
     const long long need = 2 + region_doubles(n_b, Lp) + (whole ? 0 : region_doubles(n_a, Lp));
     if (workspace_doubles < need) return (int)hipErrorInvalidValue;
-    // a inside b's storage on a structure boundary = a row chunk of the self matrix
-    long long row0 = -1;
-    const long long stride = 3ll * n_res;
-    if (a >= b && a - b < stride * n_b && (a - b) % stride == 0 && (a - b) / stride + n_a <= n_b) row0 = (a - b) / stride;
+    const long long row0 = ensemble::self_row0(a, b, n_a, n_b, n_res);
     hipStream_t st = (hipStream_t)stream;
     double* gb = workspace + 2;
     double* cb = gb + nbb * 16;

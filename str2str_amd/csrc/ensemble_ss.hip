@@ -19,6 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "ensemble_common.h"
 #include "str2str_hip.h"
 
 namespace {
@@ -248,14 +249,7 @@ __global__ void __launch_bounds__(THREADS) ss_kernel(int L, Params p) {
 
 template <int THREADS>
 int launch(int n, int L, const Params& p, hipStream_t st) {
-    const size_t lds = lds_bytes(L);
-    if (lds > 64 * 1024) {   // above the default limit of dynamic LDS
-        const hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&ss_kernel<THREADS>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (rc != hipSuccess) return (int)rc;
-    }
-    hipLaunchKernelGGL(ss_kernel<THREADS>, dim3((unsigned)n), dim3(THREADS), lds, st, L, p);
-    return (int)hipGetLastError();
+    return ensemble::launch_dynamic_lds(ss_kernel<THREADS>, dim3((unsigned)n), dim3(THREADS), lds_bytes(L), st, L, p);
 }
 
 }  // namespace

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "ensemble_common.h"
 #include "kabsch_f64.h"
 #include "str2str_hip.h"
 
@@ -209,14 +210,8 @@ int launch(const float* a, int n_a, const float* b, int n_b, int L, double d0, l
     if (seeds.n > MAX_SEEDS) return (int)hipErrorInvalidValue;
     if (!(d0 > 0.0)) d0 = L > 15 ? fmax(0.5, 1.24 * cbrt((double)L - 15.0) - 1.8) : 0.5;
     const size_t lds = ((size_t)L * 3 * SLOTS + SLOTS * 3) * sizeof(double);
-    if (lds > 64 * 1024) {   // above the default limit of dynamic LDS
-        const hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&tm_pairs_kernel<XFORM>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (rc != hipSuccess) return (int)rc;
-    }
-    hipLaunchKernelGGL(tm_pairs_kernel<XFORM>, dim3((unsigned)ta, (unsigned)tb), dim3(256), lds, st, a, n_a, b, n_b, L, seeds,
-                       1.0 / (d0 * d0), row0, mirror, tm, xform);
-    return (int)hipGetLastError();
+    return ensemble::launch_dynamic_lds(tm_pairs_kernel<XFORM>, dim3((unsigned)ta, (unsigned)tb), dim3(256), lds, st, a, n_a, b, n_b, L, seeds,
+                                        1.0 / (d0 * d0), row0, mirror, tm, xform);
 }
 
 }  // namespace
@@ -224,11 +219,7 @@ int launch(const float* a, int n_a, const float* b, int n_b, int L, double d0, l
 extern "C" int s2s_ca_tm_matrix(const float* a, int n_a, const float* b, int n_b, int n_res, double d0, double* tm, void* stream) {
     if (!a || !b || !tm || n_a < 1 || n_b < 1 || n_res < 1) return (int)hipErrorInvalidValue;
     const bool whole = a == b && n_a == n_b;
-    // a inside b's storage on a structure boundary = a row chunk of the self matrix
-    long long row0 = -1;
-    const long long stride = 3ll * n_res;
-    if (a >= b && a - b < stride * n_b && (a - b) % stride == 0 && (a - b) / stride + n_a <= n_b) row0 = (a - b) / stride;
-    return launch<false>(a, n_a, b, n_b, n_res, d0, row0, whole ? 1 : 0, tm, nullptr, (hipStream_t)stream);
+    return launch<false>(a, n_a, b, n_b, n_res, d0, ensemble::self_row0(a, b, n_a, n_b, n_res), whole ? 1 : 0, tm, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int s2s_ca_tm_superpose(const float* mobile, int n_mobile, const float* target, int n_res, double d0, double* tm,

@@ -19,9 +19,12 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "ensemble_common.h"
 #include "str2str_hip.h"
 
 namespace {
+
+using ensemble::wave_sum;
 
 constexpr int MAX_RES = S2S_VIOL_MAX_RES;
 constexpr int THREADS_SHORT = 512, THREADS_LONG = 1024, SHORT_RES = 256;   // chains up to SHORT_RES: three workgroups share a CU
@@ -61,11 +64,6 @@ __device__ double block_sum(double v, double* red, int lane, int wave) {
     for (int w = 0; w < WAVES; ++w) t += red[w];
     __syncthreads();
     return t;
-}
-
-__device__ inline int wave_sum(int v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // The C-N peptide bond of two residues numbered n and n + 1 is no clash: its slots (`a` of residue i, `b` of residue j), -1 if there is none.
@@ -301,14 +299,7 @@ __global__ void __launch_bounds__(THREADS) violations_kernel(int L, Params p) {
 
 template <int THREADS>
 int launch(int n, int L, const Params& p, hipStream_t st) {
-    const size_t lds = lds_bytes(L, THREADS);
-    if (lds > 64 * 1024) {   // above the default limit of dynamic LDS
-        const hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&violations_kernel<THREADS>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (rc != hipSuccess) return (int)rc;
-    }
-    hipLaunchKernelGGL(violations_kernel<THREADS>, dim3((unsigned)n), dim3(THREADS), lds, st, L, p);
-    return (int)hipGetLastError();
+    return ensemble::launch_dynamic_lds(violations_kernel<THREADS>, dim3((unsigned)n), dim3(THREADS), lds_bytes(L, THREADS), st, L, p);
 }
 
 }  // namespace

@@ -29,7 +29,7 @@ eight states from the backbone hydrogen bonds and ``backbone_torsions`` gives ph
 from __future__ import annotations
 
 import math
-from typing import NamedTuple
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -179,8 +179,75 @@ def js_tica(ca_coords_dict, ref_key="target", n_bins=50, lagtime=20, return_tic=
     return results
 
 
+# ---- pair scores: RMSD, TM-score and lDDT as one family ------------------------------------------------------------------------------
+COVERAGE_CHUNK_PAIRS = 1 << 24   # pairs per launch of a coverage or cluster walk: 128 MiB of float64 scores at a time, whatever the ensembles' sizes
+
+
+class PairScore(NamedTuple):
+    """A score of one structure against another, described for the ensemble summaries every such score gets (``_diversity``,
+    ``_coverage``, ``_cluster``)."""
+    matrix: Callable          # (a, b=None, **kwargs) -> device float64 [Ra, Rb]: ops.ca_rmsd_matrix, ops.ca_tm_matrix, ops.ca_lddt_matrix
+    higher_is_better: bool
+    self_value: float         # of a structure against itself
+    symmetric: bool           # matrix(a)[i, j] is matrix(a)[j, i] bit for bit; otherwise the structure of the row is the reference of a pair
+    reference_rows: bool      # a coverage walk takes its rows from the reference ensemble (the lDDT references), not from the samples
+
+
+RMSD = PairScore(ops.ca_rmsd_matrix, higher_is_better=False, self_value=0.0, symmetric=True, reference_rows=False)
+TM = PairScore(ops.ca_tm_matrix, higher_is_better=True, self_value=1.0, symmetric=True, reference_rows=False)
+LDDT = PairScore(ops.ca_lddt_matrix, higher_is_better=True, self_value=1.0, symmetric=False, reference_rows=True)
+
+
+def _chunk_rows(n: int, chunk_pairs) -> int:
+    return ops.rmsd_row_chunk(n, COVERAGE_CHUNK_PAIRS if chunk_pairs is None else chunk_pairs)
+
+
+def _diversity(score: PairScore, ca_coords_dict, **kwargs):
+    """Per ensemble the mean score over its pairs i != j (``self_value`` for a single structure)."""
+    out = {}
+    for k, v in ca_coords_dict.items():
+        x = _dev(v)
+        n = x.shape[0]
+        if n <= 1:
+            out[k] = score.self_value
+        elif score.symmetric:   # (the diagonal is ``self_value`` up to rounding, which the upper-triangle sum leaves out)
+            out[k] = np.around(float(torch.triu(score.matrix(x, None, **kwargs), diagonal=1).sum()) / (n * (n - 1) / 2), decimals=4)
+        else:                   # (the diagonal is exactly ``self_value``)
+            out[k] = np.around((float(score.matrix(x, None, **kwargs).sum()) - n * score.self_value) / (n * (n - 1)), decimals=4)
+    return out
+
+
+def _coverage_extrema(score: PairScore, samples: torch.Tensor, ref: torch.Tensor, chunk_pairs=None, **kwargs):
+    """(per reference frame: its best score with any sample, per sample: its best score with any reference frame), device float64, over
+    row chunks of the matrix with running extrema: the matrix itself is never held, and an extremum is exact whatever the chunking."""
+    row_set, col_set = (ref, samples) if score.reference_rows else (samples, ref)
+    best, running, start = ("max", torch.maximum, -float("inf")) if score.higher_is_better else ("min", torch.minimum, float("inf"))
+    rows = _chunk_rows(col_set.shape[0], chunk_pairs)
+    per_col = torch.full((col_set.shape[0],), start, dtype=torch.float64, device=ref.device)
+    per_row = torch.empty(row_set.shape[0], dtype=torch.float64, device=ref.device)
+    for r0 in range(0, row_set.shape[0], rows):
+        m = score.matrix(row_set[r0:r0 + rows], col_set, **kwargs)
+        per_row[r0:r0 + rows] = getattr(m, best)(dim=1).values
+        per_col = running(per_col, getattr(m, best)(dim=0).values)
+    return (per_row, per_col) if score.reference_rows else (per_col, per_row)
+
+
+def _coverage(score: PairScore, ca_coords_dict, ref_key, chunk_pairs=None, **kwargs):
+    """-> (recall, precision): per ensemble the mean over the reference frames of the best score with any of its samples, and the mean
+    over its samples of the best score with any reference frame; the reference's own entries are ``self_value``."""
+    ref = _dev(ca_coords_dict[ref_key])
+    recall, precision = {}, {}
+    for k, v in ca_coords_dict.items():
+        if k == ref_key:
+            continue
+        per_ref, per_sample = _coverage_extrema(score, _dev(v), ref, chunk_pairs, **kwargs)
+        recall[k] = np.around(float(per_ref.mean()), decimals=4)
+        precision[k] = np.around(float(per_sample.mean()), decimals=4)
+    recall[ref_key] = precision[ref_key] = score.self_value
+    return recall, precision
+
+
 # ---- minimum RMSD under optimal superposition (csrc/ensemble_rmsd.hip) -----------------------------------------------------------
-COVERAGE_CHUNK_PAIRS = 1 << 24   # pairs per launch of coverage_rmsd: 128 MiB of float64 RMSDs at a time, whatever the ensembles' sizes
 
 
 def pairwise_rmsd(a, b=None, weights=None) -> np.ndarray:
@@ -191,41 +258,13 @@ def pairwise_rmsd(a, b=None, weights=None) -> np.ndarray:
 
 def diversity_rmsd(ca_coords_dict, weights=None):
     """Ensemble diversity: the mean RMSD over the pairs i < j of each ensemble (0.0 for a single structure)."""
-    out = {}
-    for k, v in ca_coords_dict.items():
-        x = _dev(v)
-        n = x.shape[0]
-        # (the matrix is symmetric with a diagonal of rounding size, which the upper-triangle sum leaves out)
-        out[k] = np.around(float(torch.triu(ops.ca_rmsd_matrix(x, None, weights), diagonal=1).sum()) / (n * (n - 1) / 2), decimals=4) if n > 1 else 0.0
-    return out
-
-
-def _coverage_minima(samples: torch.Tensor, ref: torch.Tensor, weights=None, chunk_pairs=None):
-    """(per reference frame: min RMSD to any sample, per sample: min RMSD to any reference frame), device float64, over row chunks of
-    the sample x reference matrix with running minima: the matrix itself is never held."""
-    rows = ops.rmsd_row_chunk(ref.shape[0], COVERAGE_CHUNK_PAIRS if chunk_pairs is None else chunk_pairs)
-    per_ref = torch.full((ref.shape[0],), float("inf"), dtype=torch.float64, device=ref.device)
-    per_sample = torch.empty(samples.shape[0], dtype=torch.float64, device=ref.device)
-    for r0 in range(0, samples.shape[0], rows):
-        m = ops.ca_rmsd_matrix(samples[r0:r0 + rows], ref, weights)
-        per_sample[r0:r0 + rows] = m.min(dim=1).values
-        per_ref = torch.minimum(per_ref, m.min(dim=0).values)
-    return per_ref, per_sample
+    return _diversity(RMSD, ca_coords_dict, weights=weights)
 
 
 def coverage_rmsd(ca_coords_dict, ref_key="target", weights=None, chunk_pairs=None):
     """How well each ensemble covers the reference ensemble -> (recall, precision): recall[k] = mean over reference frames of the
     minimum RMSD to any sample of k, precision[k] = mean over samples of k of the minimum RMSD to any reference frame."""
-    ref = _dev(ca_coords_dict[ref_key])
-    recall, precision = {}, {}
-    for k, v in ca_coords_dict.items():
-        if k == ref_key:
-            continue
-        per_ref, per_sample = _coverage_minima(_dev(v), ref, weights, chunk_pairs)
-        recall[k] = np.around(float(per_ref.mean()), decimals=4)
-        precision[k] = np.around(float(per_sample.mean()), decimals=4)
-    recall[ref_key] = precision[ref_key] = 0.0
-    return recall, precision
+    return _coverage(RMSD, ca_coords_dict, ref_key, chunk_pairs, weights=weights)
 
 
 def superpose(coords, target, weights=None):
@@ -263,41 +302,14 @@ def pairwise_tm(a, b=None, d0=None) -> np.ndarray:
 def diversity_tm(ca_coords_dict):
     """Ensemble diversity: the mean TM-score over the pairs i < j of each ensemble (1.0 for a single structure).  LOWER means more
     diverse, the opposite sense of ``diversity_rmsd``."""
-    out = {}
-    for k, v in ca_coords_dict.items():
-        x = _dev(v)
-        n = x.shape[0]
-        out[k] = np.around(float(torch.triu(ops.ca_tm_matrix(x), diagonal=1).sum()) / (n * (n - 1) / 2), decimals=4) if n > 1 else 1.0
-    return out
-
-
-def _coverage_maxima(samples: torch.Tensor, ref: torch.Tensor, chunk_pairs=None):
-    """(per reference frame: max TM to any sample, per sample: max TM to any reference frame), device float64, over row chunks of the
-    sample x reference matrix with running maxima: the matrix itself is never held."""
-    rows = ops.rmsd_row_chunk(ref.shape[0], COVERAGE_CHUNK_PAIRS if chunk_pairs is None else chunk_pairs)
-    per_ref = torch.full((ref.shape[0],), -float("inf"), dtype=torch.float64, device=ref.device)
-    per_sample = torch.empty(samples.shape[0], dtype=torch.float64, device=ref.device)
-    for r0 in range(0, samples.shape[0], rows):
-        m = ops.ca_tm_matrix(samples[r0:r0 + rows], ref)
-        per_sample[r0:r0 + rows] = m.max(dim=1).values
-        per_ref = torch.maximum(per_ref, m.max(dim=0).values)
-    return per_ref, per_sample
+    return _diversity(TM, ca_coords_dict)
 
 
 def coverage_tm(ca_coords_dict, ref_key="target", chunk_pairs=None):
     """How well each ensemble covers the reference ensemble -> (recall, precision): recall[k] = mean over reference frames of the
     maximum TM-score to any sample of k, precision[k] = mean over samples of k of the maximum TM-score to any reference frame
     (higher is better; the reference's own entries are 1.0)."""
-    ref = _dev(ca_coords_dict[ref_key])
-    recall, precision = {}, {}
-    for k, v in ca_coords_dict.items():
-        if k == ref_key:
-            continue
-        per_ref, per_sample = _coverage_maxima(_dev(v), ref, chunk_pairs)
-        recall[k] = np.around(float(per_ref.mean()), decimals=4)
-        precision[k] = np.around(float(per_sample.mean()), decimals=4)
-    recall[ref_key] = precision[ref_key] = 1.0
-    return recall, precision
+    return _coverage(TM, ca_coords_dict, ref_key, chunk_pairs)
 
 
 def tm_superpose(coords, target):
@@ -326,42 +338,14 @@ def lddt(coords, target, per_residue=False) -> np.ndarray:
 def diversity_lddt(ca_coords_dict):
     """Ensemble diversity: the mean lDDT over the ordered pairs i != j of each ensemble (1.0 for a single structure).  LOWER means more
     diverse, the sense of ``diversity_tm``."""
-    out = {}
-    for k, v in ca_coords_dict.items():
-        x = _dev(v)
-        n = x.shape[0]
-        # (the diagonal is exactly 1.0)
-        out[k] = np.around((float(ops.ca_lddt_matrix(x).sum()) - n) / (n * (n - 1)), decimals=4) if n > 1 else 1.0
-    return out
-
-
-def _coverage_lddt_maxima(ref: torch.Tensor, samples: torch.Tensor, chunk_pairs=None):
-    """(per reference frame: max lDDT of any sample in its environment, per sample: max lDDT in the environment of any reference frame),
-    device float64, over row chunks of the reference x sample matrix with running maxima, as ``_coverage_maxima``."""
-    rows = ops.rmsd_row_chunk(samples.shape[0], COVERAGE_CHUNK_PAIRS if chunk_pairs is None else chunk_pairs)
-    per_ref = torch.empty(ref.shape[0], dtype=torch.float64, device=ref.device)
-    per_sample = torch.full((samples.shape[0],), -float("inf"), dtype=torch.float64, device=ref.device)
-    for r0 in range(0, ref.shape[0], rows):
-        m = ops.ca_lddt_matrix(ref[r0:r0 + rows], samples)
-        per_ref[r0:r0 + rows] = m.max(dim=1).values
-        per_sample = torch.maximum(per_sample, m.max(dim=0).values)
-    return per_ref, per_sample
+    return _diversity(LDDT, ca_coords_dict)
 
 
 def coverage_lddt(ca_coords_dict, ref_key="target", chunk_pairs=None):
     """How well each ensemble covers the reference ensemble -> (recall, precision), the reference ensemble's frames being the lDDT
     references: recall[k] = mean over reference frames of the best lDDT any sample of k reaches in that frame's environment, precision[k]
     = mean over samples of k of its best lDDT in any reference frame's environment (higher is better; the reference's own entries are 1.0)."""
-    ref = _dev(ca_coords_dict[ref_key])
-    recall, precision = {}, {}
-    for k, v in ca_coords_dict.items():
-        if k == ref_key:
-            continue
-        per_ref, per_sample = _coverage_lddt_maxima(ref, _dev(v), chunk_pairs)
-        recall[k] = np.around(float(per_ref.mean()), decimals=4)
-        precision[k] = np.around(float(per_sample.mean()), decimals=4)
-    recall[ref_key] = precision[ref_key] = 1.0
-    return recall, precision
+    return _coverage(LDDT, ca_coords_dict, ref_key, chunk_pairs)
 
 
 # ---- backbone violations: inside each structure (csrc/ensemble_violations.hip; the definition of src/models/loss.py:714-1017, 1237-1314) ----
@@ -409,10 +393,7 @@ def backbone_violations(atoms, aatype=None, residue_index=None, tolerance_factor
     defaults."""
     x = _backbone_dev(atoms)
     L = x.shape[1]
-    aatype = np.zeros(L, dtype=np.int64) if aatype is None else np.asarray(aatype.cpu() if torch.is_tensor(aatype) else aatype).reshape(-1)
-    residue_index = np.arange(L) if residue_index is None else np.asarray(residue_index.cpu() if torch.is_tensor(residue_index) else residue_index).reshape(-1)
-    if aatype.shape != (L,) or residue_index.shape != (L,):
-        raise ValueError(f"backbone_violations: aatype {aatype.shape} and residue_index {residue_index.shape} for {L} residues")
+    aatype, residue_index = _sequence_arrays("backbone_violations", L, aatype, residue_index)
     exists = np.ones((L, 5), dtype=np.uint8)
     exists[aatype == GLY, 4] = 0
     losses, fractions, per_res, bond_mask, clash_mask, n_pairs = ops.backbone_violations(x, exists, aatype, residue_index, tolerance_factor,
@@ -422,22 +403,28 @@ def backbone_violations(atoms, aatype=None, residue_index=None, tolerance_factor
                               clash_mask.cpu().numpy().astype(bool), n_pairs.cpu().numpy())
 
 
+def validity_of_violations(res: BackboneViolations):
+    """-> (the share of structures without a violated connection, the share without a clash) of one ensemble's violations."""
+    return (np.around(1.0 - float(res.bond_mask.any(axis=1).mean()), decimals=4),
+            np.around(1.0 - float((res.n_clash_pairs > 0).mean()), decimals=4))
+
+
+def rate_of_violations(res: BackboneViolations):
+    """-> the mean over the structures of ``violations_per_residue`` of one ensemble's violations."""
+    return np.around(float(res.violations_per_residue.mean()), decimals=4)
+
+
 def backbone_validity(atoms_dict, aatype=None, residue_index=None):
     """The full-backbone companions of ``validity`` / ``bonding_validity`` -> (val_bb_bond, val_bb_clash): per ensemble the share of
     structures without a violated connection, and without a clash."""
-    bond, clash = {}, {}
-    for k, v in atoms_dict.items():
-        res = backbone_violations(v, aatype, residue_index)
-        bond[k] = np.around(1.0 - float(res.bond_mask.any(axis=1).mean()), decimals=4)
-        clash[k] = np.around(1.0 - float((res.n_clash_pairs > 0).mean()), decimals=4)
-    return bond, clash
+    shares = {k: validity_of_violations(backbone_violations(v, aatype, residue_index)) for k, v in atoms_dict.items()}
+    return {k: v[0] for k, v in shares.items()}, {k: v[1] for k, v in shares.items()}
 
 
 def violation_rate(atoms_dict, aatype=None, residue_index=None):
     """Per ensemble the mean over its structures of ``violations_per_residue``: the fraction of residues at a violated connection or with
     a clashing atom."""
-    return {k: np.around(float(backbone_violations(v, aatype, residue_index).violations_per_residue.mean()), decimals=4)
-            for k, v in atoms_dict.items()}
+    return {k: rate_of_violations(backbone_violations(v, aatype, residue_index)) for k, v in atoms_dict.items()}
 
 
 # ---- secondary structure and backbone torsions (csrc/ensemble_ss.hip; Kabsch & Sander 1983, include/str2str_hip.h has the definition) ----
@@ -556,8 +543,17 @@ def _cluster_chunks(n: int, rows: int, chunk, cutoff: float, at_least: bool) -> 
     return ClusterResult(*(t.cpu().numpy() for t in ops.cluster_gromos(adj, deg)))
 
 
-def _chunk_rows(n: int, chunk_pairs) -> int:
-    return ops.rmsd_row_chunk(n, COVERAGE_CHUNK_PAIRS if chunk_pairs is None else chunk_pairs)
+def _cluster(score: PairScore, coords, cutoff: float, chunk_pairs=None, **kwargs) -> ClusterResult:
+    """GROMOS clusters of an ensemble under ``score`` at an already checked ``cutoff``; a directed score counts as the worse of its two
+    directions (rows r0 .. r1 of the matrix and of its transpose come from two launches)."""
+    x = _dev(coords)
+    n = x.shape[0]
+    if score.symmetric:
+        chunk = lambda r0, r1: score.matrix(x[r0:r1], x, **kwargs)   # noqa: E731
+    else:
+        worse = torch.minimum if score.higher_is_better else torch.maximum
+        chunk = lambda r0, r1: worse(score.matrix(x[r0:r1], x, **kwargs), score.matrix(x, x[r0:r1], **kwargs).T)   # noqa: E731
+    return _cluster_chunks(n, _chunk_rows(n, chunk_pairs), chunk, cutoff, score.higher_is_better)
 
 
 def cluster_rmsd(coords, cutoff: float, weights=None, chunk_pairs=None) -> ClusterResult:
@@ -568,9 +564,7 @@ def cluster_rmsd(coords, cutoff: float, weights=None, chunk_pairs=None) -> Clust
     cutoff = float(cutoff)
     if not 0.0 < cutoff < math.inf:
         raise ValueError(f"cluster_rmsd: cutoff must be a positive finite RMSD in Angstrom, got {cutoff}")
-    x = _dev(coords)
-    n = x.shape[0]
-    return _cluster_chunks(n, _chunk_rows(n, chunk_pairs), lambda r0, r1: ops.ca_rmsd_matrix(x[r0:r1], x, weights), cutoff, False)
+    return _cluster(RMSD, coords, cutoff, chunk_pairs, weights=weights)
 
 
 def cluster_tm(coords, cutoff: float, d0=None) -> ClusterResult:
@@ -578,9 +572,7 @@ def cluster_tm(coords, cutoff: float, d0=None) -> ClusterResult:
     cutoff = float(cutoff)
     if not 0.0 < cutoff <= 1.0:
         raise ValueError(f"cluster_tm: cutoff must be a TM-score in (0, 1], got {cutoff}")
-    x = _dev(coords)
-    n = x.shape[0]
-    return _cluster_chunks(n, _chunk_rows(n, None), lambda r0, r1: ops.ca_tm_matrix(x[r0:r1], x, d0), cutoff, True)
+    return _cluster(TM, coords, cutoff, d0=d0)
 
 
 def cluster_lddt(coords, cutoff: float) -> ClusterResult:
@@ -590,10 +582,7 @@ def cluster_lddt(coords, cutoff: float) -> ClusterResult:
     cutoff = float(cutoff)
     if not 0.0 < cutoff <= 1.0:
         raise ValueError(f"cluster_lddt: cutoff must be an lDDT in (0, 1], got {cutoff}")
-    x = _dev(coords)
-    n = x.shape[0]
-    return _cluster_chunks(n, _chunk_rows(n, None), lambda r0, r1: torch.minimum(ops.ca_lddt_matrix(x[r0:r1], x), ops.ca_lddt_matrix(x, x[r0:r1]).T),
-                           cutoff, True)
+    return _cluster(LDDT, coords, cutoff)
 
 
 def cluster_from_matrix(values, cutoff: float, at_least: bool = False) -> ClusterResult:

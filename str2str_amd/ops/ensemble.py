@@ -66,6 +66,60 @@ def ca_pwd_js(ref_ca: torch.Tensor, pred_ca: torch.Tensor, offset: int = 3, n_bi
     return out
 
 
+def _ensemble_pair(fn: str, a, b, on_device: bool = True):
+    """The two ensembles of a pair matrix of ``fn``, a [Ra, L, 3] and b [Rb, L, 3] (None: ``a`` itself), checked -> (a, b, Ra, L, Rb).
+    ``on_device=False`` leaves the device / dtype / contiguity check to the caller, who has something to check before it."""
+    b = a if b is None else b
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
+        raise HipLibraryError(f"{fn}: expected tensors, got {type(a).__name__} and {type(b).__name__}")
+    if a.ndim != 3 or b.ndim != 3 or a.shape[2] != 3 or b.shape[1:] != a.shape[1:] or a.shape[0] < 1 or b.shape[0] < 1 or a.shape[1] < 1:
+        raise HipLibraryError(f"{fn}: coordinates {tuple(a.shape)} and {tuple(b.shape)}")
+    if on_device:
+        _req(a, name="a"); _req(b, name="b")
+    return a, b, a.shape[0], a.shape[1], b.shape[0]
+
+
+def _mobile_target(fn: str, mobile, target, what: str = "mobile", on_device: bool = True):
+    """``mobile`` [R, L, 3] (named ``what`` in the messages of ``fn``) onto ``target`` [L, 3], checked -> (R, L)."""
+    if not (isinstance(mobile, torch.Tensor) and isinstance(target, torch.Tensor)):
+        raise HipLibraryError(f"{fn}: expected tensors, got {type(mobile).__name__} and {type(target).__name__}")
+    if mobile.ndim != 3 or mobile.shape[2] != 3 or target.shape != mobile.shape[1:] or mobile.shape[0] < 1 or mobile.shape[1] < 1:
+        raise HipLibraryError(f"{fn}: {what} {tuple(mobile.shape)}, target {tuple(target.shape)}")
+    if on_device:
+        _req(mobile, name=what); _req(target, name="target")
+    return mobile.shape[0], mobile.shape[1]
+
+
+def _backbone_ensemble(fn: str, atoms, max_res: int, max_structures, launch_structures: int) -> int:
+    """``atoms`` [R, L, 5, 3] of at most ``max_res`` residues and ``max_structures`` (None or an integer >= 1) of ``fn``, checked but for
+    the device -> the structures per launch."""
+    if not isinstance(atoms, torch.Tensor):
+        raise HipLibraryError(f"{fn}: expected a tensor, got {type(atoms).__name__}")
+    if atoms.ndim != 4 or atoms.shape[2:] != (5, 3) or atoms.shape[0] < 1 or atoms.shape[1] < 1:
+        raise HipLibraryError(f"{fn}: atoms {tuple(atoms.shape)}, expected [R, L, 5, 3]")
+    if atoms.shape[1] > max_res:
+        raise HipLibraryError(f"{fn}: at most {max_res} residues, got {atoms.shape[1]}")
+    if max_structures is not None and (isinstance(max_structures, bool) or int(max_structures) != max_structures or max_structures < 1):
+        raise HipLibraryError(f"{fn}: max_structures must be an integer >= 1, got {max_structures}")
+    return launch_structures if max_structures is None else min(int(max_structures), launch_structures)
+
+
+def _pair_out(fn: str, out, n_a: int, n_b: int, device) -> torch.Tensor:
+    """The [n_a, n_b] float64 result of a pair matrix of ``fn``: the caller's ``out``, checked, or a new tensor."""
+    if out is None:
+        return torch.empty(n_a, n_b, dtype=torch.float64, device=device)
+    if _req(out, torch.float64, "out").shape != (n_a, n_b):
+        raise HipLibraryError(f"{fn}: out {tuple(out.shape)} for {n_a} x {n_b} pairs")
+    return out
+
+
+def _row_chunks(n: int, rows: int, *tensors):
+    """Chunks of at most ``rows`` of the ``n`` leading rows of every tensor -> (rows of the chunk, a pointer to the chunk of each)."""
+    for r0 in range(0, n, rows):
+        m = min(rows, n - r0)
+        yield (m, *(_p(t[r0:r0 + m]) for t in tensors))
+
+
 def _rmsd_weights(weights, L: int, device):
     if weights is None:
         return None
@@ -87,32 +141,24 @@ def ca_rmsd_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, weights=No
     -> [Ra, Rb] fp64.  ``b=None``: the self matrix of ``a`` (exactly symmetric).  ``weights``: per-residue [L], >= 0.  ``max_pairs``
     bounds the pairs (and with them the scratch) of one launch: rows are chunked, the result is bit for bit the same for any value.
     The caller bounds Ra x Rb (the output); metrics.coverage_rmsd shows the chunked use that never holds the whole matrix."""
-    lib = load_library()
-    _req(a, name="a")
-    b = a if b is None else _req(b, name="b")
-    if a.ndim != 3 or b.ndim != 3 or a.shape[2] != 3 or b.shape[1:] != a.shape[1:] or a.shape[0] < 1 or b.shape[0] < 1 or a.shape[1] < 1:
-        raise HipLibraryError(f"ca_rmsd_matrix: coordinates {tuple(a.shape)} and {tuple(b.shape)}")
-    (n_a, L), n_b = a.shape[:2], b.shape[0]
+    a, b, n_a, L, n_b = _ensemble_pair("ca_rmsd_matrix", a, b)
     w = _rmsd_weights(weights, L, a.device)
-    out = torch.empty(n_a, n_b, dtype=torch.float64, device=a.device) if out is None else out
+    out = _pair_out("ca_rmsd_matrix", out, n_a, n_b, a.device)
     rows = rmsd_row_chunk(n_b, max_pairs)
+    lib = load_library()
     region = lambda n: -(-n // 16) * 16 * (3 * (-(-L // 4) * 4) + 1)  # noqa: E731
     ws = torch.empty(2 + region(n_b) + region(min(rows, n_a)), dtype=torch.float64, device=a.device)
-    for r0 in range(0, n_a, rows):
-        n = min(rows, n_a - r0)
-        _check(lib.s2s_ca_rmsd_matrix(_p(a[r0:r0 + n]), n, _p(b), n_b, L, _p(w), _p(out[r0:r0 + n]), _p(ws), ws.numel(), _stream()), "s2s_ca_rmsd_matrix")
+    for n, pa, po in _row_chunks(n_a, rows, a, out):
+        _check(lib.s2s_ca_rmsd_matrix(pa, n, _p(b), n_b, L, _p(w), po, _p(ws), ws.numel(), _stream()), "s2s_ca_rmsd_matrix")
     return out
 
 
 def ca_superpose(mobile: torch.Tensor, target: torch.Tensor, weights=None):
     """mobile [R, L, 3] onto target [L, 3] (fp32 device tensors) -> (rmsd [R] fp64, xform [R, 12] fp64: row-major proper rotation, then
     translation; rotation @ x + translation maps mobile onto target)."""
-    lib = load_library()
-    _req(mobile, name="mobile"); _req(target, name="target")
-    if mobile.ndim != 3 or mobile.shape[2] != 3 or target.shape != mobile.shape[1:] or mobile.shape[0] < 1 or mobile.shape[1] < 1:
-        raise HipLibraryError(f"ca_superpose: mobile {tuple(mobile.shape)}, target {tuple(target.shape)}")
-    R, L = mobile.shape[:2]
+    R, L = _mobile_target("ca_superpose", mobile, target)
     w = _rmsd_weights(weights, L, mobile.device)
+    lib = load_library()
     rmsd = torch.empty(R, dtype=torch.float64, device=mobile.device)
     xform = torch.empty(R, 12, dtype=torch.float64, device=mobile.device)
     _check(lib.s2s_ca_superpose(_p(mobile), R, _p(target), L, _p(w), _p(rmsd), _p(xform), _stream()), "s2s_ca_superpose")
@@ -147,37 +193,21 @@ def ca_tm_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, d0: Optional
     distance scale in Angstrom, None = max(0.5, 1.24 cbrt(L - 15) - 1.8).  The superposition search is the fixed monotone reweighted
     Kabsch iteration of include/str2str_hip.h: a certified lower bound of the optimum, a heuristic like the TMscore program's.
     ``max_pairs`` bounds the pairs of one launch: rows are chunked, the result is bit for bit the same for any value."""
-    b = a if b is None else b
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
-        raise HipLibraryError(f"ca_tm_matrix: expected tensors, got {type(a).__name__} and {type(b).__name__}")
-    if a.ndim != 3 or b.ndim != 3 or a.shape[2] != 3 or b.shape[1:] != a.shape[1:] or a.shape[0] < 1 or b.shape[0] < 1 or a.shape[1] < 1:
-        raise HipLibraryError(f"ca_tm_matrix: coordinates {tuple(a.shape)} and {tuple(b.shape)}")
-    _req(a, name="a"); _req(b, name="b")
-    (n_a, L), n_b = a.shape[:2], b.shape[0]
+    a, b, n_a, L, n_b = _ensemble_pair("ca_tm_matrix", a, b)
     if L > TM_MAX_RES or n_b > TM_MAX_COLS:
         raise HipLibraryError(f"ca_tm_matrix: at most {TM_MAX_RES} residues and {TM_MAX_COLS} structures of b, got {L} and {n_b}")
     d0 = _tm_d0(d0)
-    if out is None:
-        out = torch.empty(n_a, n_b, dtype=torch.float64, device=a.device)
-    elif _req(out, torch.float64, "out").shape != (n_a, n_b):
-        raise HipLibraryError(f"ca_tm_matrix: out {tuple(out.shape)} for {n_a} x {n_b} pairs")
-    rows = rmsd_row_chunk(n_b, max_pairs)
+    out = _pair_out("ca_tm_matrix", out, n_a, n_b, a.device)
     lib = load_library()
-    for r0 in range(0, n_a, rows):
-        n = min(rows, n_a - r0)
-        _check(lib.s2s_ca_tm_matrix(_p(a[r0:r0 + n]), n, _p(b), n_b, L, d0, _p(out[r0:r0 + n]), _stream()), "s2s_ca_tm_matrix")
+    for n, pa, po in _row_chunks(n_a, rmsd_row_chunk(n_b, max_pairs), a, out):
+        _check(lib.s2s_ca_tm_matrix(pa, n, _p(b), n_b, L, d0, po, _stream()), "s2s_ca_tm_matrix")
     return out
 
 
 def ca_tm_superpose(mobile: torch.Tensor, target: torch.Tensor, d0: Optional[float] = None):
     """mobile [R, L, 3] onto target [L, 3] (fp32 device tensors) -> (tm [R] fp64: the ca_tm_matrix entries of the pairs, xform [R, 12]
     fp64 in ca_superpose's layout: the superposition that scored each TM; apply_xform consumes it)."""
-    if not (isinstance(mobile, torch.Tensor) and isinstance(target, torch.Tensor)):
-        raise HipLibraryError(f"ca_tm_superpose: expected tensors, got {type(mobile).__name__} and {type(target).__name__}")
-    if mobile.ndim != 3 or mobile.shape[2] != 3 or target.shape != mobile.shape[1:] or mobile.shape[0] < 1 or mobile.shape[1] < 1:
-        raise HipLibraryError(f"ca_tm_superpose: mobile {tuple(mobile.shape)}, target {tuple(target.shape)}")
-    _req(mobile, name="mobile"); _req(target, name="target")
-    R, L = mobile.shape[:2]
+    R, L = _mobile_target("ca_tm_superpose", mobile, target)
     if L > TM_MAX_RES:
         raise HipLibraryError(f"ca_tm_superpose: at most {TM_MAX_RES} residues, got {L}")
     d0 = _tm_d0(d0)
@@ -213,36 +243,22 @@ def ca_lddt_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, cutoff: fl
     against itself (the diagonal is exactly 1).  Rows of ``a`` are chunked so that the pair lists of one launch stay within
     LDDT_WORKSPACE_BYTES and the pairs within ``max_pairs``; every entry is one division of two integers, bit for bit the same for any
     chunking."""
-    b = a if b is None else b
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
-        raise HipLibraryError(f"ca_lddt_matrix: expected tensors, got {type(a).__name__} and {type(b).__name__}")
-    if a.ndim != 3 or b.ndim != 3 or a.shape[2] != 3 or b.shape[1:] != a.shape[1:] or a.shape[0] < 1 or b.shape[0] < 1 or a.shape[1] < 1:
-        raise HipLibraryError(f"ca_lddt_matrix: coordinates {tuple(a.shape)} and {tuple(b.shape)}")
-    (n_a, L), n_b = a.shape[:2], b.shape[0]
+    a, b, n_a, L, n_b = _ensemble_pair("ca_lddt_matrix", a, b, on_device=False)
     cutoff, min_seq_sep = _lddt_args("ca_lddt_matrix", L, cutoff, min_seq_sep)
     _req(a, name="a"); _req(b, name="b")
-    if out is None:
-        out = torch.empty(n_a, n_b, dtype=torch.float64, device=a.device)
-    elif _req(out, torch.float64, "out").shape != (n_a, n_b):
-        raise HipLibraryError(f"ca_lddt_matrix: out {tuple(out.shape)} for {n_a} x {n_b} pairs")
+    out = _pair_out("ca_lddt_matrix", out, n_a, n_b, a.device)
     rows = min(rmsd_row_chunk(n_b, max_pairs), max(1, LDDT_WORKSPACE_BYTES // lddt_workspace_bytes(1, L)), n_a)
     lib = load_library()
     ws = torch.empty(lddt_workspace_bytes(rows, L) // 8 + 1, dtype=torch.int64, device=a.device)
-    for r0 in range(0, n_a, rows):
-        n = min(rows, n_a - r0)
-        _check(lib.s2s_ca_lddt_matrix(_p(a[r0:r0 + n]), n, _p(b), n_b, L, cutoff, min_seq_sep, _p(out[r0:r0 + n]), _p(ws), ws.numel() * 8,
-                                      _stream()), "s2s_ca_lddt_matrix")
+    for n, pa, po in _row_chunks(n_a, rows, a, out):
+        _check(lib.s2s_ca_lddt_matrix(pa, n, _p(b), n_b, L, cutoff, min_seq_sep, po, _p(ws), ws.numel() * 8, _stream()), "s2s_ca_lddt_matrix")
     return out
 
 
 def ca_lddt_per_residue(model: torch.Tensor, target: torch.Tensor, cutoff: float = 15.0, min_seq_sep: int = 1):
     """model [R, L, 3] scored in the environment of the reference target [L, 3] (fp32 device tensors) -> (per_res [R, L] fp64: the lDDT of
     every residue, 1.0 where the target gives it no partner; total [R] fp64: bit for bit ``ca_lddt_matrix(target[None], model)[0]``)."""
-    if not (isinstance(model, torch.Tensor) and isinstance(target, torch.Tensor)):
-        raise HipLibraryError(f"ca_lddt_per_residue: expected tensors, got {type(model).__name__} and {type(target).__name__}")
-    if model.ndim != 3 or model.shape[2] != 3 or target.shape != model.shape[1:] or model.shape[0] < 1 or model.shape[1] < 1:
-        raise HipLibraryError(f"ca_lddt_per_residue: model {tuple(model.shape)}, target {tuple(target.shape)}")
-    R, L = model.shape[:2]
+    R, L = _mobile_target("ca_lddt_per_residue", model, target, "model", on_device=False)
     cutoff, min_seq_sep = _lddt_args("ca_lddt_per_residue", L, cutoff, min_seq_sep)
     _req(model, name="model"); _req(target, name="target")
     lib = load_library()
@@ -275,18 +291,11 @@ def backbone_violations(atoms: torch.Tensor, atom_exists, aatype, residue_index,
     connection, with a clashing atom, with either, extreme CA-CA steps; per_residue_loss [R, L] fp64; bond_mask [R, L] uint8;
     clash_atom_mask [R, L, 5] uint8; n_clash_pairs [R] int32).  ``max_structures`` bounds the structures of one launch; a structure's
     results are bit for bit the same for any value."""
-    if not isinstance(atoms, torch.Tensor):
-        raise HipLibraryError(f"backbone_violations: expected a tensor, got {type(atoms).__name__}")
-    if atoms.ndim != 4 or atoms.shape[2:] != (5, 3) or atoms.shape[0] < 1 or atoms.shape[1] < 1:
-        raise HipLibraryError(f"backbone_violations: atoms {tuple(atoms.shape)}, expected [R, L, 5, 3]")
+    rows = _backbone_ensemble("backbone_violations", atoms, VIOL_MAX_RES, max_structures, VIOL_MAX_STRUCTURES)
     R, L = atoms.shape[:2]
-    if L > VIOL_MAX_RES:
-        raise HipLibraryError(f"backbone_violations: at most {VIOL_MAX_RES} residues, got {L}")
     tolerance_factor, clash_tolerance = float(tolerance_factor), float(clash_tolerance)
     if not (abs(tolerance_factor) < float("inf") and abs(clash_tolerance) < float("inf")):
         raise HipLibraryError(f"backbone_violations: tolerances must be finite, got {tolerance_factor} and {clash_tolerance}")
-    if max_structures is not None and (isinstance(max_structures, bool) or int(max_structures) != max_structures or max_structures < 1):
-        raise HipLibraryError(f"backbone_violations: max_structures must be an integer >= 1, got {max_structures}")
     exists = _viol_small("atom_exists", atom_exists, (L, 5), torch.uint8)
     aatype = _viol_small("aatype", aatype, (L,), torch.int32)
     residue_index = _viol_small("residue_index", residue_index, (L,), torch.int32)
@@ -299,12 +308,9 @@ def backbone_violations(atoms: torch.Tensor, atom_exists, aatype, residue_index,
     bond_mask = torch.empty(R, L, dtype=torch.uint8, device=dev)
     clash_mask = torch.empty(R, L, 5, dtype=torch.uint8, device=dev)
     n_pairs = torch.empty(R, dtype=torch.int32, device=dev)
-    rows = VIOL_MAX_STRUCTURES if max_structures is None else min(int(max_structures), VIOL_MAX_STRUCTURES)
-    for r0 in range(0, R, rows):
-        n = min(rows, R - r0)
-        _check(lib.s2s_backbone_violations(_p(atoms[r0:r0 + n]), n, L, _p(exists), _p(aatype), _p(residue_index), tolerance_factor, clash_tolerance,
-                                           _p(losses[r0:r0 + n]), _p(fractions[r0:r0 + n]), _p(per_res[r0:r0 + n]), _p(bond_mask[r0:r0 + n]),
-                                           _p(clash_mask[r0:r0 + n]), _p(n_pairs[r0:r0 + n]), _stream()), "s2s_backbone_violations")
+    for n, p_atoms, *p_out in _row_chunks(R, rows, atoms, losses, fractions, per_res, bond_mask, clash_mask, n_pairs):
+        _check(lib.s2s_backbone_violations(p_atoms, n, L, _p(exists), _p(aatype), _p(residue_index), tolerance_factor, clash_tolerance, *p_out,
+                                           _stream()), "s2s_backbone_violations")
     return losses, fractions, per_res, bond_mask, clash_mask, n_pairs
 
 
@@ -316,15 +322,8 @@ def secondary_structure(atoms: torch.Tensor, aatype, residue_index, max_structur
     int32; hb_energy [R, L] fp64 and hb_partner [R, L] int32: the best acceptor of every N-H, 0.0 and -1 where there is none; torsions
     [R, L, 3] fp64: phi, psi, omega in radians, 0.0 where undefined).  ``max_structures`` bounds the structures of one launch; a
     structure's results are bit for bit the same for any value."""
-    if not isinstance(atoms, torch.Tensor):
-        raise HipLibraryError(f"secondary_structure: expected a tensor, got {type(atoms).__name__}")
-    if atoms.ndim != 4 or atoms.shape[2:] != (5, 3) or atoms.shape[0] < 1 or atoms.shape[1] < 1:
-        raise HipLibraryError(f"secondary_structure: atoms {tuple(atoms.shape)}, expected [R, L, 5, 3]")
+    rows = _backbone_ensemble("secondary_structure", atoms, SS_MAX_RES, max_structures, SS_MAX_STRUCTURES)
     R, L = atoms.shape[:2]
-    if L > SS_MAX_RES:
-        raise HipLibraryError(f"secondary_structure: at most {SS_MAX_RES} residues, got {L}")
-    if max_structures is not None and (isinstance(max_structures, bool) or int(max_structures) != max_structures or max_structures < 1):
-        raise HipLibraryError(f"secondary_structure: max_structures must be an integer >= 1, got {max_structures}")
     aatype = _viol_small("aatype", aatype, (L,), torch.int32, "secondary_structure")
     residue_index = _viol_small("residue_index", residue_index, (L,), torch.int32, "secondary_structure")
     _req(atoms, name="atoms")
@@ -336,12 +335,8 @@ def secondary_structure(atoms: torch.Tensor, aatype, residue_index, max_structur
     hb_energy = torch.empty(R, L, dtype=torch.float64, device=dev)
     hb_partner = torch.empty(R, L, dtype=torch.int32, device=dev)
     torsions = torch.empty(R, L, 3, dtype=torch.float64, device=dev)
-    rows = SS_MAX_STRUCTURES if max_structures is None else min(int(max_structures), SS_MAX_STRUCTURES)
-    for r0 in range(0, R, rows):
-        n = min(rows, R - r0)
-        _check(lib.s2s_secondary_structure(_p(atoms[r0:r0 + n]), n, L, _p(aatype), _p(residue_index), _p(ss[r0:r0 + n]), _p(n_hbonds[r0:r0 + n]),
-                                           _p(hb_energy[r0:r0 + n]), _p(hb_partner[r0:r0 + n]), _p(torsions[r0:r0 + n]), _stream()),
-               "s2s_secondary_structure")
+    for n, p_atoms, *p_out in _row_chunks(R, rows, atoms, ss, n_hbonds, hb_energy, hb_partner, torsions):
+        _check(lib.s2s_secondary_structure(p_atoms, n, L, _p(aatype), _p(residue_index), *p_out, _stream()), "s2s_secondary_structure")
     return ss, n_hbonds, hb_energy, hb_partner, torsions
 
 

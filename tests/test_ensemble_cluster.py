@@ -7,15 +7,13 @@ holds only while no pair sits at the cutoff: the test checks that precondition w
 """
 import functools
 import glob
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import ref_cluster as ref
-from conftest import ROOT
+from ensemble_cases import load_eval_entry
 
 pytestmark = pytest.mark.gpu
 
@@ -225,9 +223,7 @@ def test_eval_writes_cluster_centres_and_summary(tmp_path):
     from str2str_amd.common.pdb_utils import atom37_to_pdb, extract_backbone_coords
     from str2str_amd.metrics import metrics
 
-    spec = importlib.util.spec_from_file_location("s2s_eval_entry_cluster", os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
+    entry = load_eval_entry("s2s_eval_entry_cluster")
     x, _ = ref.planted_ensemble(seed=11, L=24, copies=(12, 7, 3, 1))
     target_dir = tmp_path / "targets"
     target_dir.mkdir()

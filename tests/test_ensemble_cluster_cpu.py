@@ -7,6 +7,7 @@ import pytest
 
 import ref_cluster as ref
 from conftest import GOLDEN, ROOT
+from ensemble_cases import load_eval_entry
 
 SIZES = (1, 2, 63, 64, 65, 130, 257)
 HIS = (3, 8, 40)
@@ -139,7 +140,6 @@ def test_abi_and_interface_are_declared():
 
 
 def test_cluster_cutoff_parses_from_the_command_line(monkeypatch):
-    import importlib.util
 
     from str2str_amd.utils import config as C
 
@@ -147,9 +147,7 @@ def test_cluster_cutoff_parses_from_the_command_line(monkeypatch):
     cfg = C.compose(os.path.join(ROOT, "configs"), "eval.yaml", ["+cluster_cutoff=2.5"])
     assert float(cfg.get("cluster_cutoff")) == 2.5
     assert C.compose(os.path.join(ROOT, "configs"), "eval.yaml", []).get("cluster_cutoff") is None
-    spec = importlib.util.spec_from_file_location("s2s_eval_entry_cluster_cpu", os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
+    entry = load_eval_entry("s2s_eval_entry_cluster_cpu")
     row = entry.cluster_summary([40, 25, 12, 3, 1, 1])
     assert row == {"n_clusters": 6, "top1_population": 0.4878, "top5_population": 0.9878, "n_singletons": 2}
     for bad in (0.0, -2.0, float("nan")):

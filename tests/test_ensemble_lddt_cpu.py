@@ -2,7 +2,6 @@
 margin that makes every device case a parity input, the C-ABI surface, the evaluation columns, and the argument checks that must fire
 before any device call."""
 import ctypes
-import importlib.util
 import os
 import re
 
@@ -13,6 +12,7 @@ import torch
 import lddt_cases as cases
 import ref_lddt as ref
 from conftest import ROOT, golden, record_margin
+from ensemble_cases import load_eval_entry
 from ref_tm64 import random_walk
 from str2str_amd.ops.ensemble import LDDT_MAX_RES, lddt_workspace_bytes   # (the binding's statement of the header's limits, held to it below)
 
@@ -129,13 +129,6 @@ def test_margin_sees_a_pair_on_the_edge():
 
 
 # ------------------------------------------------------------------------------------------------------------ header and binding
-def _eval_entry():
-    spec = importlib.util.spec_from_file_location("s2s_eval_entry_lddt_cpu", os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
-    return entry
-
-
 def test_header_declares_and_ops_exports_the_entry_points():
     from str2str_amd import ops
     from str2str_amd.ops import binding
@@ -232,7 +225,7 @@ def test_argument_checks_fire_before_the_device(monkeypatch):
 
 
 def test_metric_columns_accept_the_lddt_names():
-    entry = _eval_entry()
+    entry = load_eval_entry("s2s_eval_entry_lddt_cpu")
     five = ["val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"]
     assert entry.metric_columns(["lddt_precision", "div_lddt", "lddt_recall"]) == five + ["lddt_precision", "div_lddt", "lddt_recall"]
     assert entry.metric_columns(["div_tm", "div_lddt"]) == five + ["div_tm", "div_lddt"]

@@ -16,11 +16,11 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT, record_margin
+from conftest import GOLDEN, record_margin
+from ensemble_cases import load_eval_entry, to_device as _dev, write_models
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 U64 = 2.0 ** -53
 LENGTHS = (1, 2, 3, 7, 35, 80, 255, 256, 512)
 CROSS = ((1, 5), (17, 24), (100, 17), (5, 100))
@@ -146,10 +146,6 @@ def horn(h):
 
 
 # ------------------------------------------------------------------------------------------------------------------------ checks
-def _dev(x):
-    return None if x is None else torch.as_tensor(x).to(DEV)
-
-
 def check_matrix(tag, got, a, b, w):
     msd_ref, s_raw, g_sum = ref_msd_matrix(a, b, w)
     rmsd_ref = np.sqrt(np.maximum(msd_ref, 0.0))
@@ -292,7 +288,7 @@ def test_diversity_and_coverage_metrics():
 
     cross = ref_rmsd_matrix(pred, ref)                     # [100, 1000]
     for chunk in (None, 5000):
-        per_ref, per_sample = metrics._coverage_minima(_dev(pred), _dev(ref), chunk_pairs=chunk)
+        per_ref, per_sample = metrics._coverage_extrema(metrics.RMSD, _dev(pred), _dev(ref), chunk_pairs=chunk)
         assert np.abs(per_ref.cpu().numpy() - cross.min(0)).max() <= 1e-4 and np.abs(per_sample.cpu().numpy() - cross.min(1)).max() <= 1e-4
         recall, precision = metrics.coverage_rmsd({"target": ref, "pred": pred}, chunk_pairs=chunk)
         assert recall == {"pred": np.around(cross.min(0).mean(), decimals=4), "target": 0.0}
@@ -329,43 +325,25 @@ def test_rmsf():
     assert np.abs(np.sqrt(((aligned.astype(np.float64) - target) ** 2).sum(-1).mean(-1)) - rmsd).max() <= 1e-4
 
 
-def _write_models(path, template, coords):
-    """A multi-model PDB with the CA-bearing residues of ``template`` (one model) moved to ``coords`` [R, L, 3] (all atoms of a residue
-    shifted with its CA)."""
-    atoms = [ln for ln in open(template) if ln.startswith("ATOM")]
-    ca = np.array([[float(ln[30:38]), float(ln[38:46]), float(ln[46:54])] for ln in atoms if ln[12:16].strip() == "CA"])
-    res_of = np.cumsum([ln[12:16].strip() == "N" for ln in atoms]) - 1
-    with open(path, "w") as f:
-        for m, x in enumerate(coords):
-            f.write(f"MODEL     {m + 1:4d}\n")
-            for ln, r in zip(atoms, res_of):
-                p = np.array([float(ln[30:38]), float(ln[38:46]), float(ln[46:54])]) - ca[r] + x[r]
-                f.write(f"{ln[:30]}{p[0]:8.3f}{p[1]:8.3f}{p[2]:8.3f}{ln[54:]}")
-            f.write("ENDMDL\n")
-        f.write("END\n")
-
-
-def test_eval_extra_metric_columns(tmp_path):
+@pytest.mark.parametrize("family", ["rmsd", "tm", "lddt"])
+def test_eval_extra_metric_columns(tmp_path, family):
     import glob
-    import importlib.util
 
     from str2str_amd.common.pdb_utils import extract_backbone_coords
     from str2str_amd.metrics import metrics
 
-    spec = importlib.util.spec_from_file_location("s2s_eval_entry", os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
+    entry = load_eval_entry(f"s2s_eval_entry_{family}")
     target_dir = os.path.join(GOLDEN, "pdb")
     template = os.path.join(target_dir, "CLN025.pdb")
     tgt = extract_backbone_coords(template)
     rng = np.random.default_rng(3)
     coords = tgt[0][None] + rng.normal(size=(6,) + tgt.shape[1:]) * 0.7
     five = ["val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"]
-    extra = ["div_rmsd", "rmsd_recall", "rmsd_precision"]
+    extra = [f"div_{family}", f"{family}_recall", f"{family}_precision"]
     for sub, names in (("plain", None), ("extra", extra)):
         pred_dir = tmp_path / sub / "samples" / "all"
         pred_dir.mkdir(parents=True)
-        _write_models(str(pred_dir / "CLN025.pdb"), template, coords)
+        write_models(str(pred_dir / "CLN025.pdb"), template, coords)
         entry.evaluate_prediction(str(pred_dir), target_dir, tag="t", extra_metrics=names)
         files = glob.glob(str(tmp_path / sub / "metrics_t_*.csv"))
         assert len(files) == 1
@@ -374,6 +352,65 @@ def test_eval_extra_metric_columns(tmp_path):
         if names:
             ca = {"target": tgt, "pred": extract_backbone_coords(str(pred_dir / "CLN025.pdb"))}
             assert ca["pred"].shape == (6,) + tgt.shape[1:]
-            recall, precision = metrics.coverage_rmsd(ca)
-            want = [metrics.diversity_rmsd(ca)["pred"], recall["pred"], precision["pred"]]
-            assert [float(v) for v in rows[1][6:]] == [float(v) for v in want] and want[0] > 0.0
+            recall, precision = getattr(metrics, f"coverage_{family}")(ca)
+            want = [getattr(metrics, f"diversity_{family}")(ca)["pred"], recall["pred"], precision["pred"]]
+            # (an RMSD diversity is positive; a TM-score or lDDT diversity lies strictly inside (0, 1))
+            assert [float(v) for v in rows[1][6:]] == [float(v) for v in want] and (want[0] > 0.0 if family == "rmsd" else 0.0 < want[0] < 1.0)
+
+
+def test_wrong_out_is_rejected_and_eval_computes_every_family_once(tmp_path, monkeypatch):
+    """``ca_rmsd_matrix`` checks a caller's ``out`` like the TM and lDDT wrappers; one ``evaluate_prediction`` with every extra column
+    computes each coverage pair and the backbone violations once per target, and writes the row the public functions give."""
+    import glob
+
+    from str2str_amd import ops
+    from str2str_amd.common.pdb_utils import extract_backbone_atoms, extract_backbone_coords
+    from str2str_amd.metrics import metrics
+
+    entry = load_eval_entry("s2s_eval_entry_once")
+    target_dir = os.path.join(GOLDEN, "pdb")
+    template = os.path.join(target_dir, "CLN025.pdb")
+    tgt = extract_backbone_coords(template)
+    rng = np.random.default_rng(3)
+    coords = tgt[0][None] + rng.normal(size=(6,) + tgt.shape[1:]) * 0.7
+    a = _dev(coords.astype(np.float32))
+    for out in (torch.empty(7, 6, dtype=torch.float64, device="cuda"), torch.empty(6, 6, dtype=torch.float32, device="cuda")):
+        with pytest.raises(ops.HipLibraryError, match="out"):
+            ops.ca_rmsd_matrix(a, out=out)
+    out = torch.empty(6, 6, dtype=torch.float64, device="cuda")
+    assert ops.ca_rmsd_matrix(a, out=out) is out and torch.equal(out, ops.ca_rmsd_matrix(a))
+
+    calls = {}
+
+    def counted(module, name):
+        fn = getattr(module, name)
+
+        def passes_through(*args, **kwargs):
+            calls[name] = calls.get(name, 0) + 1
+            return fn(*args, **kwargs)
+
+        monkeypatch.setattr(module, name, passes_through)
+
+    for name in ("coverage_rmsd", "coverage_tm", "coverage_lddt"):
+        counted(metrics, name)
+    counted(ops, "backbone_violations")
+    pred_dir = tmp_path / "samples" / "all"
+    pred_dir.mkdir(parents=True)
+    pred_file = str(pred_dir / "CLN025.pdb")
+    write_models(pred_file, template, coords)
+    entry.evaluate_prediction(str(pred_dir), target_dir, tag="t", extra_metrics=list(entry.EXTRA_METRICS))
+    assert calls == {"coverage_rmsd": 1, "coverage_tm": 1, "coverage_lddt": 1, "backbone_violations": 1}
+    monkeypatch.undo()
+
+    files = glob.glob(str(tmp_path / "metrics_t_*.csv"))
+    assert len(files) == 1
+    rows = [ln.rstrip("\n").split("\t") for ln in open(files[0])]
+    assert rows[0][6:] == list(entry.EXTRA_METRICS) and [r[0] for r in rows[1:]] == ["CLN025", "mean"]
+    atoms, aatype, residue_index = extract_backbone_atoms(pred_file)
+    bond, clash = metrics.backbone_validity({"pred": atoms}, aatype, residue_index)
+    want = [bond["pred"], clash["pred"], metrics.violation_rate({"pred": atoms}, aatype, residue_index)["pred"]]
+    ca = {"target": tgt, "pred": extract_backbone_coords(pred_file)}
+    for family in ("rmsd", "tm", "lddt"):
+        recall, precision = getattr(metrics, f"coverage_{family}")(ca)
+        want += [getattr(metrics, f"diversity_{family}")(ca)["pred"], recall["pred"], precision["pred"]]
+    assert [float(v) for v in rows[1][6:]] == [float(v) for v in want]

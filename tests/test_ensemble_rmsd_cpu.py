@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, record_margin
+from ensemble_cases import load_eval_entry
 from test_ensemble_rmsd import LENGTHS, U64, horn, make_ensemble, make_weights, random_walk, ref_msd_matrix
 
 NAMES = ("s2s_ca_rmsd_matrix", "s2s_ca_superpose", "s2s_apply_xform")
@@ -77,11 +78,8 @@ def test_svd_reference_agrees_with_eigvalsh(L, wmode):
 
 
 def test_unknown_extra_metric_is_rejected_before_the_device(tmp_path, monkeypatch):
-    import importlib.util
 
-    spec = importlib.util.spec_from_file_location("s2s_eval_entry_cpu", os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
+    entry = load_eval_entry("s2s_eval_entry_cpu")
     assert entry.metric_columns(None) == ["val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"]
     assert entry.metric_columns(["rmsd_recall", "div_rmsd"])[5:] == ["rmsd_recall", "div_rmsd"]
     from str2str_amd.metrics import metrics
@@ -99,3 +97,26 @@ def test_extra_metrics_parse_from_the_command_line(monkeypatch):
     cfg = C.compose(os.path.join(ROOT, "configs"), "eval.yaml", ["+extra_metrics=[div_rmsd,rmsd_recall,rmsd_precision]"])
     assert list(cfg.get("extra_metrics")) == ["div_rmsd", "rmsd_recall", "rmsd_precision"]
     assert C.compose(os.path.join(ROOT, "configs"), "eval.yaml", []).get("extra_metrics") is None
+
+
+def test_argument_checks_fire_before_the_library(monkeypatch):
+    """``ca_rmsd_matrix`` and ``ca_superpose`` look at their arguments before they load the library: the malformed inputs of
+    tests/test_ensemble_tm_cpu.py raise HipLibraryError with ``load_library`` out of reach."""
+    import torch
+
+    from str2str_amd import ops
+    from str2str_amd.ops import ensemble
+
+    def touched(*a, **k):
+        raise AssertionError("loaded the library")
+
+    monkeypatch.setattr(ensemble, "load_library", touched)
+    x = torch.zeros(4, 8, 3)
+    for kwargs in (dict(a=torch.zeros(4, 8)), dict(a=torch.zeros(4, 8, 2)), dict(a=torch.zeros(0, 8, 3)), dict(a=torch.zeros(4, 0, 3)),
+                   dict(a=x, b=torch.zeros(4, 9, 3)), dict(a=x, b=torch.zeros(8, 3)), dict(a=np.zeros((4, 8, 3), dtype=np.float32))):
+        with pytest.raises(ops.HipLibraryError):
+            ops.ca_rmsd_matrix(**kwargs)
+    for mobile, target in ((torch.zeros(4, 8), torch.zeros(8, 3)), (x, torch.zeros(9, 3)), (x, torch.zeros(1, 8, 3)), (torch.zeros(0, 8, 3), torch.zeros(8, 3)),
+                           (x.numpy(), torch.zeros(8, 3)), (x, torch.zeros(8, 3))):
+        with pytest.raises(ops.HipLibraryError):
+            ops.ca_superpose(mobile, target)

@@ -19,7 +19,6 @@ Achieved values are recorded through ``record_margin`` in units of their bound.
 """
 import functools
 import glob
-import importlib.util
 import os
 
 import numpy as np
@@ -28,17 +27,14 @@ import torch
 
 import ref_ss as ref
 import ss_cases as cases
-from conftest import ROOT, record_margin
+from conftest import record_margin
+from ensemble_cases import load_eval_entry, to_device as _dev
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 ULP = 2.0 ** -52
 ENERGY_OPS = 44
-
-
-def _dev(x):
-    return torch.as_tensor(np.asarray(x)).to(DEV)
 
 
 @functools.lru_cache(maxsize=None)
@@ -210,13 +206,6 @@ def test_ensemble_metrics_against_the_yardsticks_tail():
     assert metrics.js_rama(both, "target", n_bins=12, residue_index=ri)["pred"] == _tails(both, aatype, ri, 12)["js"]["pred"]
 
 
-def _eval_entry():
-    spec = importlib.util.spec_from_file_location("s2s_eval_entry_ss", os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
-    return entry
-
-
 def test_eval_secondary_structure_switch(tmp_path):
     """Three targets written with the project's own writer, the last one's target file cut down to its CA trace.  With the switch the ss
     csv and the per-residue tables hold the yardstick's values for what the reader returns (NaN in the target columns of the CA trace);
@@ -224,7 +213,7 @@ def test_eval_secondary_structure_switch(tmp_path):
     from str2str_amd.common.pdb_utils import atom37_to_pdb, extract_backbone_atoms
     from str2str_amd.metrics import metrics
 
-    entry = _eval_entry()
+    entry = load_eval_entry("s2s_eval_entry_ss")
     target_dir = tmp_path / "targets"
     target_dir.mkdir()
     ensembles = {}

@@ -3,7 +3,6 @@ of the fixture proteins and, for its dihedral, to the reference through tests/go
 case a parity input; the C-ABI surface, the numpy tails of the ensemble metrics and the evaluation switch."""
 import ctypes
 import glob
-import importlib.util
 import os
 import re
 
@@ -14,6 +13,7 @@ import torch
 import ref_ss as ref
 import ss_cases as cases
 from conftest import GOLDEN, ROOT, golden, record_margin
+from ensemble_cases import load_eval_entry
 
 ALA = lambda L: (np.zeros(L, dtype=np.int64), np.arange(L))   # noqa: E731
 
@@ -276,17 +276,10 @@ def test_propensity_strings_and_ramachandran_tails():
 
 
 # ---------------------------------------------------------------------------------------------------------------------- eval.py
-def _eval_entry(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
-    return entry
-
-
 def test_ss_columns_and_the_switch(monkeypatch):
     from str2str_amd.utils import config as C
 
-    entry = _eval_entry("s2s_eval_entry_ss_cpu")
+    entry = load_eval_entry("s2s_eval_entry_ss_cpu")
     assert entry.SS_COLUMNS == ("ss_helix", "ss_strand", "ss_helix_target", "ss_strand_target", "ss_mae", "js_rama")
     assert not set(entry.SS_COLUMNS) & set(entry.EXTRA_METRICS) and len(entry.EXTRA_METRICS) == 12 and len(entry.BACKBONE_METRICS) == 3
     monkeypatch.setenv("TEST_DATA", "/nonexistent")

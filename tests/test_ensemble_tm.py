@@ -8,16 +8,14 @@ is ill conditioned and left out, and at most 1 % of the pairs may be.  L = 2 (tw
 parity inputs: finite values in (0, 1] only.
 """
 import functools
-import glob
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import ref_tm64 as ref
-from conftest import GOLDEN, ROOT, record_margin
+from conftest import record_margin
+from ensemble_cases import close_4 as _close_4, to_device as _dev
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +24,6 @@ BOUND = 1e-9
 # no windows; the duplicate-window case; the d0 floor edge; wave-width edges; several residues per staging lane; above 341 residues the
 # tile needs more than the default 64 KiB of dynamic LDS
 LENGTHS = (1, 3, 4, 5, 8, 16, 21, 22, 35, 63, 64, 65, 130, 256, 400)
-
-
-def _dev(x):
-    return torch.as_tensor(np.asarray(x)).to(DEV)
 
 
 def _sizes(L):
@@ -175,10 +169,6 @@ def test_tm_superpose(L):
     assert (aligned == ops.apply_xform(_dev(mobile), xform).cpu().numpy()).all()
 
 
-def _close_4(got, want):
-    return abs(float(got) - float(np.around(want, decimals=4))) <= 1e-4 + 1e-12   # (+- 1e-4: a value on a rounding edge)
-
-
 def test_diversity_and_coverage_metrics():
     from str2str_amd.metrics import metrics
 
@@ -201,52 +191,6 @@ def test_diversity_and_coverage_metrics():
     assert _close_4(recall["pred"], cross.max(0).mean()) and _close_4(precision["pred"], cross.max(1).mean())
     # 12 x 9 pairs in chunks of 36 = three row chunks: running maxima, the very same numbers
     assert metrics.coverage_tm({"target": target, "pred": pred}, chunk_pairs=36) == (recall, precision)
-    per_ref, per_sample = metrics._coverage_maxima(_dev(pred), _dev(target), chunk_pairs=36)
+    per_ref, per_sample = metrics._coverage_extrema(metrics.TM, _dev(pred), _dev(target), chunk_pairs=36)
     assert np.abs(per_ref.cpu().numpy() - cross.max(0)).max() <= BOUND and np.abs(per_sample.cpu().numpy() - cross.max(1)).max() <= BOUND
 
-
-def _write_models(path, template, coords):
-    """A multi-model PDB with the CA-bearing residues of ``template`` (one model) moved to ``coords`` [R, L, 3] (all atoms of a residue
-    shifted with its CA)."""
-    atoms = [ln for ln in open(template) if ln.startswith("ATOM")]
-    ca = np.array([[float(ln[30:38]), float(ln[38:46]), float(ln[46:54])] for ln in atoms if ln[12:16].strip() == "CA"])
-    res_of = np.cumsum([ln[12:16].strip() == "N" for ln in atoms]) - 1
-    with open(path, "w") as f:
-        for m, x in enumerate(coords):
-            f.write(f"MODEL     {m + 1:4d}\n")
-            for ln, r in zip(atoms, res_of):
-                p = np.array([float(ln[30:38]), float(ln[38:46]), float(ln[46:54])]) - ca[r] + x[r]
-                f.write(f"{ln[:30]}{p[0]:8.3f}{p[1]:8.3f}{p[2]:8.3f}{ln[54:]}")
-            f.write("ENDMDL\n")
-        f.write("END\n")
-
-
-def test_eval_tm_metric_columns(tmp_path):
-    from str2str_amd.common.pdb_utils import extract_backbone_coords
-    from str2str_amd.metrics import metrics
-
-    spec = importlib.util.spec_from_file_location("s2s_eval_entry_tm", os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
-    target_dir = os.path.join(GOLDEN, "pdb")
-    template = os.path.join(target_dir, "CLN025.pdb")
-    tgt = extract_backbone_coords(template)
-    rng = np.random.default_rng(3)
-    coords = tgt[0][None] + rng.normal(size=(6,) + tgt.shape[1:]) * 0.7
-    five = ["val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"]
-    extra = ["div_tm", "tm_recall", "tm_precision"]
-    for sub, names in (("plain", None), ("extra", extra)):
-        pred_dir = tmp_path / sub / "samples" / "all"
-        pred_dir.mkdir(parents=True)
-        _write_models(str(pred_dir / "CLN025.pdb"), template, coords)
-        entry.evaluate_prediction(str(pred_dir), target_dir, tag="t", extra_metrics=names)
-        files = glob.glob(str(tmp_path / sub / "metrics_t_*.csv"))
-        assert len(files) == 1
-        rows = [ln.rstrip("\n").split("\t") for ln in open(files[0])]
-        assert rows[0] == [""] + five + (names or []) and [r[0] for r in rows[1:]] == ["CLN025", "mean"]
-        if names:
-            ca = {"target": tgt, "pred": extract_backbone_coords(str(pred_dir / "CLN025.pdb"))}
-            assert ca["pred"].shape == (6,) + tgt.shape[1:]
-            recall, precision = metrics.coverage_tm(ca)
-            want = [metrics.diversity_tm(ca)["pred"], recall["pred"], precision["pred"]]
-            assert [float(v) for v in rows[1][6:]] == [float(v) for v in want] and 0.0 < want[0] < 1.0

@@ -1,7 +1,6 @@
 """The TM-score feature without a GPU: its yardstick (tests/ref_tm64.py) held to the properties the definition promises, the C-ABI
 surface, the evaluation columns, and the argument checks that must fire before any device call."""
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
@@ -10,6 +9,7 @@ import torch
 
 import ref_tm64 as ref
 from conftest import ROOT, record_margin
+from ensemble_cases import load_eval_entry
 from str2str_amd.metrics.metrics import tm_d0   # (the package's d0 drives the yardstick below: the two must be one function of L)
 
 NAMES = ("s2s_ca_tm_matrix", "s2s_ca_tm_superpose")
@@ -80,15 +80,8 @@ def test_seed_list():
         assert seeds[0] == (0, L) and len(seeds) <= 16 and all(0 <= s and n >= 1 and s + n <= L for s, n in seeds)
 
 
-def _eval_entry():
-    spec = importlib.util.spec_from_file_location("s2s_eval_entry_tm_cpu", os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
-    return entry
-
-
 def test_metric_columns_accept_the_tm_names():
-    entry = _eval_entry()
+    entry = load_eval_entry("s2s_eval_entry_tm_cpu")
     five = ["val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"]
     assert entry.metric_columns(["tm_precision", "div_tm", "tm_recall"]) == five + ["tm_precision", "div_tm", "tm_recall"]
     assert entry.metric_columns(["div_rmsd", "div_tm"]) == five + ["div_rmsd", "div_tm"]
@@ -173,7 +166,7 @@ def test_unknown_names_stay_unknown(tmp_path, monkeypatch):
     before the device."""
     from str2str_amd.metrics import metrics
 
-    entry = _eval_entry()
+    entry = load_eval_entry("s2s_eval_entry_tm_cpu")
     monkeypatch.setattr(metrics, "_dev", lambda x: (_ for _ in ()).throw(AssertionError("touched the device")))
     for bad in (["div_tm", "tm_score"], ["tm"], "rmsd", ["tm_recall", "tm_recall"]):
         with pytest.raises(ValueError):

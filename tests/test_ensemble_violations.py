@@ -9,8 +9,6 @@ n_terms 2^-52 max(1, |value|), the a-priori bound of such a sum.
 """
 import functools
 import glob
-import importlib.util
-import os
 
 import numpy as np
 import pytest
@@ -18,16 +16,12 @@ import torch
 
 import ref_violations as ref
 import violations_cases as cases
-from conftest import ROOT, golden, record_margin
+from conftest import golden, record_margin
+from ensemble_cases import load_eval_entry, to_device as _dev
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 ULP = 2.0 ** -52
-
-
-def _dev(x):
-    return torch.as_tensor(np.asarray(x)).to(DEV)
 
 
 @functools.lru_cache(maxsize=None)
@@ -168,20 +162,13 @@ def test_validity_and_rate_metrics():
         assert 0.0 < bond[k] < 1.0 and 0.0 < clash[k] < 1.0 and 0.0 < rate[k] < 1.0
 
 
-def _eval_entry():
-    spec = importlib.util.spec_from_file_location("s2s_eval_entry_violations", os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
-    return entry
-
-
 def test_eval_backbone_columns(tmp_path):
     """Two targets written with the project's own writer; the three columns hold the yardstick's values for what the reader returns, and a
     run without them gives the five columns of before."""
     from str2str_amd.common.pdb_utils import atom37_to_pdb, extract_backbone_atoms
     from str2str_amd.metrics import metrics
 
-    entry = _eval_entry()
+    entry = load_eval_entry("s2s_eval_entry_violations")
     target_dir = tmp_path / "targets"
     target_dir.mkdir()
     five = ["val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"]

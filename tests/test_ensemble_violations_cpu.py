@@ -3,7 +3,6 @@ tests/golden/violations.npz and to cases worked by hand, the margin that makes e
 reader of the five backbone atoms and the evaluation columns."""
 import ctypes
 import glob
-import importlib.util
 import os
 import re
 
@@ -14,6 +13,7 @@ import torch
 import ref_violations as ref
 import violations_cases as cases
 from conftest import GOLDEN, ROOT, golden, record_margin
+from ensemble_cases import load_eval_entry
 
 FIXTURE_BOUND = 5e-7   # x max(1, |value|): the reference works in float32 (2^-23 = 1.2e-7); 1.0e-7 was measured when the fixture was made
 TAGS = ("ideal12", "ideal40", "stretched", "o_n", "hairpin")
@@ -285,9 +285,7 @@ def test_extract_backbone_atoms(tmp_path):
 
 # ---------------------------------------------------------------------------------------------------------------------- eval.py
 def test_metric_columns_accept_the_backbone_names():
-    spec = importlib.util.spec_from_file_location("s2s_eval_entry_violations_cpu", os.path.join(ROOT, "eval.py"))
-    entry = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(entry)
+    entry = load_eval_entry("s2s_eval_entry_violations_cpu")
     five = ["val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"]
     names = ["val_bb_bond", "val_bb_clash", "viol_per_residue"]
     assert entry.metric_columns(None) == five and entry.metric_columns([]) == five

@@ -13,13 +13,12 @@ The kernel's work is counted from the lists themselves: (included unordered pair
 float32 points (24 B) from LDS, 11 float64 operations (three differences, three products and two sums for the squared distance count as
 8, with the conversions left out) and eight float64 comparisons.
 """
-import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import timing_common
+
+ROOT = timing_common.ROOT
 sys.path.insert(0, ROOT)
 
 CASES = {"1000x1000_L256": (1000, 256), "2000x2000_L64": (2000, 64)}
@@ -27,7 +26,6 @@ CUTOFF = 15.0
 REPEATS = 5
 TORCH_CHUNK_BYTES = 1 << 30          # the [chunk, Rb, L, L] float64 difference tensor of the torch restatement
 CASE_TIMEOUT_S = 420
-LATTICE = 24.0                       # A between the tiled copies of the chain (its radius of gyration is 11.4 A)
 PEAK_F64_VECTOR = 78.6e12            # the data sheet's float64 vector rate
 
 
@@ -38,9 +36,7 @@ def chain(L):
     from str2str_amd.common.pdb_utils import extract_backbone_coords
 
     ca = np.asarray(extract_backbone_coords(os.path.join(ROOT, "tests", "golden", "pdb", "lambda.pdb"))[0], dtype=np.float64)
-    copies = -(-L // len(ca))
-    cells = [(i, j, k) for k in range(copies) for j in range(2) for i in range(2)][:copies]
-    return np.concatenate([ca + LATTICE * np.asarray(c, dtype=np.float64) for c in cells])[:L]
+    return timing_common.tile_on_lattice(ca, L)
 
 
 def ensemble(n, L, seed):
@@ -80,24 +76,6 @@ def torch_lddt(a, b, cutoff=CUTOFF, want_pairs=False):
     return (out, pairs) if want_pairs else out
 
 
-def timed(fn, repeats=REPEATS, warmup=1):
-    """-> the time of every repetition (ms), each between its own pair of device events."""
-    import torch
-
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b))
-    return out
-
-
 def run_case(name, kernel_only=False):
     import torch
 
@@ -106,11 +84,11 @@ def run_case(name, kernel_only=False):
     n, L = CASES[name]
     a, b = ensemble(n, L, 1), ensemble(n, L, 2)
     out = torch.empty(n, n, dtype=torch.float64, device="cuda")
-    kernel_ms = timed(lambda: ops.ca_lddt_matrix(a, b, out=out), warmup=2)
+    kernel_ms = timing_common.time_repetitions(lambda: ops.ca_lddt_matrix(a, b, out=out), REPEATS, warmup=2)
     res = {"case": name, "n": n, "L": L, "pairs": n * n, "kernel_ms": kernel_ms, "device": torch.cuda.get_device_name(0)}
     if kernel_only:
         return res
-    torch_ms = timed(lambda: torch_lddt(a, b), warmup=1)
+    torch_ms = timing_common.time_repetitions(lambda: torch_lddt(a, b), REPEATS, warmup=1)
     want, included = torch_lddt(a, b, want_pairs=True)
     evals = float(included.sum()) / 2.0 * n                             # (unordered pair of a reference, model)
     diff = (want - out).abs()
@@ -128,22 +106,9 @@ def _ms(xs):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(CASES))
-    ap.add_argument("--kernel-only", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lddt_timing.md"))
-    args = ap.parse_args()
-    if args.case:
-        print(json.dumps(run_case(args.case, args.kernel_only)), flush=True)
+    rows, out = timing_common.collect(__file__, CASES, run_case, os.path.join(ROOT, "profiles", "lddt_timing.md"), CASE_TIMEOUT_S, kernel_only=True)
+    if rows is None:
         return 0
-    rows = []
-    for name in CASES:      # one child per case, each under its own time limit; nothing more is started after a failure
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name], capture_output=True, text=True, timeout=CASE_TIMEOUT_S)
-        if p.returncode != 0:
-            sys.stderr.write(p.stdout + p.stderr)
-            return p.returncode or 1
-        rows.append(json.loads(p.stdout.strip().splitlines()[-1]))
-        print(rows[-1], flush=True)
     holds = all(r["holds"] for r in rows)
     lines = ["# All-pairs lDDT: s2s_ca_lddt_matrix against the same definition in batched float64 torch", "",
              f"Device: {rows[0]['device']}.  `python tools/lddt_timing.py`; every repetition between its own pair of device events around the whole "
@@ -167,9 +132,7 @@ def main():
         lines.append(f"| {r['case']} | {r['evaluations']:.3e} | {r['evaluations_per_s']:.3e} | {r['lds_gather_bytes_per_s'] / 1e12:.2f} | "
                      f"{100 * r['share_of_f64_vector_peak']:.1f} % |")
     lines.append("")
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines))
+    timing_common.write_report(out, lines)
     return 0 if holds else 2
 
 

@@ -10,13 +10,12 @@ first rows of the case, BASELINE_PAIRS pairs, and scaled to all pairs (stated in
 "Share of the float64 matrix peak" = 2 * 9 * L flop per computed pair (the cross-covariance product only) over the kernel's time,
 against the 78.6 TFLOP/s float64 matrix rate of the MI355X data sheet.
 """
-import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import timing_common
+
+ROOT = timing_common.ROOT
 sys.path.insert(0, ROOT)
 
 CASES = {"self_1000_L35": (1000, None, 35), "self_1000_L256": (1000, None, 256), "cross_1000x10000_L256": (1000, 10000, 256)}
@@ -48,24 +47,6 @@ def svd_rmsd(a, b):
     return msd.clamp_min(0.0).sqrt()
 
 
-def timed(fn, min_window_s=0.5, warmup=3):
-    import torch
-
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    reps, total = 0, 0.0
-    while total < min_window_s * 1e3 and reps < 5000:
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        total += a.elapsed_time(b)
-        reps += 1
-    return total / reps, reps
-
-
 def run_case(name):
     import torch
 
@@ -76,7 +57,7 @@ def run_case(name):
     b = None if n_b is None else chains(n_b, L, 2)
     cols = n_a if b is None else n_b
     out = torch.empty(n_a, cols, dtype=torch.float64, device="cuda")
-    kernel_ms, reps = timed(lambda: ops.ca_rmsd_matrix(a, b, out=out))
+    kernel_ms, reps = timing_common.time_window(lambda: ops.ca_rmsd_matrix(a, b, out=out), warmup=3)
     pairs = n_a * cols
     computed = n_a * (n_a + 1) // 2 if b is None else pairs         # the self case evaluates the upper triangle and mirrors it
     rows = max(1, min(n_a, BASELINE_PAIRS // cols))
@@ -87,7 +68,7 @@ def run_case(name):
         for r0 in range(0, n_rows, rows):
             svd_rmsd(a[r0:r0 + rows], bb)
 
-    svd_ms, svd_reps = timed(baseline, min_window_s=0.5, warmup=1)
+    svd_ms, svd_reps = timing_common.time_window(baseline, warmup=1)
     err = float((svd_rmsd(a[:rows], bb) - out[:rows]).abs().max())
     return {"case": name, "n_a": n_a, "n_b": cols, "L": L, "pairs": pairs, "kernel_ms": kernel_ms, "kernel_reps": reps,
             "svd_ms_measured": svd_ms, "svd_pairs_measured": n_rows * cols, "svd_reps": svd_reps, "svd_ms_all_pairs": svd_ms * n_a / n_rows,
@@ -96,21 +77,9 @@ def run_case(name):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(CASES))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ensemble_rmsd_timing.md"))
-    args = ap.parse_args()
-    if args.case:
-        print(json.dumps(run_case(args.case)), flush=True)
+    rows, out = timing_common.collect(__file__, CASES, run_case, os.path.join(ROOT, "profiles", "ensemble_rmsd_timing.md"), CASE_TIMEOUT_S)
+    if rows is None:
         return 0
-    rows = []
-    for name in CASES:      # one child per case, each under its own time limit; nothing more is started after a failure
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name], capture_output=True, text=True, timeout=CASE_TIMEOUT_S)
-        if p.returncode != 0:
-            sys.stderr.write(p.stdout + p.stderr)
-            return p.returncode or 1
-        rows.append(json.loads(p.stdout.strip().splitlines()[-1]))
-        print(rows[-1], flush=True)
     lines = ["# All-pairs minimum RMSD: s2s_ca_rmsd_matrix against batched float64 torch.linalg.svd", "",
              f"Device: {rows[0]['device']}.  `python tools/rmsd_timing.py`; device events around the whole call, mean over the repetitions.", "",
              "| case | pairs | kernel (ms) | torch.linalg.svd float64, same pairs (ms) | speed-up | share of the float64 matrix peak | max abs diff vs SVD (A) |",
@@ -122,9 +91,7 @@ def main():
     lines += ["", "Share of peak: 2 x 9 x L flop per computed pair (the cross-covariance product alone; the self case computes the upper "
               "triangle) over the call's time, against the data sheet's 78.6 TFLOP/s float64 matrix rate.  The call also runs the prepass and "
               "one 4 x 4 Jacobi eigen-solve per pair, which the flop count leaves out.", ""]
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines))
+    timing_common.write_report(out, lines)
     return 0
 
 

@@ -8,37 +8,17 @@ of tests/golden/pdb/lambda.pdb (80 residues, five helices) cut or tiled on a 24 
 copies.  Every repetition is timed on its own with device events around the whole call (one launch: staging, hydrogens and torsions, the
 hydrogen-bond sweep, patterns, states), after warm-up; all of them are written out.  The share of (acceptor, donor) residue pairs that
 pass the 9 A CA prefilter -- the pairs whose energy is evaluated -- is counted in torch from the CA atoms of the first 16 structures."""
-import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import timing_common
+
+ROOT = timing_common.ROOT
 sys.path.insert(0, ROOT)
 
 CASES = {"20000x64": (20000, 64), "10000x256": (10000, 256), "4000x512": (4000, 512)}
 REPEATS = 5
 CASE_TIMEOUT_S = 300
-LATTICE = 24.0                       # A between the tiled copies of the chain (its radius of gyration is 11.4 A)
-
-
-def ensemble(n, L, seed=1):
-    """-> (atoms [n, L, 5, 3] float32 on the device, aatype [L], residue_index [L])."""
-    import numpy as np
-    import torch
-
-    from str2str_amd.common.pdb_utils import extract_backbone_atoms
-
-    atoms, aatype, _ = extract_backbone_atoms(os.path.join(ROOT, "tests", "golden", "pdb", "lambda.pdb"))
-    per = atoms.shape[1]
-    copies = -(-L // per)
-    cells = [(i, j, k) for k in range(copies) for j in range(2) for i in range(2)][:copies]
-    base = np.concatenate([atoms[0].astype(np.float64) + LATTICE * np.asarray(c, dtype=np.float64) for c in cells])[:L]
-    g = torch.Generator().manual_seed(seed)
-    x = torch.as_tensor(base)[None] + torch.randn(n, L, 5, 3, generator=g, dtype=torch.float64) * torch.linspace(0.02, 1.0, n, dtype=torch.float64)[:, None, None, None]
-    residue_index = np.arange(L) + 10 * (np.arange(L) // per)          # a numbering gap between the copies
-    return x.to("cuda", torch.float32), np.tile(aatype, copies)[:L], residue_index
 
 
 def survivors(atoms):
@@ -52,32 +32,16 @@ def survivors(atoms):
     return float(((d < 9.0) & off).sum()) / float(off.sum() * d.shape[0])
 
 
-def timed(fn, repeats=REPEATS, warmup=2):
-    """-> the time of every repetition (ms), each between its own pair of device events."""
-    import torch
-
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b))
-    return out
-
-
 def run_case(name):
+    import numpy as np
     import torch
 
     from str2str_amd import ops
 
     n, L = CASES[name]
-    atoms, aatype, residue_index = ensemble(n, L)
-    ms = timed(lambda: ops.secondary_structure(atoms, aatype, residue_index))
+    atoms, aatype, per = timing_common.lambda_backbone_ensemble(n, L)
+    residue_index = np.arange(L) + 10 * (np.arange(L) // per)          # a numbering gap between the copies
+    ms = timing_common.time_repetitions(lambda: ops.secondary_structure(atoms, aatype, residue_index), REPEATS, warmup=2)
     ss, n_hbonds, _, _, _ = ops.secondary_structure(atoms, aatype, residue_index)
     helix = float(((ss == ord("H")) | (ss == ord("G")) | (ss == ord("I"))).double().mean())
     return {"case": name, "n": n, "L": L, "kernel_ms": ms, "structures_per_s": n / (min(ms) * 1e-3),
@@ -86,21 +50,9 @@ def run_case(name):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(CASES))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ss_timing.md"))
-    args = ap.parse_args()
-    if args.case:
-        print(json.dumps(run_case(args.case)), flush=True)
+    rows, out = timing_common.collect(__file__, CASES, run_case, os.path.join(ROOT, "profiles", "ss_timing.md"), CASE_TIMEOUT_S)
+    if rows is None:
         return 0
-    rows = []
-    for name in CASES:      # one child per case, each under its own time limit; nothing more is started after a failure
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name], capture_output=True, text=True, timeout=CASE_TIMEOUT_S)
-        if p.returncode != 0:
-            sys.stderr.write(p.stdout + p.stderr)
-            return p.returncode or 1
-        rows.append(json.loads(p.stdout.strip().splitlines()[-1]))
-        print(rows[-1], flush=True)
     lines = ["# Secondary structure and torsions: s2s_secondary_structure", "",
              f"Device: {rows[0]['device']}.  `python tools/ss_timing.py`; every repetition between its own pair of device events around the "
              "whole call (one launch: staging, hydrogens and torsions, hydrogen-bond sweep, patterns, states), after warm-up (measured).  "
@@ -111,9 +63,7 @@ def main():
         lines.append(f"| {r['case']} | {', '.join(f'{x:.2f}' for x in r['kernel_ms'])} | {r['structures_per_s']:.3e} | {r['residue_pairs_per_s']:.3e} | "
                      f"{100 * r['pairs_passing_prefilter']:.1f} % | {r['mean_hbonds']:.1f} | {r['helix_fraction']:.3f} |")
     lines.append("")
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines))
+    timing_common.write_report(out, lines)
     return 0
 
 

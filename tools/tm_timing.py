@@ -11,13 +11,12 @@ to all computed pairs (stated in the output); its values are compared with the k
 78.6 TFLOP/s float64 vector rate of the MI355X data sheet; the 4 x 4 eigen-solves and the duplicate lanes of short seed lists are left
 out of the count.
 """
-import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import timing_common
+
+ROOT = timing_common.ROOT
 sys.path.insert(0, ROOT)
 
 CASES = {"self_1000_L35": (1000, 35), "self_1000_L80": (1000, 80), "self_1000_L256": (1000, 256)}
@@ -81,24 +80,6 @@ def torch_tm(a, b):
     return best
 
 
-def timed(fn, min_window_s=0.5, warmup=2):
-    import torch
-
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    reps, total = 0, 0.0
-    while total < min_window_s * 1e3 and reps < 5000:
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        total += a.elapsed_time(b)
-        reps += 1
-    return total / reps, reps
-
-
 def run_case(name, kernel_only=False):
     import torch
 
@@ -107,7 +88,7 @@ def run_case(name, kernel_only=False):
     n, L = CASES[name]
     a = chains(n, L, 1)
     out = torch.empty(n, n, dtype=torch.float64, device="cuda")
-    kernel_ms, reps = timed(lambda: ops.ca_tm_matrix(a, out=out))
+    kernel_ms, reps = timing_common.time_window(lambda: ops.ca_tm_matrix(a, out=out), warmup=2)
     computed = n * (n + 1) // 2                               # the self case evaluates i <= j and mirrors
     flop = float(FLOP_PER_RESIDUE) * computed * len(seeds(L)) * (ITERS + 1) * L
     res = {"case": name, "n": n, "L": L, "pairs": n * n, "computed_pairs": computed, "seeds": len(seeds(L)), "kernel_ms": kernel_ms,
@@ -118,7 +99,7 @@ def run_case(name, kernel_only=False):
     i, j = torch.triu_indices(n, n, 1, device="cuda")
     pick = torch.randperm(i.numel(), generator=torch.Generator().manual_seed(3))[:BASELINE_PAIRS].to("cuda")
     i, j = i[pick], j[pick]
-    torch_ms, torch_reps = timed(lambda: torch_tm(a[i], a[j]), min_window_s=0.5, warmup=1)
+    torch_ms, torch_reps = timing_common.time_window(lambda: torch_tm(a[i], a[j]), warmup=1)
     res.update({"torch_ms_measured": torch_ms, "torch_pairs_measured": int(i.numel()), "torch_reps": torch_reps,
                 "torch_ms_all_pairs": torch_ms * computed / i.numel(), "max_abs_diff_vs_torch": float((torch_tm(a[i], a[j]) - out[i, j]).abs().max()),
                 "mean_tm": float(out[i, j].mean())})
@@ -126,22 +107,9 @@ def run_case(name, kernel_only=False):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(CASES))
-    ap.add_argument("--kernel-only", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ensemble_tm_timing.md"))
-    args = ap.parse_args()
-    if args.case:
-        print(json.dumps(run_case(args.case, args.kernel_only)), flush=True)
+    rows, out = timing_common.collect(__file__, CASES, run_case, os.path.join(ROOT, "profiles", "ensemble_tm_timing.md"), CASE_TIMEOUT_S, kernel_only=True)
+    if rows is None:
         return 0
-    rows = []
-    for name in CASES:      # one child per case, each under its own time limit; nothing more is started after a failure
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name], capture_output=True, text=True, timeout=CASE_TIMEOUT_S)
-        if p.returncode != 0:
-            sys.stderr.write(p.stdout + p.stderr)
-            return p.returncode or 1
-        rows.append(json.loads(p.stdout.strip().splitlines()[-1]))
-        print(rows[-1], flush=True)
     lines = ["# All-pairs TM-score: s2s_ca_tm_matrix against the same algorithm in batched float64 torch", "",
              f"Device: {rows[0]['device']}.  `python tools/tm_timing.py`; device events around the whole call, mean over the repetitions (measured).", "",
              "| case | pairs (computed) | seeds | kernel (ms) | torch float64, same algorithm (ms) | ratio | share of the float64 vector peak | max abs diff vs torch |",
@@ -153,9 +121,7 @@ def main():
     lines += ["", f"Share of peak: {FLOP_PER_RESIDUE} flop per (computed pair, seed, pass, residue), {ITERS} evaluations plus the seeding pass, over the "
               "call's time, against the data sheet's 78.6 TFLOP/s float64 vector rate.  The count leaves out one 4 x 4 Jacobi eigen-solve per "
               "(pair, seed, evaluation) and the staging, and the lanes that repeat the whole-chain seed where the list has fewer than 16 seeds.", ""]
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines))
+    timing_common.write_report(out, lines)
     return 0
 
 

@@ -9,39 +9,19 @@ neighbours within the prefilter's reach -- and as ``globule``: the same structur
 prefilter and are expanded into their 25 atom pairs, the work the kernel would do everywhere without it.  Every repetition is timed on its
 own with device events around the whole call, after warm-up; all of them are written out.  The share of residue pairs that pass the
 prefilter is counted in torch from the CA atoms of the first 16 structures."""
-import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import timing_common
+
+ROOT = timing_common.ROOT
 sys.path.insert(0, ROOT)
 
 SIZES = {"10000x256": (10000, 256), "1000x1024": (1000, 1024)}
 CASES = {f"{size}_{kind}": (size, kind) for size in SIZES for kind in ("chain", "globule")}
 REPEATS = 5
 CASE_TIMEOUT_S = 300
-LATTICE = 24.0                       # A between the tiled copies of the chain (its radius of gyration is 11.4 A)
 SHRINK = 0.1
-
-
-def ensemble(n, L, kind, seed=1):
-    """-> (atoms [n, L, 5, 3] float32 on the device, aatype [L], residue_index [L])."""
-    import numpy as np
-    import torch
-
-    from str2str_amd.common.pdb_utils import extract_backbone_atoms
-
-    atoms, aatype, _ = extract_backbone_atoms(os.path.join(ROOT, "tests", "golden", "pdb", "lambda.pdb"))
-    copies = -(-L // atoms.shape[1])
-    cells = [(i, j, k) for k in range(copies) for j in range(2) for i in range(2)][:copies]
-    base = np.concatenate([atoms[0].astype(np.float64) + LATTICE * np.asarray(c, dtype=np.float64) for c in cells])[:L]
-    g = torch.Generator().manual_seed(seed)
-    x = torch.as_tensor(base)[None] + torch.randn(n, L, 5, 3, generator=g, dtype=torch.float64) * torch.linspace(0.02, 1.0, n, dtype=torch.float64)[:, None, None, None]
-    if kind == "globule":
-        x = x * SHRINK
-    return x.to("cuda", torch.float32), np.tile(aatype, copies)[:L], np.arange(L)
 
 
 def survivors(atoms, exists, clash_tolerance=1.5):
@@ -55,24 +35,6 @@ def survivors(atoms, exists, clash_tolerance=1.5):
     return float(((d < rho[:, :, None] + rho[:, None, :] + (3.4 - clash_tolerance)) & upper).sum()) / float(upper.sum() * x.shape[0])
 
 
-def timed(fn, repeats=REPEATS, warmup=2):
-    """-> the time of every repetition (ms), each between its own pair of device events."""
-    import torch
-
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b))
-    return out
-
-
 def run_case(name):
     import numpy as np
     import torch
@@ -81,10 +43,11 @@ def run_case(name):
 
     size, kind = CASES[name]
     n, L = SIZES[size]
-    atoms, aatype, residue_index = ensemble(n, L, kind)
+    atoms, aatype, _ = timing_common.lambda_backbone_ensemble(n, L, scale=SHRINK if kind == "globule" else 1.0)
+    residue_index = np.arange(L)
     exists = np.ones((L, 5), dtype=np.uint8)
     exists[aatype == 7, 4] = 0
-    ms = timed(lambda: ops.backbone_violations(atoms, exists, aatype, residue_index))
+    ms = timing_common.time_repetitions(lambda: ops.backbone_violations(atoms, exists, aatype, residue_index), REPEATS, warmup=2)
     out = ops.backbone_violations(atoms, exists, aatype, residue_index)
     return {"case": name, "n": n, "L": L, "kind": kind, "kernel_ms": ms, "structures_per_s": n / (min(ms) * 1e-3),
             "residue_pairs_per_s": n * (L * (L - 1) / 2) / (min(ms) * 1e-3), "pairs_passing_prefilter": survivors(atoms[:16], exists),
@@ -93,21 +56,9 @@ def run_case(name):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(CASES))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "violations_timing.md"))
-    args = ap.parse_args()
-    if args.case:
-        print(json.dumps(run_case(args.case)), flush=True)
+    rows, out = timing_common.collect(__file__, CASES, run_case, os.path.join(ROOT, "profiles", "violations_timing.md"), CASE_TIMEOUT_S)
+    if rows is None:
         return 0
-    rows = []
-    for name in CASES:      # one child per case, each under its own time limit; nothing more is started after a failure
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name], capture_output=True, text=True, timeout=CASE_TIMEOUT_S)
-        if p.returncode != 0:
-            sys.stderr.write(p.stdout + p.stderr)
-            return p.returncode or 1
-        rows.append(json.loads(p.stdout.strip().splitlines()[-1]))
-        print(rows[-1], flush=True)
     lines = ["# Backbone violations: s2s_backbone_violations, with and without the prefilter's effect", "",
              f"Device: {rows[0]['device']}.  `python tools/violations_timing.py`; every repetition between its own pair of device events around the "
              "whole call (one launch: staging, connection terms, prefilter sweep, atom-pair expansion, outputs), after warm-up (measured).  `chain`: "
@@ -126,9 +77,7 @@ def main():
                      f"{min(g['kernel_ms']) / min(c['kernel_ms']):.1f} x faster than the globule, where it drops "
                      f"{100 * (1 - g['pairs_passing_prefilter']):.1f} %.")
     lines.append("")
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines))
+    timing_common.write_report(out, lines)
     return 0
 
 
