@@ -8,7 +8,10 @@ into the reference's tab-separated ``metrics_<tag>_<mmdd-HH-MM>.csv``.  ``+clust
 (GROMOS at that RMSD, on the device) into ``clusters/<target>.pdb`` and ``clusters_<tag>_<mmdd-HH-MM>.csv`` next to it.
 ``+secondary_structure=true`` also assigns Kabsch & Sander's states to the sampled and the target ensembles (on the device) and writes
 ``ss_<tag>_<mmdd-HH-MM>.csv`` (helix and strand content, their distance from the target's, the Ramachandran JS distance) and the
-per-residue propensities ``secondary_structure/<target>.csv``."""
+per-residue propensities ``secondary_structure/<target>.csv``.
+``+contacts=true`` also computes the CA contacts of the sampled and the target ensembles (on the device) and writes
+``contacts_<tag>_<mmdd-HH-MM>.csv`` (mean fraction of native contacts Q of both, the JS distance of their Q distributions, the mean
+absolute difference of their contact maps, mean relative contact order of both) and the contact probabilities ``contacts/<target>.csv``."""
 import logging
 import os
 import sys
@@ -79,13 +82,42 @@ SS_COLUMNS = ("ss_helix", "ss_strand", "ss_helix_target", "ss_strand_target", "s
 SS_CLASSES = ("helix", "strand", "other")
 
 
-def secondary_structure_switch(value) -> bool:
-    """``+secondary_structure=...`` as a bool: absent, null and false leave everything as it was."""
+def _switch(name, value) -> bool:
     if value is None or isinstance(value, bool):
         return bool(value)
     if isinstance(value, str) and value.strip().lower() in ("true", "false", "1", "0", "yes", "no"):
         return value.strip().lower() in ("true", "1", "yes")
-    raise ValueError(f"secondary_structure {value!r}: expected true or false")
+    raise ValueError(f"{name} {value!r}: expected true or false")
+
+
+def secondary_structure_switch(value) -> bool:
+    """``+secondary_structure=...`` as a bool: absent, null and false leave everything as it was."""
+    return _switch("secondary_structure", value)
+
+
+CONTACT_COLUMNS = ("q_mean", "q_mean_target", "js_q", "contact_mae", "rco", "rco_target")
+
+
+def contacts_switch(value) -> bool:
+    """``+contacts=...`` as a bool: absent, null and false leave everything as it was."""
+    return _switch("contacts", value)
+
+
+def contacts_row(ca):
+    """One row of the contacts csv (CONTACT_COLUMNS) and the table of contact probabilities (i, j, p_pred, p_target: every pair i < j with
+    either above 0) of one target from its CA ensembles {"pred": [R, L, 3], "target": [Rt, L, 3]}.  The native of Q is the first structure
+    of the target ensemble."""
+    import numpy as np
+
+    from str2str_amd.metrics import metrics
+
+    q = metrics.mean_q(ca, ref_key="target")
+    rco = {k: np.around(float(metrics.contact_order(v).mean()), decimals=4) for k, v in ca.items()}
+    row = {"q_mean": q["pred"], "q_mean_target": q["target"], "js_q": metrics.js_q(ca, ref_key="target")["pred"],
+           "contact_mae": metrics.contact_mae(ca, ref_key="target")["pred"], "rco": rco["pred"], "rco_target": rco["target"]}
+    p = {k: metrics.contact_map(v) for k, v in ca.items()}
+    i, j = np.nonzero(np.triu((p["pred"] > 0) | (p["target"] > 0)))
+    return row, {"i": i, "j": j, "p_pred": np.around(p["pred"][i, j], decimals=4), "p_target": np.around(p["target"][i, j], decimals=4)}
 
 
 def secondary_structure_row(pred_file, target_file, log=log):
@@ -116,16 +148,19 @@ def secondary_structure_row(pred_file, target_file, log=log):
 
 
 def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None, cluster_cutoff=None,
-                        secondary_structure=None):
+                        secondary_structure=None, contacts=None):
     """reference src/eval.py:47-99: one row per target, one column per metric, plus the mean row.  ``extra_metrics``: names out of
     EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's).
     ``cluster_cutoff`` (A; None: nothing of this happens): the ``pred`` ensemble of every target is clustered by ``metrics.cluster_rmsd``;
     ``clusters/<target>.pdb`` receives the centres' MODELs, most populated first, and ``clusters_<tag>_<mmdd-HH-MM>.csv`` one row per
     target (CLUSTER_COLUMNS), both next to the metrics csv.  ``secondary_structure`` (true; otherwise nothing of this happens): the
     states of the ``pred`` and the ``target`` ensemble of every target; ``ss_<tag>_<mmdd-HH-MM>.csv`` receives one row per target
-    (SS_COLUMNS) and ``secondary_structure/<target>.csv`` the per-residue propensities of both."""
+    (SS_COLUMNS) and ``secondary_structure/<target>.csv`` the per-residue propensities of both.  ``contacts`` (true; otherwise nothing of
+    this happens): ``contacts_<tag>_<mmdd-HH-MM>.csv`` receives one row per target (CONTACT_COLUMNS) and the mean row, and
+    ``contacts/<target>.csv`` the contact probabilities of both ensembles."""
     columns = metric_columns(extra_metrics)
     secondary_structure = secondary_structure_switch(secondary_structure)
+    contacts = contacts_switch(contacts)
     if cluster_cutoff is not None and not 0.0 < float(cluster_cutoff) < float("inf"):
         raise ValueError(f"cluster_cutoff {cluster_cutoff}: expected a positive finite RMSD in Angstrom")
     from time import strftime
@@ -148,7 +183,7 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
            "div_rmsd": metrics.diversity_rmsd, "div_tm": metrics.diversity_tm, "div_lddt": metrics.diversity_lddt}
     coverage = {"rmsd": metrics.coverage_rmsd, "tm": metrics.coverage_tm, "lddt": metrics.coverage_lddt}
     eval_res = {k: {} for k in columns}
-    clusters, ss_rows = {}, {}
+    clusters, ss_rows, contact_rows = {}, {}, {}
     for target in targets:
         pred_file = os.path.join(pred_dir, f"{target}.pdb")
         if not os.path.isfile(pred_file):
@@ -186,6 +221,10 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
                     table[f"{k}_{c}"] = np.full(len(numbers), np.nan) if prop[k] is None else np.around(prop[k][:, q], decimals=4)
             os.makedirs(os.path.join(output_dir, "secondary_structure"), exist_ok=True)
             pd.DataFrame(table).to_csv(os.path.join(output_dir, "secondary_structure", f"{target}.csv"), index=False, sep="\t")
+        if contacts:
+            contact_rows[target], table = contacts_row(ca)
+            os.makedirs(os.path.join(output_dir, "contacts"), exist_ok=True)
+            pd.DataFrame(table).to_csv(os.path.join(output_dir, "contacts", f"{target}.csv"), index=False, sep="\t")
     df = pd.DataFrame.from_dict(eval_res)
     df.loc["mean"] = np.around(df.mean(), decimals=4)
     df.to_csv(os.path.join(output_dir, f"metrics_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
@@ -195,13 +234,18 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     if secondary_structure:
         pd.DataFrame.from_dict(ss_rows, orient="index", columns=list(SS_COLUMNS)).to_csv(
             os.path.join(output_dir, f"ss_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
+    if contacts:
+        cf = pd.DataFrame.from_dict(contact_rows, orient="index", columns=list(CONTACT_COLUMNS))
+        cf.loc["mean"] = np.around(cf.mean(), decimals=4)
+        cf.to_csv(os.path.join(output_dir, f"contacts_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
     return df.loc["mean"]
 
 
 def evaluate(cfg):
     pred_dir = cfg.get("pred_dir")
     scoring = dict(target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"), extra_metrics=cfg.get("extra_metrics"),
-                   cluster_cutoff=cfg.get("cluster_cutoff"), secondary_structure=cfg.get("secondary_structure"))
+                   cluster_cutoff=cfg.get("cluster_cutoff"), secondary_structure=cfg.get("secondary_structure"),
+                   contacts=cfg.get("contacts"))
     if pred_dir and os.path.isdir(pred_dir):
         log.info(f"Found pre-computed prediction directory {pred_dir}.")
         return evaluate_prediction(pred_dir, **scoring)

@@ -580,6 +580,59 @@ int s2s_cluster_adjacency(const double* values, int n_rows, int row0, int n, dou
 int s2s_cluster_gromos(const unsigned long long* adj, int* deg, int n, int init, int n_rounds, int* labels, int* centres, int* sizes,
                        int* state, unsigned long long* live_ws, unsigned long long* members_ws, void* stream);
 
+/* ---- Contacts on CA atoms: the contact map of an ensemble, contact order, and the fraction of native contacts Q
+ * (csrc/ensemble_contacts.hip; no counterpart in the reference) ----
+ * Coordinates are CA atoms [., n_res, 3] float32, residue i of one structure matched to residue i of another (the identity correspondence).
+ * All arithmetic is float64, one rounding per operation (no contraction).  For residues i < j of one structure
+ *   v(i, j) = (dx dx + dy dy) + dz dz,  the differences formed in float64 from the widened coordinates.
+ *  Contact.  (i, j) with j - i >= min_seq_sep is a contact iff v < cutoff^2: squared form, no square root decides a contact.  A comparison
+ *     with NaN is false.  The usual choice is cutoff = 8.0 A, min_seq_sep = 3.
+ *  Contact map of n structures.  counts[i, j] = counts[j, i] = the number of structures in which (i, j) is a contact, int32;
+ *     weighted[i, j] = weighted[j, i] = sum over the structures r, in ASCENDING r, of weights[r] [contact_r(i, j)], float64.  Both are 0
+ *     inside the band |i - j| < min_seq_sep.  The probability P = counts / n, or weighted / sum of the weights, is the caller's one division.
+ *  Per-structure statistics.  n_contacts[r] int32; sep_sum[r] = the sum of (j - i) over its contacts, int64.  The relative contact order
+ *     (Plaxco, Simons and Baker 1998) is sep_sum / (n_res n_contacts), 0.0 for a structure without contacts: the caller forms it from the
+ *     two integers.
+ *  Native contact list of one structure.  All (i, j), j - i >= min_seq_sep, with v0 < native_cutoff^2, and d0 = sqrt(v0), in ascending
+ *     (i, j) order.  Best, Hummer and Eaton (2013) take |i - j| > 3, i.e. min_seq_sep = 4.
+ *  Q of a structure against a list of n entries.
+ *     hard:  hits = #{entries : v < (lam d0)^2},  Q = hits / n                  (integer hits, one division; (lam d0)^2 is formed once per entry)
+ *     soft:  Q = (1 / n) sum over the entries of 1 / (1 + exp(beta (sqrt(v) - lam d0)))        (Best, Hummer and Eaton 2013)
+ *     Their values are beta = 5 / A and lam = 1.2, the lam they give for coarse-grained CA models (1.8 is their all-atom value).  Under the
+ *     soft form the native scores slightly BELOW 1 against itself: every term is 1 / (1 + exp(-beta (lam - 1) d0)) < 1.  n = 0 gives 1.0 in
+ *     both forms (the convention of the lDDT section for an empty set; it covers n_res <= min_seq_sep).  A structure with a NaN coordinate
+ *     in an entry misses the hit and has a NaN soft Q.
+ *     The soft sum is formed in an order that depends on n and on the kernel's fixed block shape alone: thread t of 256 adds the entries
+ *     t, t + 256, ... in ascending order, the 64 lanes of a wave meet in an xor tree, the four waves are added in turn.  A structure's Q is
+ *     therefore bit for bit the same in any launch.
+ * Limits: n_res <= S2S_CONTACT_MAX_RES; CA atoms only (no CB or all-atom contacts), one sequence, no per-residue Q. */
+#define S2S_CONTACT_MAX_RES 1024          /* a tile of 8 structures of the Q kernel stays in LDS as float32: 96 B per residue */
+#define S2S_CONTACT_MAX_STRUCTURES 65535  /* structures per s2s_ca_contact_map call (the binding walks longer ensembles in such runs) */
+#define S2S_CONTACT_LIST_SLOTS(n_res) ((long long)(n_res) > 1 ? (long long)(n_res) * ((long long)(n_res) - 1) / 2 : 1)
+
+/* ca [n, n_res, 3] -> ADDS into counts [n_res, n_res] int32 and, with weights [n] float64 (NULL: none; then weighted must be NULL too),
+ * into weighted [n_res, n_res] float64; the caller zeroes both before the first call of a map.  The upper triangle is accumulated and then
+ * copied over the lower one.  Without weights the structures are split over workgroups that meet in int32 atomics.  With weights every
+ * pair's sum is continued by one thread from the value the buffer holds, in ascending structure order: calls over consecutive runs of
+ * structures of an ensemble give bit for bit the sum of one call.  1 <= n <= S2S_CONTACT_MAX_STRUCTURES, 1 <= n_res <=
+ * S2S_CONTACT_MAX_RES, cutoff positive and finite, min_seq_sep >= 1; otherwise hipErrorInvalidValue before any launch. */
+int s2s_ca_contact_map(const float* ca, int n, int n_res, double cutoff, int min_seq_sep, const double* weights, int* counts,
+                       double* weighted, void* stream);
+
+/* ca [n, n_res, 3] -> n_contacts [n] int32, sep_sum [n] int64.  No scratch.  The checks of s2s_ca_contact_map, without its limit on n. */
+int s2s_ca_contact_stats(const float* ca, int n, int n_res, double cutoff, int min_seq_sep, int* n_contacts, long long* sep_sum,
+                         void* stream);
+
+/* native [n_res, 3] -> pairs [slots, 2] int32 (i, j) and d0 [slots] float64, slots >= S2S_CONTACT_LIST_SLOTS(n_res), caller-owned; the
+ * first *n_pairs entries are the list, *n_pairs (device memory) is written by the kernel.  The same checks. */
+int s2s_ca_native_contacts(const float* native, int n_res, double cutoff, int min_seq_sep, int* pairs, double* d0, int* n_pairs,
+                           void* stream);
+
+/* ca [n, n_res, 3] against the first n_pairs entries of (pairs, d0) -> q_soft [n], q_hard [n] float64 and hits [n] int32.  beta and lam
+ * positive and finite, 0 <= n_pairs <= S2S_CONTACT_LIST_SLOTS(n_res); an entry with an index outside 0 .. n_res - 1 is skipped. */
+int s2s_ca_native_q(const float* ca, int n, int n_res, const int* pairs, const double* d0, int n_pairs, double beta, double lam,
+                    double* q_soft, double* q_hard, int* hits, void* stream);
+
 /* ---- PDB text at the exit of the path (HOST pointers, host code; byte-identical to the reference's writers) ---- */
 
 /* protein.to_pdb per model (src/common/protein.py:152-234) over atom37 [n_models, n_res, 37, 3] float32 HOST coordinates with

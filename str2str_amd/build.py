@@ -35,6 +35,9 @@ UNITS = {
     "ensemble_tm.hip": [],     # (as above)
     "ensemble_cluster.hip": [],   # integer and float64 comparisons only
     "ensemble_lddt.hip": [],      # float64 distances against squared bounds, integer sums
+    # contraction off: the argument of the soft Q's exponential is then bit for bit the numpy yardstick's, so the a-priori bound of its
+    # test needs exp, one addition and one division only (the integer outputs are safe either way: the cases' margins are >= 1e-9 relative)
+    "ensemble_contacts.hip": ["-ffp-contract=off"],
     "ensemble_violations.hip": ["-ffp-contract=off"],   # every float64 term rounds like the numpy yardstick's
     "ensemble_ss.hip": ["-ffp-contract=off"],           # (as above: energies and cosines decide letters)
     # the MFMA chains are fully unrolled on purpose (accumulator tiles must be statically indexed)

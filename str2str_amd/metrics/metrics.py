@@ -24,7 +24,9 @@ other; ``backbone_violations`` (csrc/ensemble_violations.hip) looks inside each 
 terms (src/models/loss.py:714-1017, 1237-1314) on the full backbone the sampler writes, with ``backbone_validity`` and ``violation_rate``
 as its dict-in / dict-out companions.  What a conformation is: ``secondary_structure`` (csrc/ensemble_ss.hip) assigns Kabsch & Sander's
 eight states from the backbone hydrogen bonds and ``backbone_torsions`` gives phi, psi, omega; ``ss_propensity``, ``ss_content``,
-``ss_mae`` and ``js_rama`` are the ensemble summaries built on them.
+``ss_mae`` and ``js_rama`` are the ensemble summaries built on them.  Which residues touch: ``contact_map``, ``contact_order``,
+``native_contacts`` and ``fraction_native_contacts`` (csrc/ensemble_contacts.hip: CA contacts by squared float64 distances; the hard Q and
+the soft Q of Best, Hummer and Eaton 2013), with ``contact_mae``, ``js_q`` and ``mean_q`` as the ensemble-against-reference summaries.
 """
 from __future__ import annotations
 
@@ -346,6 +348,87 @@ def coverage_lddt(ca_coords_dict, ref_key="target", chunk_pairs=None):
     references: recall[k] = mean over reference frames of the best lDDT any sample of k reaches in that frame's environment, precision[k]
     = mean over samples of k of its best lDDT in any reference frame's environment (higher is better; the reference's own entries are 1.0)."""
     return _coverage(LDDT, ca_coords_dict, ref_key, chunk_pairs)
+
+
+# ---- contacts: which residues touch (csrc/ensemble_contacts.hip; CA atoms, the identity correspondence) -----------------------------------
+def contact_map(coords, cutoff=8.0, min_seq_sep=3, weights=None) -> np.ndarray:
+    """The contact-probability map of the ensemble ``coords`` [R, L, 3] -> float64 [L, L], symmetric: the fraction of structures (with
+    per-structure ``weights`` [R]: of their weight) in which residues i and j, at least ``min_seq_sep`` apart in sequence, have CA atoms
+    closer than ``cutoff`` A.  0 inside the band |i - j| < min_seq_sep."""
+    n = len(coords) if np.ndim(coords) == 3 else 1
+    if weights is None:
+        return ops.ca_contact_map(_dev(coords), cutoff, min_seq_sep)[0].cpu().numpy() / float(n)
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape != (n,):
+        raise ValueError(f"weights has shape {w.shape} for {n} structures")
+    return ops.ca_contact_map(_dev(coords), cutoff, min_seq_sep, torch.as_tensor(w, device="cuda"))[1].cpu().numpy() / w.sum()
+
+
+def contact_order(coords, cutoff=8.0, min_seq_sep=3) -> np.ndarray:
+    """The relative contact order (Plaxco, Simons and Baker 1998) of every structure of ``coords`` [R, L, 3] -> float64 [R]: the mean
+    sequence separation of its contacts over the chain length, 0.0 for a structure without contacts."""
+    x = _dev(coords)
+    n, sep_sum = (t.cpu().numpy() for t in ops.ca_contact_stats(x, cutoff, min_seq_sep))
+    return np.where(n > 0, sep_sum.astype(np.float64) / (float(x.shape[1]) * np.maximum(n, 1)), 0.0)
+
+
+def native_contacts(native, cutoff=8.0, min_seq_sep=4):
+    """The native contact list of ``native`` [L, 3] -> (pairs [n, 2] int32 in ascending (i, j) order, d0 [n] float64: their distances).
+    The defaults are those of Best, Hummer and Eaton (2013) on CA atoms: closer than 8 A, |i - j| > 3."""
+    if np.ndim(native) != 2:
+        raise ValueError(f"native has shape {np.shape(native)}, expected [L, 3]")
+    pairs, d0 = ops.ca_native_contacts(_dev(native)[0], cutoff, min_seq_sep)
+    return pairs.cpu().numpy(), d0.cpu().numpy()
+
+
+def fraction_native_contacts(coords, native, soft=True, beta=5.0, lam=1.2, cutoff=8.0, min_seq_sep=4) -> np.ndarray:
+    """Q of every structure of ``coords`` [R, L, 3] against the native contacts of ``native`` [L, 3] -> float64 [R].  ``soft``: the mean
+    over the native contacts of 1 / (1 + exp(beta (d - lam d0))) (Best, Hummer and Eaton 2013; beta = 5 / A and lam = 1.2 are their
+    values for CA models -- the native itself then scores slightly below 1); otherwise the fraction with d < lam d0.  1.0 when the native
+    has no contact."""
+    if np.ndim(native) != 2:
+        raise ValueError(f"native has shape {np.shape(native)}, expected [L, 3]")
+    x, nat = _dev(coords), _dev(native)[0]
+    if nat.shape[0] != x.shape[1]:
+        raise ValueError(f"native has {nat.shape[0]} residues for the ensemble's {x.shape[1]}")
+    q_soft, q_hard, _ = ops.ca_native_q(x, *ops.ca_native_contacts(nat, cutoff, min_seq_sep), beta, lam)
+    return (q_soft if soft else q_hard).cpu().numpy()
+
+
+def contact_mae(ca_coords_dict, ref_key="target", cutoff=8.0, min_seq_sep=3, weights=None):
+    """The mean absolute difference of each ensemble's contact-probability map from the reference ensemble's, over the pairs at least
+    ``min_seq_sep`` apart (0.0 when there is none).  ``weights``: per-structure weights by key, as in ``js_pwd``."""
+    w = _weights(weights, ca_coords_dict) if weights else {}
+    maps = {k: contact_map(v, cutoff, min_seq_sep, w.get(k)) for k, v in ca_coords_dict.items()}
+    upper = np.triu_indices(maps[ref_key].shape[0], k=min_seq_sep)
+    out = {k: np.around(float(np.abs(m[upper] - maps[ref_key][upper]).mean()) if len(upper[0]) else 0.0, decimals=4)
+           for k, m in maps.items() if k != ref_key}
+    out[ref_key] = 0.0
+    return out
+
+
+def _q_by_key(ca_coords_dict, ref_key, native, **q_args):
+    """Q of every ensemble against ``native`` (None: the first structure of the reference ensemble) -> {k: float64 [len(v)]}."""
+    native = ca_coords_dict[ref_key][0] if native is None else native
+    return {k: fraction_native_contacts(v, native, **q_args) for k, v in ca_coords_dict.items()}
+
+
+def js_q(ca_coords_dict, ref_key="target", native=None, n_bins=50, weights=None, **q_args):
+    """The Jensen-Shannon distance between each ensemble's distribution of the fraction of native contacts and the reference ensemble's:
+    histograms of ``n_bins`` bins over the fixed range [0, 1].  ``native`` [L, 3]: None takes the first structure of the reference
+    ensemble; ``q_args``: the arguments of ``fraction_native_contacts``."""
+    w = _weights(weights, ca_coords_dict)
+    q = _q_by_key(ca_coords_dict, ref_key, native, **q_args)
+    binned = {k: np.histogram(v, bins=n_bins, weights=w[k], range=(0.0, 1.0))[0] + PSEUDO_C for k, v in q.items()}
+    out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
+    out[ref_key] = 0.0
+    return out
+
+
+def mean_q(ca_coords_dict, ref_key="target", native=None, weights=None, **q_args):
+    """The (weighted) mean fraction of native contacts of each ensemble; the arguments of ``js_q``."""
+    w = _weights(weights, ca_coords_dict)
+    return {k: np.around(float(np.average(v, weights=w[k])), decimals=4) for k, v in _q_by_key(ca_coords_dict, ref_key, native, **q_args).items()}
 
 
 # ---- backbone violations: inside each structure (csrc/ensemble_violations.hip; the definition of src/models/loss.py:714-1017, 1237-1314) ----

@@ -7,7 +7,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # str2str_amd/: where build.py links the library
 LIB_PATH = os.environ.get("STR2STR_HIP_LIB") or os.path.join(_PKG, "libstr2str_hip.so")  # env override: A/B builds
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 _lib = None   # rebound by load_library: read it through that function only
 
@@ -52,6 +52,10 @@ _SIGNATURES = {
     "s2s_ca_tm_superpose": [_vp, _i, _vp, _i, _d, _vp, _vp, _vp],
     "s2s_ca_lddt_matrix": [_vp, _i, _vp, _i, _i, _d, _i, _vp, _vp, _ll, _vp],
     "s2s_ca_lddt_per_residue": [_vp, _i, _vp, _i, _d, _i, _vp, _vp, _vp, _ll, _vp],
+    "s2s_ca_contact_map": [_vp, _i, _i, _d, _i, _vp, _vp, _vp, _vp],
+    "s2s_ca_contact_stats": [_vp, _i, _i, _d, _i, _vp, _vp, _vp],
+    "s2s_ca_native_contacts": [_vp, _i, _d, _i, _vp, _vp, _vp, _vp],
+    "s2s_ca_native_q": [_vp, _i, _i, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp],
     "s2s_backbone_violations": [_vp, _i, _i, _vp, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "s2s_secondary_structure": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "s2s_cluster_adjacency": [_vp, _i, _i, _i, _d, _i, _vp, _vp, _vp],

@@ -1,5 +1,5 @@
 """Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition, lDDT, clustering,
-backbone violations, secondary structure and torsions."""
+backbone violations, secondary structure and torsions, contact maps and the fraction of native contacts."""
 from typing import Optional
 
 import torch
@@ -15,6 +15,8 @@ VIOL_MAX_RES = 1024               # S2S_VIOL_MAX_RES: the chain length whose ato
 VIOL_MAX_STRUCTURES = 1 << 20     # structures per s2s_backbone_violations launch, unless max_structures says less
 SS_MAX_RES = 704                  # S2S_SS_MAX_RES: the chain length whose atoms and bond relation fit the LDS of s2s_secondary_structure
 SS_MAX_STRUCTURES = 1 << 20       # structures per s2s_secondary_structure launch, unless max_structures says less
+CONTACT_MAX_RES = 1024            # S2S_CONTACT_MAX_RES: the chain length whose tile of structures fits the LDS of s2s_ca_native_q
+CONTACT_LAUNCH_STRUCTURES = 65535  # S2S_CONTACT_MAX_STRUCTURES: structures per launch of the contact kernels
 CLUSTER_MAX_N = 65536             # S2S_CLUSTER_MAX_N: structures per clustering (512 MB of neighbour bits)
 CLUSTER_ROUNDS_PER_SYNC = 32      # rounds of the greedy loop enqueued between two readbacks of its state
 
@@ -268,6 +270,101 @@ def ca_lddt_per_residue(model: torch.Tensor, target: torch.Tensor, cutoff: float
     _check(lib.s2s_ca_lddt_per_residue(_p(model), R, _p(target), L, cutoff, min_seq_sep, _p(per_res), _p(total), _p(ws), ws.numel() * 8,
                                        _stream()), "s2s_ca_lddt_per_residue")
     return per_res, total
+
+
+def _contact_args(what: str, L: int, min_seq_sep=None, **positive):
+    """The parameters of a contact function ``what`` on chains of ``L`` residues, checked -> the ``positive`` ones as floats, in order,
+    then ``min_seq_sep`` (unless None) as an int."""
+    out = []
+    for name, v in positive.items():
+        v = float(v)
+        if not 0.0 < v < float("inf"):
+            raise HipLibraryError(f"{what}: {name} must be positive and finite, got {v}")
+        out.append(v)
+    if min_seq_sep is not None:
+        if isinstance(min_seq_sep, bool) or int(min_seq_sep) != min_seq_sep or min_seq_sep < 1:
+            raise HipLibraryError(f"{what}: min_seq_sep must be an integer >= 1, got {min_seq_sep}")
+        out.append(int(min_seq_sep))
+    if L > CONTACT_MAX_RES:
+        raise HipLibraryError(f"{what}: at most {CONTACT_MAX_RES} residues, got {L}")
+    return out
+
+
+def ca_contact_map(ca: torch.Tensor, cutoff: float = 8.0, min_seq_sep: int = 3, weights: Optional[torch.Tensor] = None):
+    """The contact map of the ensemble ca [R, L, 3] (fp32 device tensor; include/str2str_hip.h: residues at least ``min_seq_sep`` apart in
+    sequence whose squared CA distance, in float64, is below ``cutoff``^2) -> (counts [L, L] int32: the structures in which each pair is a
+    contact, symmetric, zero inside the band; weighted [L, L] fp64, or None without ``weights``: the sum of ``weights`` [R] (fp64 device
+    tensor) over those structures, in ascending structure order).  The contact probability is ``counts / R`` or ``weighted /
+    weights.sum()``.  R is walked in launches of CONTACT_LAUNCH_STRUCTURES; both results are bit for bit the same for any such size."""
+    ca, _, R, L, _ = _ensemble_pair("ca_contact_map", ca, None, on_device=False)
+    cutoff, min_seq_sep = _contact_args("ca_contact_map", L, min_seq_sep, cutoff=cutoff)
+    if weights is not None and (not isinstance(weights, torch.Tensor) or weights.shape != (R,)):
+        raise HipLibraryError(f"ca_contact_map: weights {tuple(getattr(weights, 'shape', ()))} for {R} structures")
+    _req(ca, name="ca")
+    if weights is not None:
+        _req(weights, torch.float64, "weights")
+    counts = torch.zeros(L, L, dtype=torch.int32, device=ca.device)
+    weighted = None if weights is None else torch.zeros(L, L, dtype=torch.float64, device=ca.device)
+    lib = load_library()
+    for n, p_ca, *p_w in _row_chunks(R, CONTACT_LAUNCH_STRUCTURES, ca, *(() if weights is None else (weights,))):
+        _check(lib.s2s_ca_contact_map(p_ca, n, L, cutoff, min_seq_sep, p_w[0] if p_w else None, _p(counts), _p(weighted), _stream()),
+               "s2s_ca_contact_map")
+    return counts, weighted
+
+
+def ca_contact_stats(ca: torch.Tensor, cutoff: float = 8.0, min_seq_sep: int = 3):
+    """Per structure of ca [R, L, 3] (fp32 device tensor) -> (n_contacts [R] int32; sep_sum [R] int64: the sum of j - i over its contacts).
+    The relative contact order is ``sep_sum / (L * n_contacts)``, 0.0 for a structure without contacts."""
+    ca, _, R, L, _ = _ensemble_pair("ca_contact_stats", ca, None, on_device=False)
+    cutoff, min_seq_sep = _contact_args("ca_contact_stats", L, min_seq_sep, cutoff=cutoff)
+    _req(ca, name="ca")
+    n_contacts = torch.empty(R, dtype=torch.int32, device=ca.device)
+    sep_sum = torch.empty(R, dtype=torch.int64, device=ca.device)
+    lib = load_library()
+    for n, p_ca, *p_out in _row_chunks(R, CONTACT_LAUNCH_STRUCTURES, ca, n_contacts, sep_sum):
+        _check(lib.s2s_ca_contact_stats(p_ca, n, L, cutoff, min_seq_sep, *p_out, _stream()), "s2s_ca_contact_stats")
+    return n_contacts, sep_sum
+
+
+def ca_native_contacts(native: torch.Tensor, cutoff: float = 8.0, min_seq_sep: int = 4):
+    """The native contact list of native [L, 3] (fp32 device tensor) -> (pairs [n, 2] int32: (i, j) with j - i >= ``min_seq_sep`` closer
+    than ``cutoff``, in ascending (i, j) order; d0 [n] fp64: their distances).  Reads the length of the list back from the device."""
+    if not isinstance(native, torch.Tensor):
+        raise HipLibraryError(f"ca_native_contacts: expected a tensor, got {type(native).__name__}")
+    if native.ndim != 2 or native.shape[1] != 3 or native.shape[0] < 1:
+        raise HipLibraryError(f"ca_native_contacts: native {tuple(native.shape)}, expected [L, 3]")
+    L = native.shape[0]
+    cutoff, min_seq_sep = _contact_args("ca_native_contacts", L, min_seq_sep, cutoff=cutoff)
+    _req(native, name="native")
+    slots = max(1, L * (L - 1) // 2)                           # S2S_CONTACT_LIST_SLOTS
+    pairs = torch.empty(slots, 2, dtype=torch.int32, device=native.device)
+    d0 = torch.empty(slots, dtype=torch.float64, device=native.device)
+    n = torch.zeros(1, dtype=torch.int32, device=native.device)
+    _check(load_library().s2s_ca_native_contacts(_p(native), L, cutoff, min_seq_sep, _p(pairs), _p(d0), _p(n), _stream()), "s2s_ca_native_contacts")
+    n = int(n.item())
+    return pairs[:n].clone(), d0[:n].clone()
+
+
+def ca_native_q(ca: torch.Tensor, pairs: torch.Tensor, d0: torch.Tensor, beta: float = 5.0, lam: float = 1.2):
+    """The fraction of native contacts of every structure of ca [R, L, 3] (fp32 device tensor) against the list (pairs [n, 2] int32, d0 [n]
+    fp64) of ``ca_native_contacts`` -> (q_soft [R] fp64: the mean of 1 / (1 + exp(beta (d - lam d0))), Best, Hummer and Eaton 2013; q_hard
+    [R] fp64: hits / n; hits [R] int32: the entries with d < lam d0).  An empty list gives 1.0.  A structure's values are bit for bit the
+    same in any launch."""
+    ca, _, R, L, _ = _ensemble_pair("ca_native_q", ca, None, on_device=False)
+    beta, lam = _contact_args("ca_native_q", L, beta=beta, lam=lam)
+    if not (isinstance(pairs, torch.Tensor) and isinstance(d0, torch.Tensor)) or pairs.ndim != 2 or pairs.shape[1] != 2 or d0.shape != pairs.shape[:1]:
+        raise HipLibraryError(f"ca_native_q: pairs {tuple(getattr(pairs, 'shape', ()))} and d0 {tuple(getattr(d0, 'shape', ()))}, expected [n, 2] and [n]")
+    n_pairs = pairs.shape[0]
+    if n_pairs > max(1, L * (L - 1) // 2):
+        raise HipLibraryError(f"ca_native_q: {n_pairs} entries for a chain of {L} residues")
+    _req(ca, name="ca"); _req(pairs, torch.int32, "pairs"); _req(d0, torch.float64, "d0")
+    q_soft, q_hard = (torch.empty(R, dtype=torch.float64, device=ca.device) for _ in range(2))
+    hits = torch.empty(R, dtype=torch.int32, device=ca.device)
+    lib = load_library()
+    for n, p_ca, *p_out in _row_chunks(R, CONTACT_LAUNCH_STRUCTURES, ca, q_soft, q_hard, hits):
+        _check(lib.s2s_ca_native_q(p_ca, n, L, _p(pairs) if n_pairs else None, _p(d0) if n_pairs else None, n_pairs, beta, lam, *p_out, _stream()),
+               "s2s_ca_native_q")
+    return q_soft, q_hard, hits
 
 
 def _viol_small(what: str, v, shape, dtype, fn: str = "backbone_violations") -> torch.Tensor:
