@@ -11,7 +11,10 @@ into the reference's tab-separated ``metrics_<tag>_<mmdd-HH-MM>.csv``.  ``+clust
 per-residue propensities ``secondary_structure/<target>.csv``.
 ``+contacts=true`` also computes the CA contacts of the sampled and the target ensembles (on the device) and writes
 ``contacts_<tag>_<mmdd-HH-MM>.csv`` (mean fraction of native contacts Q of both, the JS distance of their Q distributions, the mean
-absolute difference of their contact maps, mean relative contact order of both) and the contact probabilities ``contacts/<target>.csv``."""
+absolute difference of their contact maps, mean relative contact order of both) and the contact probabilities ``contacts/<target>.csv``.
+``+sasa=true`` also computes the solvent-accessible surface of the backbone and CB atoms of the sampled and the target ensembles (on the
+device; no side chains) and writes ``sasa_<tag>_<mmdd-HH-MM>.csv`` (mean total surface of both, the JS distance of their distributions, the
+mean absolute difference of their per-residue relative accessibilities) and the per-residue means ``sasa/<target>.csv``."""
 import logging
 import os
 import sys
@@ -120,6 +123,43 @@ def contacts_row(ca):
     return row, {"i": i, "j": j, "p_pred": np.around(p["pred"][i, j], decimals=4), "p_target": np.around(p["target"][i, j], decimals=4)}
 
 
+SASA_COLUMNS = ("sasa_mean", "sasa_mean_target", "js_sasa", "sasa_mae")
+
+
+def sasa_switch(value) -> bool:
+    """``+sasa=...`` as a bool: absent, null and false leave everything as it was."""
+    return _switch("sasa", value)
+
+
+def sasa_row(pred_file, target_file, log=log):
+    """One row of the sasa csv (SASA_COLUMNS) and the per-residue means {"pred": (sasa [L], relative [L]), "target": the same or None} of
+    one target.  A target without a full backbone (a CA trace) leaves NaN in the columns that need it."""
+    import numpy as np
+
+    from str2str_amd.common.pdb_utils import extract_backbone_atoms
+    from str2str_amd.metrics import metrics
+
+    atoms, aatype, residue_index = extract_backbone_atoms(pred_file)
+    both = {"pred": atoms}
+    try:
+        t_atoms, _, _ = extract_backbone_atoms(target_file)
+        if t_atoms.shape[1] != atoms.shape[1]:
+            raise ValueError(f"{t_atoms.shape[1]} residues for the samples' {atoms.shape[1]}")
+        both["target"] = t_atoms
+    except ValueError as e:
+        log.warning(f"solvent accessibility of the target {target_file}: {e}")
+    row = dict.fromkeys(SASA_COLUMNS, float("nan"))
+    per_res = {k: (metrics.solvent_accessibility(v, aatype, residue_index).per_residue.mean(0),
+                   metrics.relative_accessibility(v, aatype, residue_index).mean(0)) for k, v in both.items()}
+    mean = metrics.mean_sasa(both, aatype, residue_index)
+    row["sasa_mean"] = mean["pred"]
+    if "target" in both:
+        row["sasa_mean_target"] = mean["target"]
+        row["js_sasa"] = metrics.js_sasa(both, ref_key="target", aatype=aatype, residue_index=residue_index)["pred"]
+        row["sasa_mae"] = np.around(float(np.abs(per_res["pred"][1] - per_res["target"][1]).mean()), decimals=4)
+    return row, {"pred": per_res["pred"], "target": per_res.get("target")}, residue_index
+
+
 def secondary_structure_row(pred_file, target_file, log=log):
     """One row of the ss csv (SS_COLUMNS) and the per-residue propensities {"pred": [L, 3], "target": [L, 3] or None} of one target.  A
     target without a full backbone (a CA trace) leaves NaN in the columns that need it."""
@@ -148,7 +188,7 @@ def secondary_structure_row(pred_file, target_file, log=log):
 
 
 def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None, cluster_cutoff=None,
-                        secondary_structure=None, contacts=None):
+                        secondary_structure=None, contacts=None, sasa=None):
     """reference src/eval.py:47-99: one row per target, one column per metric, plus the mean row.  ``extra_metrics``: names out of
     EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's).
     ``cluster_cutoff`` (A; None: nothing of this happens): the ``pred`` ensemble of every target is clustered by ``metrics.cluster_rmsd``;
@@ -157,10 +197,13 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     states of the ``pred`` and the ``target`` ensemble of every target; ``ss_<tag>_<mmdd-HH-MM>.csv`` receives one row per target
     (SS_COLUMNS) and ``secondary_structure/<target>.csv`` the per-residue propensities of both.  ``contacts`` (true; otherwise nothing of
     this happens): ``contacts_<tag>_<mmdd-HH-MM>.csv`` receives one row per target (CONTACT_COLUMNS) and the mean row, and
-    ``contacts/<target>.csv`` the contact probabilities of both ensembles."""
+    ``contacts/<target>.csv`` the contact probabilities of both ensembles.  ``sasa`` (true; otherwise nothing of this happens):
+    ``sasa_<tag>_<mmdd-HH-MM>.csv`` receives one row per target (SASA_COLUMNS) and the mean row, and ``sasa/<target>.csv`` the per-residue
+    mean surface and mean relative accessibility of both ensembles."""
     columns = metric_columns(extra_metrics)
     secondary_structure = secondary_structure_switch(secondary_structure)
     contacts = contacts_switch(contacts)
+    sasa = sasa_switch(sasa)
     if cluster_cutoff is not None and not 0.0 < float(cluster_cutoff) < float("inf"):
         raise ValueError(f"cluster_cutoff {cluster_cutoff}: expected a positive finite RMSD in Angstrom")
     from time import strftime
@@ -183,7 +226,7 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
            "div_rmsd": metrics.diversity_rmsd, "div_tm": metrics.diversity_tm, "div_lddt": metrics.diversity_lddt}
     coverage = {"rmsd": metrics.coverage_rmsd, "tm": metrics.coverage_tm, "lddt": metrics.coverage_lddt}
     eval_res = {k: {} for k in columns}
-    clusters, ss_rows, contact_rows = {}, {}, {}
+    clusters, ss_rows, contact_rows, sasa_rows = {}, {}, {}, {}
     for target in targets:
         pred_file = os.path.join(pred_dir, f"{target}.pdb")
         if not os.path.isfile(pred_file):
@@ -225,6 +268,14 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
             contact_rows[target], table = contacts_row(ca)
             os.makedirs(os.path.join(output_dir, "contacts"), exist_ok=True)
             pd.DataFrame(table).to_csv(os.path.join(output_dir, "contacts", f"{target}.csv"), index=False, sep="\t")
+        if sasa:
+            sasa_rows[target], per_res, numbers = sasa_row(pred_file, os.path.join(target_dir, f"{target}.pdb"))
+            table = {"residue_index": numbers}
+            for k in ("pred", "target"):
+                for q, c in enumerate(("sasa", "relative")):
+                    table[f"{k}_{c}"] = np.full(len(numbers), np.nan) if per_res[k] is None else np.around(per_res[k][q], decimals=4)
+            os.makedirs(os.path.join(output_dir, "sasa"), exist_ok=True)
+            pd.DataFrame(table).to_csv(os.path.join(output_dir, "sasa", f"{target}.csv"), index=False, sep="\t")
     df = pd.DataFrame.from_dict(eval_res)
     df.loc["mean"] = np.around(df.mean(), decimals=4)
     df.to_csv(os.path.join(output_dir, f"metrics_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
@@ -238,6 +289,10 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
         cf = pd.DataFrame.from_dict(contact_rows, orient="index", columns=list(CONTACT_COLUMNS))
         cf.loc["mean"] = np.around(cf.mean(), decimals=4)
         cf.to_csv(os.path.join(output_dir, f"contacts_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
+    if sasa:
+        sf = pd.DataFrame.from_dict(sasa_rows, orient="index", columns=list(SASA_COLUMNS))
+        sf.loc["mean"] = np.around(sf.mean(), decimals=4)
+        sf.to_csv(os.path.join(output_dir, f"sasa_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
     return df.loc["mean"]
 
 
@@ -245,7 +300,7 @@ def evaluate(cfg):
     pred_dir = cfg.get("pred_dir")
     scoring = dict(target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"), extra_metrics=cfg.get("extra_metrics"),
                    cluster_cutoff=cfg.get("cluster_cutoff"), secondary_structure=cfg.get("secondary_structure"),
-                   contacts=cfg.get("contacts"))
+                   contacts=cfg.get("contacts"), sasa=cfg.get("sasa"))
     if pred_dir and os.path.isdir(pred_dir):
         log.info(f"Found pre-computed prediction directory {pred_dir}.")
         return evaluate_prediction(pred_dir, **scoring)

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-/* Library ABI version (bumped on any signature change). */
+/* Library ABI version (bumped on any signature change).  Still 40 with s2s_backbone_sasa: an entry point was added, no signature changed. */
 int s2s_abi_version(void);
 
 /* Arithmetic.  Every matrix product of the path exists in two forms behind the same operator contract:
@@ -632,6 +632,38 @@ int s2s_ca_native_contacts(const float* native, int n_res, double cutoff, int mi
  * positive and finite, 0 <= n_pairs <= S2S_CONTACT_LIST_SLOTS(n_res); an entry with an index outside 0 .. n_res - 1 is skipped. */
 int s2s_ca_native_q(const float* ca, int n, int n_res, const int* pairs, const double* d0, int n_pairs, double beta, double lam,
                     double* q_soft, double* q_hard, int* hits, void* stream);
+
+/* ---- Solvent accessibility: how much of each residue, and of the chain, is exposed?  (csrc/ensemble_sasa.hip; the point test of Shrake and
+ * Rupley, J. Mol. Biol. 79 (1973) 351; no counterpart in the reference.  It is the ACC column the secondary-structure section leaves out) ----
+ * Per structure of atoms [n, n_res, 5, 3] (atom14 slots N, CA, C, O, CB), with atom_exists [n_res, 5] (bytes, != 0: the atom exists; GLY has
+ * no CB) and radii [n_res, 5] float64 (van der Waals radii in Angstrom, the caller's) shared by the n structures.  An atom that does not
+ * exist has no surface and buries nothing, whatever its coordinates and its radius.
+ *  Expanded radius.  R_a = radii_a + probe, one float64 addition; probe >= 0 is the radius of the solvent sphere (1.4 A for water).
+ *  Sphere.  sphere [n_points, 3] float64 unit vectors, built by the HOST and read as they are: no sine or cosine runs on the device, so the
+ *     device and a numpy statement of this definition see the same bits.  The binding's table is the golden spiral, for k = 0 .. P - 1:
+ *       y = (k (2 / P) - 1) + 1 / P,  r = sqrt(1 - y y),  phi = k (pi (3 - sqrt 5)),  u_k = (cos(phi) r, y, sin(phi) r).
+ *  Test point.  p = c_a + R_a u_k per component: the product is rounded, then the sum.  c are the widened float32 coordinates.
+ *  Buried.  The point is buried iff some existing atom b != a has (dx dx + dy dy) + dz dz < R_b R_b with d = p - c_b.  Every atom of the
+ *     structure counts, those of the point's own residue included.  A comparison with NaN is false.
+ *  Outputs.  counts[., r, a] int32 = the points of the atom that are not buried, 0 for an atom that does not exist.
+ *     per_residue[., r] float64 in A^2: area_a = (double)count_a w_a with w_a = 4.0 pi R_a R_a / P evaluated left to right (area_a = 0.0 for
+ *     an atom that does not exist), summed in slot order (((a0 + a1) + a2) + a3) + a4.
+ *     total[.] float64 = the residues' areas, summed in an order that depends on n_res and on the kernel's fixed block shape alone: thread t
+ *     of T (512 up to 256 residues, 1024 above) adds the residues t, t + T, ... in ascending order, the 64 lanes of a wave meet in an xor
+ *     tree, the waves are added in turn.
+ * Arithmetic: everything is float64, one rounding per operation (no contraction).  A wave tests an atom's points only against the atoms
+ * with |c_a - c_b|^2 < ((R_a + R_b)(1 + 2^-30) + 2^-30 (1 + M))^2, M = the largest |coordinate| of the structure's existing atoms: an atom
+ * that fails cannot bury a point under any rounding (the roundings of the point and of the test are 2^20 times smaller than the slack), so
+ * no output depends on this.  A structure's outputs depend on its own coordinates alone: bit for bit the same in any launch.
+ * What this is NOT: an all-atom surface.  There are no side chains beyond CB, so absolute values overstate the exposure of large residues,
+ * and no relative accessibility against tabulated Gly-X-Gly maxima is formed (no such table is in the tree).  No gradients. */
+#define S2S_SASA_MAX_RES 512      /* the structure's atoms stay in LDS as float64 planes with radius and area: 220 B per residue */
+#define S2S_SASA_MAX_POINTS 1024  /* the sphere stays in LDS as float64 planes, 24 KiB; a lane of a wave owns 16 points of an atom */
+
+/* No scratch.  n >= 1, 1 <= n_res <= S2S_SASA_MAX_RES, 1 <= n_points <= S2S_SASA_MAX_POINTS, probe finite and >= 0, no NULL buffer;
+ * otherwise hipErrorInvalidValue before any launch.  counts [n, n_res, 5] int, per_residue [n, n_res] and total [n] float64. */
+int s2s_backbone_sasa(const float* atoms, int n, int n_res, const unsigned char* atom_exists, const double* radii, double probe,
+                      const double* sphere, int n_points, int* counts, double* per_residue, double* total, void* stream);
 
 /* ---- PDB text at the exit of the path (HOST pointers, host code; byte-identical to the reference's writers) ---- */
 

@@ -27,6 +27,9 @@ eight states from the backbone hydrogen bonds and ``backbone_torsions`` gives ph
 ``ss_mae`` and ``js_rama`` are the ensemble summaries built on them.  Which residues touch: ``contact_map``, ``contact_order``,
 ``native_contacts`` and ``fraction_native_contacts`` (csrc/ensemble_contacts.hip: CA contacts by squared float64 distances; the hard Q and
 the soft Q of Best, Hummer and Eaton 2013), with ``contact_mae``, ``js_q`` and ``mean_q`` as the ensemble-against-reference summaries.
+How buried each residue is: ``solvent_accessibility`` and ``relative_accessibility`` (csrc/ensemble_sasa.hip: Shrake and Rupley's point
+test on N, CA, C, O, CB -- no side chains, so absolute areas overstate the exposure of large residues), with ``mean_sasa``, ``sasa_mae``
+and ``js_sasa`` as the summaries.
 """
 from __future__ import annotations
 
@@ -603,6 +606,89 @@ def js_rama(atoms_dict, ref_key="target", n_bins=36, residue_index=None):
     """Jensen-Shannon distance of the Ramachandran (phi, psi) histograms, n_bins x n_bins over [-pi, pi)^2, pooled over all structures
     and all residues with both angles defined.  The angles come from the device; the histogram tail is numpy, as for ``js_rg``."""
     binned = {k: _rama_histogram(*backbone_torsions(v, residue_index), n_bins) for k, v in atoms_dict.items()}
+    out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
+    out[ref_key] = 0.0
+    return out
+
+
+# ---- solvent accessibility (csrc/ensemble_sasa.hip; Shrake & Rupley 1973, include/str2str_hip.h has the definition) ----
+SASA_RADII = (1.55, 1.7, 1.7, 1.52, 1.7)      # Bondi radii of N, CA, C, O, CB in Angstrom: the clash radii of the violations, MDTraj's, Biopython's
+
+
+class SolventAccessibility(NamedTuple):
+    """Per structure of an ensemble [R, L, 5, 3]: ``counts`` [R, L, 5] int32 (the accessible sphere points of N, CA, C, O, CB),
+    ``per_residue`` [R, L] and ``total`` [R] float64 in square Angstrom."""
+    counts: np.ndarray
+    per_residue: np.ndarray
+    total: np.ndarray
+
+
+def _sasa_inputs(fn, atoms, aatype, radii):
+    """-> (device atoms [R, L, 5, 3], atom_exists uint8 [L, 5]: a GLY has no CB, radii float64 [L, 5]: SASA_RADII by default)."""
+    x = _backbone_dev(atoms)
+    L = x.shape[1]
+    aatype, _ = _sequence_arrays(fn, L, aatype, None)
+    exists = np.ones((L, 5), dtype=np.uint8)
+    exists[aatype == GLY, 4] = 0
+    radii = np.tile(np.asarray(SASA_RADII, dtype=np.float64), (L, 1)) if radii is None else np.asarray(radii.cpu() if torch.is_tensor(radii) else radii, dtype=np.float64)
+    if radii.shape != (L, 5):
+        raise ValueError(f"{fn}: radii {radii.shape} for {L} residues, expected [{L}, 5]")
+    return x, exists, radii
+
+
+def solvent_accessibility(atoms, aatype=None, residue_index=None, radii=None, probe=1.4, n_points=96, max_structures=None) -> SolventAccessibility:
+    """How much of each residue, and of the chain, does the solvent reach?  Shrake and Rupley's surface (``n_points`` test points on every
+    atom's sphere of radius ``radii + probe``; include/str2str_hip.h) of ``atoms`` [R, L, 5, 3] or atom37 [R, L, 37, 3], for the one
+    sequence ``aatype`` [L] (default: all ALA; a GLY has no CB).  ``radii`` [L, 5]: SASA_RADII for every residue by default.
+    ``residue_index`` is accepted like its siblings' and not used: a surface knows no chain breaks.  NOT an all-atom surface: there are no
+    side chains beyond CB, so absolute values overstate the exposure of large residues."""
+    x, exists, radii = _sasa_inputs("solvent_accessibility", atoms, aatype, radii)
+    _sequence_arrays("solvent_accessibility", x.shape[1], None, residue_index)
+    counts, per_res, total = ops.backbone_sasa(x, exists, radii, probe, n_points, max_structures)
+    return SolventAccessibility(counts.cpu().numpy(), per_res.cpu().numpy(), total.cpu().numpy())
+
+
+def relative_accessibility(atoms, aatype=None, residue_index=None, radii=None, probe=1.4, n_points=96, max_structures=None) -> np.ndarray:
+    """-> float64 [R, L] in [0, 1]: each residue's surface in the chain over the surface of the same residue's own atoms alone (the same
+    conformation of its five atoms, the rest of the chain taken away), the share of its own surface that the rest of the chain leaves
+    exposed (NaN for a residue none of whose atoms exists).  The denominator comes from the same kernel on the residues as one-residue
+    structures.  NOT the relative accessibility against tabulated Gly-X-Gly maxima: no such table is in the tree."""
+    x, exists, radii = _sasa_inputs("relative_accessibility", atoms, aatype, radii)
+    _sequence_arrays("relative_accessibility", x.shape[1], None, residue_index)
+    R, L = x.shape[:2]
+    in_chain = ops.backbone_sasa(x, exists, radii, probe, n_points, max_structures)[1]
+    alone = torch.empty_like(in_chain)
+    kinds, kind_of = np.unique(np.concatenate([radii, exists.astype(np.float64)], axis=1), axis=0, return_inverse=True)
+    for q in range(len(kinds)):                                 # the residues that share radii and existing atoms share a launch sequence
+        idx = torch.as_tensor(np.nonzero(kind_of.reshape(-1) == q)[0], device=x.device)
+        own = x[:, idx].reshape(-1, 1, 5, 3).contiguous()
+        r0 = int(idx[0])
+        alone[:, idx] = ops.backbone_sasa(own, exists[r0:r0 + 1], radii[r0:r0 + 1], probe, n_points, max_structures)[1].reshape(R, len(idx))
+    return (in_chain / alone).cpu().numpy()
+
+
+def mean_sasa(atoms_dict, aatype=None, residue_index=None, **sasa_args):
+    """Per ensemble the mean total solvent-accessible surface of its structures in square Angstrom; ``sasa_args``: the arguments of
+    ``solvent_accessibility``."""
+    return {k: np.around(float(solvent_accessibility(v, aatype, residue_index, **sasa_args).total.mean()), decimals=4) for k, v in atoms_dict.items()}
+
+
+def sasa_mae(atoms_dict, ref_key="target", aatype=None, residue_index=None, **sasa_args):
+    """Per ensemble the mean over the residues of the absolute difference of its mean relative accessibility from the reference
+    ensemble's."""
+    rel = {k: relative_accessibility(v, aatype, residue_index, **sasa_args).mean(0) for k, v in atoms_dict.items()}
+    out = {k: np.around(float(np.abs(v - rel[ref_key]).mean()), decimals=4) for k, v in rel.items() if k != ref_key}
+    out[ref_key] = 0.0
+    return out
+
+
+def js_sasa(atoms_dict, ref_key="target", n_bins=50, weights=None, aatype=None, residue_index=None, **sasa_args):
+    """Jensen-Shannon distance of the histograms of the structures' total surface, ``n_bins`` bins over the range of the reference
+    ensemble, as ``js_rg`` does it for the radius of gyration."""
+    w = _weights(weights, atoms_dict)
+    total = {k: solvent_accessibility(v, aatype, residue_index, **sasa_args).total for k, v in atoms_dict.items()}
+    d_min, d_max = total[ref_key].min(), total[ref_key].max()
+    binned = {k: np.histogram(v, bins=n_bins, weights=w[k], range=(d_min, d_max))[0] + PSEUDO_C for k, v in total.items()}
     out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
     out[ref_key] = 0.0
     return out

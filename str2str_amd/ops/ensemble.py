@@ -1,7 +1,9 @@
 """Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition, lDDT, clustering,
-backbone violations, secondary structure and torsions, contact maps and the fraction of native contacts."""
+backbone violations, secondary structure and torsions, contact maps and the fraction of native contacts, solvent accessibility."""
+import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from .binding import HipLibraryError, _check, _p, _req, _stream, load_library
@@ -15,6 +17,9 @@ VIOL_MAX_RES = 1024               # S2S_VIOL_MAX_RES: the chain length whose ato
 VIOL_MAX_STRUCTURES = 1 << 20     # structures per s2s_backbone_violations launch, unless max_structures says less
 SS_MAX_RES = 704                  # S2S_SS_MAX_RES: the chain length whose atoms and bond relation fit the LDS of s2s_secondary_structure
 SS_MAX_STRUCTURES = 1 << 20       # structures per s2s_secondary_structure launch, unless max_structures says less
+SASA_MAX_RES = 512                # S2S_SASA_MAX_RES: the chain length whose atoms, radii and areas fit the LDS of s2s_backbone_sasa as float64
+SASA_MAX_POINTS = 1024            # S2S_SASA_MAX_POINTS: the sphere of s2s_backbone_sasa stays in LDS, a lane owns at most 16 of its points
+SASA_MAX_STRUCTURES = 1 << 20     # structures per s2s_backbone_sasa launch, unless max_structures says less
 CONTACT_MAX_RES = 1024            # S2S_CONTACT_MAX_RES: the chain length whose tile of structures fits the LDS of s2s_ca_native_q
 CONTACT_LAUNCH_STRUCTURES = 65535  # S2S_CONTACT_MAX_STRUCTURES: structures per launch of the contact kernels
 CLUSTER_MAX_N = 65536             # S2S_CLUSTER_MAX_N: structures per clustering (512 MB of neighbour bits)
@@ -435,6 +440,52 @@ def secondary_structure(atoms: torch.Tensor, aatype, residue_index, max_structur
     for n, p_atoms, *p_out in _row_chunks(R, rows, atoms, ss, n_hbonds, hb_energy, hb_partner, torsions):
         _check(lib.s2s_secondary_structure(p_atoms, n, L, _p(aatype), _p(residue_index), *p_out, _stream()), "s2s_secondary_structure")
     return ss, n_hbonds, hb_energy, hb_partner, torsions
+
+
+def sphere_points(n_points: int) -> np.ndarray:
+    """The unit sphere of the Shrake-Rupley test: the golden spiral of include/str2str_hip.h -> float64 [n_points, 3].  Built on the host
+    in numpy so that the kernel and a numpy statement of the definition read the same bits."""
+    if isinstance(n_points, bool) or int(n_points) != n_points or not 1 <= n_points <= SASA_MAX_POINTS:
+        raise HipLibraryError(f"sphere_points: n_points must be an integer in 1 .. {SASA_MAX_POINTS}, got {n_points}")
+    P = int(n_points)
+    k = np.arange(P, dtype=np.float64)
+    y = (k * (2.0 / P) - 1.0) + 1.0 / P
+    r = np.sqrt(1.0 - y * y)
+    phi = k * (math.pi * (3.0 - math.sqrt(5.0)))
+    return np.stack([np.cos(phi) * r, y, np.sin(phi) * r], axis=1)
+
+
+def backbone_sasa(atoms: torch.Tensor, atom_exists, radii, probe: float = 1.4, n_points: int = 96, max_structures: Optional[int] = None):
+    """The solvent-accessible surface of include/str2str_hip.h (Shrake and Rupley's point test on the spheres of radius ``radii + probe``)
+    of every structure of atoms [R, L, 5, 3] fp32 device tensor, atom14 slots N, CA, C, O, CB.  ``atom_exists`` [L, 5] (non-zero: the atom
+    exists) and ``radii`` [L, 5] (Angstrom, finite and positive where the atom exists) belong to the one sequence of the ensemble.
+    -> device tensors (counts [R, L, 5] int32: the accessible points of ``sphere_points(n_points)`` per atom; per_residue [R, L] fp64 in
+    A^2; total [R] fp64).  Backbone and CB only: no side chains.  ``max_structures`` bounds the structures of one launch; a structure's
+    results are bit for bit the same for any value."""
+    rows = _backbone_ensemble("backbone_sasa", atoms, SASA_MAX_RES, max_structures, SASA_MAX_STRUCTURES)
+    R, L = atoms.shape[:2]
+    exists = _viol_small("atom_exists", atom_exists, (L, 5), torch.uint8, "backbone_sasa")
+    radii = torch.as_tensor(radii)
+    if radii.shape != (L, 5) or radii.is_complex():
+        raise HipLibraryError(f"backbone_sasa: radii: expected numbers of shape {(L, 5)}, got {radii.dtype} {tuple(radii.shape)}")
+    radii = radii.to("cpu", torch.float64).contiguous()
+    there = radii[exists.cpu() != 0]
+    if not bool((torch.isfinite(there) & (there > 0.0)).all()):
+        raise HipLibraryError("backbone_sasa: radii must be finite and positive where the atom exists")
+    probe = float(probe)
+    if not 0.0 <= probe < float("inf"):
+        raise HipLibraryError(f"backbone_sasa: probe must be finite and >= 0, got {probe}")
+    sphere = torch.from_numpy(sphere_points(n_points))
+    _req(atoms, name="atoms")
+    dev = atoms.device
+    exists, radii, sphere = exists.to(dev), radii.to(dev), sphere.to(dev)
+    lib = load_library()
+    counts = torch.empty(R, L, 5, dtype=torch.int32, device=dev)
+    per_res = torch.empty(R, L, dtype=torch.float64, device=dev)
+    total = torch.empty(R, dtype=torch.float64, device=dev)
+    for n, p_atoms, *p_out in _row_chunks(R, rows, atoms, counts, per_res, total):
+        _check(lib.s2s_backbone_sasa(p_atoms, n, L, _p(exists), _p(radii), probe, _p(sphere), int(n_points), *p_out, _stream()), "s2s_backbone_sasa")
+    return counts, per_res, total
 
 
 def cluster_adjacency(values: torch.Tensor, cutoff: float, at_least: bool = False, row0: int = 0, adj: Optional[torch.Tensor] = None,
