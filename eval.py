@@ -14,7 +14,12 @@ per-residue propensities ``secondary_structure/<target>.csv``.
 absolute difference of their contact maps, mean relative contact order of both) and the contact probabilities ``contacts/<target>.csv``.
 ``+sasa=true`` also computes the solvent-accessible surface of the backbone and CB atoms of the sampled and the target ensembles (on the
 device; no side chains) and writes ``sasa_<tag>_<mmdd-HH-MM>.csv`` (mean total surface of both, the JS distance of their distributions, the
-mean absolute difference of their per-residue relative accessibilities) and the per-residue means ``sasa/<target>.csv``."""
+mean absolute difference of their per-residue relative accessibilities) and the per-residue means ``sasa/<target>.csv``.
+``+saxs=true`` also computes what a solution measurement would see of the sampled and the target ensembles (on the device: the Debye
+scattering curve and the Kirkwood hydrodynamic radius of the CA beads; no hydration shell, no excluded volume, no form-factor table) and
+writes ``saxs_<tag>_<mmdd-HH-MM>.csv`` (the mean relative difference of the two curves, the mean hydrodynamic radius of both, the JS
+distance of their distributions) and the curves ``saxs/<target>.csv``; ``+saxs_data=DIR`` adds the reduced chi^2 of the sampled
+ensemble's curve against the measured ``DIR/<target>.dat`` (columns q in 1/Angstrom, I, sigma)."""
 import logging
 import os
 import sys
@@ -160,6 +165,36 @@ def sasa_row(pred_file, target_file, log=log):
     return row, {"pred": per_res["pred"], "target": per_res.get("target")}, residue_index
 
 
+SAXS_COLUMNS = ("saxs_mae", "rh_mean", "rh_mean_target", "js_rh")
+
+
+def saxs_switch(value) -> bool:
+    """``+saxs=...`` as a bool: absent, null and false leave everything as it was."""
+    return _switch("saxs", value)
+
+
+def saxs_row(ca, data_file=None):
+    """One row of the saxs csv (SAXS_COLUMNS; with ``data_file``, a path, also ``saxs_chi2``) and the table of the curves (q, i_pred,
+    i_target on metrics.SAXS_Q_GRID) of one target from its CA ensembles {"pred": [R, L, 3], "target": [Rt, L, 3]}.  ``saxs_chi2`` is the
+    reduced chi^2 of the sampled ensemble's curve, on the measured file's own q grid and scaled to it by least squares, and NaN where the
+    file does not exist."""
+    import numpy as np
+
+    from str2str_amd.metrics import metrics
+
+    q = metrics.SAXS_Q_GRID
+    curve = {k: metrics.ensemble_saxs(v, q) for k, v in ca.items()}
+    rh = metrics.mean_rh(ca)
+    row = {"saxs_mae": np.around(float((np.abs(curve["pred"] - curve["target"]) / curve["target"]).mean()), decimals=4),
+           "rh_mean": rh["pred"], "rh_mean_target": rh["target"], "js_rh": metrics.js_rh(ca, ref_key="target")["pred"]}
+    if data_file is not None:
+        row["saxs_chi2"] = float("nan")
+        if os.path.isfile(data_file):
+            q_exp, i_exp, sigma = metrics.read_saxs_dat(data_file)
+            row["saxs_chi2"] = np.around(metrics.saxs_chi2(metrics.ensemble_saxs(ca["pred"], q_exp), i_exp, sigma)[0], decimals=4)
+    return row, {"q": q, "i_pred": np.around(curve["pred"], decimals=4), "i_target": np.around(curve["target"], decimals=4)}
+
+
 def secondary_structure_row(pred_file, target_file, log=log):
     """One row of the ss csv (SS_COLUMNS) and the per-residue propensities {"pred": [L, 3], "target": [L, 3] or None} of one target.  A
     target without a full backbone (a CA trace) leaves NaN in the columns that need it."""
@@ -188,7 +223,7 @@ def secondary_structure_row(pred_file, target_file, log=log):
 
 
 def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None, cluster_cutoff=None,
-                        secondary_structure=None, contacts=None, sasa=None):
+                        secondary_structure=None, contacts=None, sasa=None, saxs=None, saxs_data=None):
     """reference src/eval.py:47-99: one row per target, one column per metric, plus the mean row.  ``extra_metrics``: names out of
     EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's).
     ``cluster_cutoff`` (A; None: nothing of this happens): the ``pred`` ensemble of every target is clustered by ``metrics.cluster_rmsd``;
@@ -199,11 +234,16 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     this happens): ``contacts_<tag>_<mmdd-HH-MM>.csv`` receives one row per target (CONTACT_COLUMNS) and the mean row, and
     ``contacts/<target>.csv`` the contact probabilities of both ensembles.  ``sasa`` (true; otherwise nothing of this happens):
     ``sasa_<tag>_<mmdd-HH-MM>.csv`` receives one row per target (SASA_COLUMNS) and the mean row, and ``sasa/<target>.csv`` the per-residue
-    mean surface and mean relative accessibility of both ensembles."""
+    mean surface and mean relative accessibility of both ensembles.  ``saxs`` (true; otherwise nothing of this happens):
+    ``saxs_<tag>_<mmdd-HH-MM>.csv`` receives one row per target (SAXS_COLUMNS, and ``saxs_chi2`` against ``<saxs_data>/<target>.dat`` when
+    the directory ``saxs_data`` is given) and the mean row, and ``saxs/<target>.csv`` the scattering curves of both ensembles."""
     columns = metric_columns(extra_metrics)
     secondary_structure = secondary_structure_switch(secondary_structure)
     contacts = contacts_switch(contacts)
     sasa = sasa_switch(sasa)
+    saxs = saxs_switch(saxs)
+    if saxs_data is not None and not saxs:
+        raise ValueError(f"saxs_data {saxs_data}: needs saxs=true")
     if cluster_cutoff is not None and not 0.0 < float(cluster_cutoff) < float("inf"):
         raise ValueError(f"cluster_cutoff {cluster_cutoff}: expected a positive finite RMSD in Angstrom")
     from time import strftime
@@ -226,7 +266,7 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
            "div_rmsd": metrics.diversity_rmsd, "div_tm": metrics.diversity_tm, "div_lddt": metrics.diversity_lddt}
     coverage = {"rmsd": metrics.coverage_rmsd, "tm": metrics.coverage_tm, "lddt": metrics.coverage_lddt}
     eval_res = {k: {} for k in columns}
-    clusters, ss_rows, contact_rows, sasa_rows = {}, {}, {}, {}
+    clusters, ss_rows, contact_rows, sasa_rows, saxs_rows = {}, {}, {}, {}, {}
     for target in targets:
         pred_file = os.path.join(pred_dir, f"{target}.pdb")
         if not os.path.isfile(pred_file):
@@ -276,6 +316,10 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
                     table[f"{k}_{c}"] = np.full(len(numbers), np.nan) if per_res[k] is None else np.around(per_res[k][q], decimals=4)
             os.makedirs(os.path.join(output_dir, "sasa"), exist_ok=True)
             pd.DataFrame(table).to_csv(os.path.join(output_dir, "sasa", f"{target}.csv"), index=False, sep="\t")
+        if saxs:
+            saxs_rows[target], table = saxs_row(ca, None if saxs_data is None else os.path.join(str(saxs_data), f"{target}.dat"))
+            os.makedirs(os.path.join(output_dir, "saxs"), exist_ok=True)
+            pd.DataFrame(table).to_csv(os.path.join(output_dir, "saxs", f"{target}.csv"), index=False, sep="\t")
     df = pd.DataFrame.from_dict(eval_res)
     df.loc["mean"] = np.around(df.mean(), decimals=4)
     df.to_csv(os.path.join(output_dir, f"metrics_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
@@ -293,6 +337,10 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
         sf = pd.DataFrame.from_dict(sasa_rows, orient="index", columns=list(SASA_COLUMNS))
         sf.loc["mean"] = np.around(sf.mean(), decimals=4)
         sf.to_csv(os.path.join(output_dir, f"sasa_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
+    if saxs:
+        xf = pd.DataFrame.from_dict(saxs_rows, orient="index", columns=list(SAXS_COLUMNS) + ([] if saxs_data is None else ["saxs_chi2"]))
+        xf.loc["mean"] = np.around(xf.mean(), decimals=4)
+        xf.to_csv(os.path.join(output_dir, f"saxs_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
     return df.loc["mean"]
 
 
@@ -300,7 +348,7 @@ def evaluate(cfg):
     pred_dir = cfg.get("pred_dir")
     scoring = dict(target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"), extra_metrics=cfg.get("extra_metrics"),
                    cluster_cutoff=cfg.get("cluster_cutoff"), secondary_structure=cfg.get("secondary_structure"),
-                   contacts=cfg.get("contacts"), sasa=cfg.get("sasa"))
+                   contacts=cfg.get("contacts"), sasa=cfg.get("sasa"), saxs=cfg.get("saxs"), saxs_data=cfg.get("saxs_data"))
     if pred_dir and os.path.isdir(pred_dir):
         log.info(f"Found pre-computed prediction directory {pred_dir}.")
         return evaluate_prediction(pred_dir, **scoring)

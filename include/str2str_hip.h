@@ -23,7 +23,8 @@
 extern "C" {
 #endif
 
-/* Library ABI version (bumped on any signature change).  Still 40 with s2s_backbone_sasa: an entry point was added, no signature changed. */
+/* Library ABI version (bumped on any signature change).  Still 40 with s2s_backbone_sasa and s2s_ca_scattering: entry points were added, no
+ * signature changed. */
 int s2s_abi_version(void);
 
 /* Arithmetic.  Every matrix product of the path exists in two forms behind the same operator contract:
@@ -664,6 +665,38 @@ int s2s_ca_native_q(const float* ca, int n, int n_res, const int* pairs, const d
  * otherwise hipErrorInvalidValue before any launch.  counts [n, n_res, 5] int, per_residue [n, n_res] and total [n] float64. */
 int s2s_backbone_sasa(const float* atoms, int n, int n_res, const unsigned char* atom_exists, const double* radii, double probe,
                       const double* sphere, int n_points, int* counts, double* per_residue, double* total, void* stream);
+
+/* ---- Solution scattering: what would a SAXS or a diffusion measurement see of this ensemble?  (csrc/ensemble_saxs.hip; Debye, Ann. Phys.
+ * 351 (1915) 809; Kirkwood, J. Polym. Sci. 12 (1954) 1; no counterpart in the reference) ----
+ * For a structure of L = n_res CA beads with positions x_i (float32 widened to float64), v_ij = |x_i - x_j|^2 = (dx dx + dy dy) + dz dz,
+ * r_ij = sqrt(v_ij), a q-list q_k >= 0 in 1/Angstrom, and a form factor f_i(q_k) = table[types[i], k] (table [n_types, n_q] float64 of any
+ * sign: contrast can be negative; types [n_res] int32 in 0 .. n_types - 1; both shared by the n structures):
+ *  Intensity (Debye 1915).  I(q_k) = sum_i f_i(q_k)^2 + 2 sum_{i<j} f_i(q_k) f_j(q_k) s(q_k r_ij), with s(a) = 1.0 if a == 0.0, else
+ *     sin(a) / a.  One sqrt per pair; one product a = q_k r_ij, one sin and one division per (pair, q); a term is (f_i f_j) s.
+ *  Kirkwood hydrodynamic radius.  1 / Rh = (1 / L^2) sum_{i != j} 1 / r_ij.  The kernel returns inv_r_mean = (2 sum_{i<j} 1 / r_ij) / (L L).
+ *     L = 1 gives 0 (Rh = inf).  Coincident beads give inf (Rh = 0).
+ *  Default form factors (the binding's): one type, all ones.  Every residue is the same point scatterer, so I(0) = L^2.  This is the usual
+ *     CA-bead approximation and holds for q <~ 0.3 / Angstrom.
+ *  NaN.  A NaN (or infinite) coordinate makes that structure's outputs NaN and touches no other structure: every diagonal term is
+ *     f_i^2 + |x_i - x_i|^2, which is f_i^2 for a finite bead, and the same sum of |x_i - x_i|^2 is added to inv_r_mean, so that a
+ *     structure of one bead follows the rule as well.
+ *  Order of the sums.  A workgroup of 256 threads owns one structure and a tile of 16 consecutive q-values.  Thread t adds the pairs
+ *     t, t + 256, ... of the flattened upper triangle (row i holds j = i + 1 .. L - 1) in ascending order, the 64 lanes of a wave meet in
+ *     an xor tree, the four waves are added in turn, the diagonal is added in ascending i, then I = diag + 2 off.  The order is a function
+ *     of n_res and the block shape alone: a structure's row of intensity and its inv_r_mean are the same bytes in any launch, any chunking,
+ *     any position in the batch, and for any q-list that contains the same q at the same offset within its tile.
+ * Arithmetic: everything is float64, one rounding per operation (no contraction); sin is the device library's double sine.
+ * What this is NOT: there is no hydration shell, no excluded-volume term, no built-in residue form-factor table (the caller brings one),
+ * no side chains, and no Nygaard or other correction of the Kirkwood value.  No gradients. */
+#define S2S_SAXS_MAX_RES 1024   /* the structure's beads stay in LDS as three float64 planes with their types: 28 KiB */
+#define S2S_SAXS_MAX_Q 1024     /* q-values per call, tiles of 16 */
+#define S2S_SAXS_MAX_TYPES 64   /* the tile's slice of the table stays in LDS: 8 KiB */
+
+/* No scratch.  n >= 1, 1 <= n_res <= S2S_SAXS_MAX_RES, 1 <= n_q <= S2S_SAXS_MAX_Q, 1 <= n_types <= S2S_SAXS_MAX_TYPES, no NULL buffer but
+ * inv_r_mean (NULL: not computed); otherwise hipErrorInvalidValue before any launch.  ca [n, n_res, 3]; intensity [n, n_q] and inv_r_mean
+ * [n] float64.  q must be finite and >= 0, the table finite and the types inside the table: the binding checks that before the device. */
+int s2s_ca_scattering(const float* ca, int n, int n_res, const double* q, int n_q, const int* types, const double* table, int n_types,
+                      double* intensity, double* inv_r_mean, void* stream);
 
 /* ---- PDB text at the exit of the path (HOST pointers, host code; byte-identical to the reference's writers) ---- */
 

@@ -41,6 +41,7 @@ UNITS = {
     "ensemble_violations.hip": ["-ffp-contract=off"],   # every float64 term rounds like the numpy yardstick's
     "ensemble_ss.hip": ["-ffp-contract=off"],           # (as above: energies and cosines decide letters)
     "ensemble_sasa.hip": ["-ffp-contract=off"],         # (as above: every point test is the yardstick's, the counts are exact)
+    "ensemble_saxs.hip": ["-ffp-contract=off"],         # (as above: the argument q r of every sine is the yardstick's)
     # the MFMA chains are fully unrolled on purpose (accumulator tiles must be statically indexed)
     "pair_mlp.hip": ["-mllvm", "-pragma-unroll-threshold=10000000"],
     # (no SLP vectorisation in the split-f16 pair kernels: hipcc packs the LayerNorm / epilogue arithmetic into v_pk_*_f32, and a packed

@@ -29,7 +29,10 @@ eight states from the backbone hydrogen bonds and ``backbone_torsions`` gives ph
 the soft Q of Best, Hummer and Eaton 2013), with ``contact_mae``, ``js_q`` and ``mean_q`` as the ensemble-against-reference summaries.
 How buried each residue is: ``solvent_accessibility`` and ``relative_accessibility`` (csrc/ensemble_sasa.hip: Shrake and Rupley's point
 test on N, CA, C, O, CB -- no side chains, so absolute areas overstate the exposure of large residues), with ``mean_sasa``, ``sasa_mae``
-and ``js_sasa`` as the summaries.
+and ``js_sasa`` as the summaries.  What a solution measurement would see: ``saxs_profile``, ``ensemble_saxs`` and ``hydrodynamic_radius``
+(csrc/ensemble_saxs.hip: the Debye intensity and the Kirkwood radius of the CA beads -- no hydration shell, no excluded volume, no
+built-in form factors, no side chains), ``saxs_mae``, ``mean_rh`` and ``js_rh`` as the summaries, ``saxs_chi2`` and ``read_saxs_dat`` for
+the comparison with a measured curve.
 """
 from __future__ import annotations
 
@@ -692,6 +695,132 @@ def js_sasa(atoms_dict, ref_key="target", n_bins=50, weights=None, aatype=None, 
     out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
     out[ref_key] = 0.0
     return out
+
+
+# ---- solution scattering (csrc/ensemble_saxs.hip; Debye 1915, Kirkwood 1954; include/str2str_hip.h has the definition) ----
+SAXS_Q_GRID = np.arange(51) / 100.0           # 0.00, 0.01, ..., 0.50 per Angstrom: the grid of eval.py, inside the range of the CA-bead approximation
+
+
+def _saxs_call(coords, q, aatype, form_factors, max_structures):
+    """-> (intensity [R, Q], inv_r_mean [R]) numpy float64: ``ops.ca_scattering`` walked over the q-list in runs of ops.SAXS_MAX_Q (whole
+    tiles, so every column has the bytes of a single call)."""
+    x = _dev(coords)
+    q = np.asarray(q.cpu() if torch.is_tensor(q) else q, dtype=np.float64)
+    if q.ndim != 1 or q.size < 1:
+        raise ValueError(f"q has shape {q.shape}, expected [Q] with Q >= 1")
+    table = types = None
+    if form_factors is not None:
+        table = np.asarray(form_factors.cpu() if torch.is_tensor(form_factors) else form_factors, dtype=np.float64)
+        if table.ndim != 2 or table.shape[1] != q.size:
+            raise ValueError(f"form_factors has shape {table.shape} for {q.size} q-values, expected [n_types, {q.size}]")
+        types = None if aatype is None else np.asarray(aatype.cpu() if torch.is_tensor(aatype) else aatype)
+        if types is not None and types.shape != (x.shape[1],):
+            raise ValueError(f"aatype has shape {types.shape} for {x.shape[1]} residues")
+    runs = [ops.ca_scattering(x, q[k:k + ops.SAXS_MAX_Q], types, None if table is None else table[:, k:k + ops.SAXS_MAX_Q], max_structures)
+            for k in range(0, q.size, ops.SAXS_MAX_Q)]
+    return np.concatenate([r[0].cpu().numpy() for r in runs], axis=1), runs[0][1].cpu().numpy()
+
+
+def saxs_profile(coords, q, aatype=None, form_factors=None, max_structures=None) -> np.ndarray:
+    """What would a SAXS measurement see of each structure?  The Debye intensity I(q) = sum_i f_i^2 + 2 sum_{i<j} f_i f_j sin(q r_ij) /
+    (q r_ij) of the CA beads of ``coords`` [R, L, 3] at the ``q`` [Q] (1/Angstrom) -> float64 [R, Q].  By default every residue is the same
+    point scatterer (f = 1, I(0) = L^2), the usual CA-bead approximation, good for q <~ 0.3 / Angstrom.  A caller with residue form factors
+    passes ``form_factors`` [n_types, Q] (any sign: contrast can be negative) and ``aatype`` [L] (the row of every residue; without
+    ``form_factors`` it is not used).  NOT here: a hydration shell, an excluded-volume term, a built-in form-factor table, side chains."""
+    return _saxs_call(coords, q, aatype, form_factors, max_structures)[0]
+
+
+def ensemble_saxs(coords, q, weights=None, aatype=None, form_factors=None, max_structures=None) -> np.ndarray:
+    """The curve of the ensemble -> float64 [Q]: the (``weights`` [R]: weighted) mean of the structures' *intensities*, which is what a
+    solution of them scatters."""
+    rows = saxs_profile(coords, q, aatype, form_factors, max_structures)
+    if weights is None:
+        return rows.mean(axis=0)
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape != (len(rows),):
+        raise ValueError(f"weights has shape {w.shape} for {len(rows)} structures")
+    return np.average(rows, axis=0, weights=w)
+
+
+def hydrodynamic_radius(coords, max_structures=None) -> np.ndarray:
+    """Kirkwood's hydrodynamic radius of the CA beads of every structure of ``coords`` [R, L, 3] -> float64 [R] in Angstrom:
+    1 / Rh = (1 / L^2) sum_{i != j} 1 / r_ij.  inf for a single bead, 0 where two beads coincide.  No Nygaard or other correction."""
+    inv = _saxs_call(coords, [0.0], None, None, max_structures)[1]
+    with np.errstate(divide="ignore"):
+        return 1.0 / inv
+
+
+def saxs_mae(ca_coords_dict, ref_key="target", q=None, weights=None, **saxs_args):
+    """Per ensemble the mean over ``q`` (SAXS_Q_GRID by default) of |I - I_ref| / I_ref, I the ensemble's curve (``ensemble_saxs``) and I_ref
+    the reference ensemble's.  ``weights``: per-structure weights by key, as in ``js_pwd``; ``saxs_args``: ``aatype``, ``form_factors``."""
+    q = SAXS_Q_GRID if q is None else q
+    w = _weights(weights, ca_coords_dict) if weights else {}
+    curve = {k: ensemble_saxs(v, q, w.get(k), **saxs_args) for k, v in ca_coords_dict.items()}
+    out = {k: np.around(float((np.abs(c - curve[ref_key]) / curve[ref_key]).mean()), decimals=4) for k, c in curve.items() if k != ref_key}
+    out[ref_key] = 0.0
+    return out
+
+
+def mean_rh(ca_coords_dict, weights=None):
+    """The (weighted) mean hydrodynamic radius of each ensemble in Angstrom."""
+    w = _weights(weights, ca_coords_dict)
+    return {k: np.around(float(np.average(hydrodynamic_radius(v), weights=w[k])), decimals=4) for k, v in ca_coords_dict.items()}
+
+
+def js_rh(ca_coords_dict, ref_key="target", n_bins=50, weights=None):
+    """Jensen-Shannon distance of the histograms of the structures' hydrodynamic radius, ``n_bins`` bins over the range of the reference
+    ensemble, as ``js_rg`` does it for the radius of gyration."""
+    w = _weights(weights, ca_coords_dict)
+    rh = {k: hydrodynamic_radius(v) for k, v in ca_coords_dict.items()}
+    d_min, d_max = rh[ref_key].min(), rh[ref_key].max()
+    binned = {k: np.histogram(v, bins=n_bins, weights=w[k], range=(d_min, d_max))[0] + PSEUDO_C for k, v in rh.items()}
+    out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
+    out[ref_key] = 0.0
+    return out
+
+
+def saxs_chi2(intensity, i_exp, sigma, background=False):
+    """A computed curve against a measured one on the same q grid -> (chi2, scale, background): the weighted least-squares fit
+    i_exp ~ scale * intensity (+ a constant with ``background``) in closed form, and its reduced chi^2 = sum(((scale * intensity +
+    background - i_exp) / sigma)^2) / (Q - 1) (Q - 2 with the constant).  ``background`` is returned as 0.0 when it is not fitted."""
+    i_calc, i_exp, sigma = (np.asarray(v, dtype=np.float64) for v in (intensity, i_exp, sigma))
+    dof = 2 if background else 1
+    if i_calc.ndim != 1 or i_exp.shape != i_calc.shape or sigma.shape != i_calc.shape or i_calc.size <= dof:
+        raise ValueError(f"saxs_chi2: curves of shapes {i_calc.shape}, {i_exp.shape}, {sigma.shape}: expected three [Q] with Q > {dof}")
+    if not (np.isfinite(sigma) & (sigma > 0.0)).all():
+        raise ValueError("saxs_chi2: sigma must be finite and positive")
+    w = 1.0 / (sigma * sigma)
+    s_cc, s_ce = float((w * i_calc * i_calc).sum()), float((w * i_calc * i_exp).sum())
+    if background:
+        s_w, s_c, s_e = float(w.sum()), float((w * i_calc).sum()), float((w * i_exp).sum())
+        det = s_cc * s_w - s_c * s_c
+        scale, const = (s_ce * s_w - s_c * s_e) / det, (s_cc * s_e - s_c * s_ce) / det
+    else:
+        scale, const = s_ce / s_cc, 0.0
+    resid = (scale * i_calc + const - i_exp) / sigma
+    return float((resid * resid).sum()) / (i_calc.size - dof), float(scale), float(const)
+
+
+def read_saxs_dat(path, q_unit="1/A"):
+    """A measured curve from a three-column text file (q, I, sigma; whitespace-separated, ``#`` starts a comment) -> (q in 1/Angstrom, I,
+    sigma) float64 [Q].  Lines that are not three numbers (headers, footers) are skipped, rows with sigma <= 0 or a non-finite value dropped.  ``q_unit``:
+    "1/A", or "1/nm" (q is divided by 10)."""
+    if q_unit not in ("1/A", "1/nm"):
+        raise ValueError(f"read_saxs_dat: q_unit {q_unit!r}: expected '1/A' or '1/nm'")
+    rows = []
+    with open(path) as f:
+        for line in f:
+            fields = line.split("#", 1)[0].split()
+            if len(fields) != 3:
+                continue
+            try:
+                row = [float(v) for v in fields]
+            except ValueError:
+                continue
+            if all(math.isfinite(v) for v in row) and row[2] > 0.0:
+                rows.append(row)
+    data = np.asarray(rows, dtype=np.float64).reshape(-1, 3)
+    return (data[:, 0] / 10.0 if q_unit == "1/nm" else data[:, 0].copy()), data[:, 1].copy(), data[:, 2].copy()
 
 
 # ---- clustering at a cutoff (csrc/ensemble_cluster.hip) ----------------------------------------------------------------------------

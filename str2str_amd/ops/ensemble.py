@@ -1,5 +1,6 @@
 """Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition, lDDT, clustering,
-backbone violations, secondary structure and torsions, contact maps and the fraction of native contacts, solvent accessibility."""
+backbone violations, secondary structure and torsions, contact maps and the fraction of native contacts, solvent accessibility, solution
+scattering (Debye intensity, Kirkwood hydrodynamic radius)."""
 import math
 from typing import Optional
 
@@ -20,6 +21,10 @@ SS_MAX_STRUCTURES = 1 << 20       # structures per s2s_secondary_structure launc
 SASA_MAX_RES = 512                # S2S_SASA_MAX_RES: the chain length whose atoms, radii and areas fit the LDS of s2s_backbone_sasa as float64
 SASA_MAX_POINTS = 1024            # S2S_SASA_MAX_POINTS: the sphere of s2s_backbone_sasa stays in LDS, a lane owns at most 16 of its points
 SASA_MAX_STRUCTURES = 1 << 20     # structures per s2s_backbone_sasa launch, unless max_structures says less
+SAXS_MAX_RES = 1024               # S2S_SAXS_MAX_RES: the chain length whose beads and types fit the LDS of s2s_ca_scattering as float64 planes
+SAXS_MAX_Q = 1024                 # S2S_SAXS_MAX_Q: q-values per s2s_ca_scattering call, in tiles of 16
+SAXS_MAX_TYPES = 64               # S2S_SAXS_MAX_TYPES: rows of the form-factor table, whose slice of a tile stays in LDS
+SAXS_MAX_STRUCTURES = 1 << 20     # structures per s2s_ca_scattering launch, unless max_structures says less
 CONTACT_MAX_RES = 1024            # S2S_CONTACT_MAX_RES: the chain length whose tile of structures fits the LDS of s2s_ca_native_q
 CONTACT_LAUNCH_STRUCTURES = 65535  # S2S_CONTACT_MAX_STRUCTURES: structures per launch of the contact kernels
 CLUSTER_MAX_N = 65536             # S2S_CLUSTER_MAX_N: structures per clustering (512 MB of neighbour bits)
@@ -486,6 +491,65 @@ def backbone_sasa(atoms: torch.Tensor, atom_exists, radii, probe: float = 1.4, n
     for n, p_atoms, *p_out in _row_chunks(R, rows, atoms, counts, per_res, total):
         _check(lib.s2s_backbone_sasa(p_atoms, n, L, _p(exists), _p(radii), probe, _p(sphere), int(n_points), *p_out, _stream()), "s2s_backbone_sasa")
     return counts, per_res, total
+
+
+def _host_array(fn: str, what: str, v, dtype) -> np.ndarray:
+    """A small per-ensemble input of ``fn`` (tensor on any device, array or list) as a contiguous host array of ``dtype``; integers stay
+    integers (a float array is no list of types)."""
+    try:
+        a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)
+    except (TypeError, ValueError) as e:
+        raise HipLibraryError(f"{fn}: {what}: {e}") from None
+    if a.dtype == object or a.dtype.kind not in ("iu" if dtype == np.int32 else "iuf"):
+        raise HipLibraryError(f"{fn}: {what}: expected {'integers' if dtype == np.int32 else 'real numbers'}, got {a.dtype}")
+    return a
+
+
+def ca_scattering(ca: torch.Tensor, q, types=None, table=None, max_structures: Optional[int] = None):
+    """The solution scattering of include/str2str_hip.h of every structure of ca [R, L, 3] fp32 device tensor, CA beads: the Debye intensity
+    I(q_k) = sum_i f_i^2 + 2 sum_{i<j} f_i f_j sin(q_k r_ij) / (q_k r_ij) at the ``q`` [Q] (1/Angstrom, finite and >= 0) and the Kirkwood
+    mean inverse distance.  ``table`` [n_types, Q]: the form factor of every type at every q, finite, of any sign (None: one type, all
+    ones, so I(0) = L^2); ``types`` [L]: the type of every residue, integers in 0 .. n_types - 1 (None: all 0).  -> device tensors
+    (intensity [R, Q] fp64; inv_r_mean [R] fp64 = (2 / L^2) sum_{i<j} 1 / r_ij: the hydrodynamic radius is its reciprocal, inf for one
+    bead, 0 for coincident beads).  No hydration shell, no excluded volume, no built-in form factors, no side chains.  ``max_structures``
+    bounds the structures of one launch; a structure's results are bit for bit the same for any value."""
+    fn = "ca_scattering"
+    if not isinstance(ca, torch.Tensor):
+        raise HipLibraryError(f"{fn}: expected a tensor, got {type(ca).__name__}")
+    if ca.ndim != 3 or ca.shape[2] != 3 or ca.shape[0] < 1 or ca.shape[1] < 1:
+        raise HipLibraryError(f"{fn}: ca {tuple(ca.shape)}, expected [R, L, 3]")
+    R, L = ca.shape[:2]
+    if L > SAXS_MAX_RES:
+        raise HipLibraryError(f"{fn}: at most {SAXS_MAX_RES} residues, got {L}")
+    if max_structures is not None and (isinstance(max_structures, bool) or int(max_structures) != max_structures or max_structures < 1):
+        raise HipLibraryError(f"{fn}: max_structures must be an integer >= 1, got {max_structures}")
+    rows = SAXS_MAX_STRUCTURES if max_structures is None else min(int(max_structures), SAXS_MAX_STRUCTURES)
+    q = _host_array(fn, "q", q, np.float64).astype(np.float64)
+    if q.ndim != 1 or not 1 <= q.size <= SAXS_MAX_Q:
+        raise HipLibraryError(f"{fn}: q {q.shape}, expected [Q] with 1 <= Q <= {SAXS_MAX_Q}")
+    if not (np.isfinite(q) & (q >= 0.0)).all():
+        raise HipLibraryError(f"{fn}: q must be finite and >= 0")
+    Q = q.size
+    table = np.ones((1, Q)) if table is None else _host_array(fn, "table", table, np.float64).astype(np.float64)
+    if table.ndim != 2 or table.shape[1] != Q or not 1 <= table.shape[0] <= SAXS_MAX_TYPES:
+        raise HipLibraryError(f"{fn}: table {table.shape}, expected [n_types, {Q}] with 1 <= n_types <= {SAXS_MAX_TYPES}")
+    if not np.isfinite(table).all():
+        raise HipLibraryError(f"{fn}: table must be finite")
+    types = np.zeros(L, dtype=np.int32) if types is None else _host_array(fn, "types", types, np.int32)
+    if types.shape != (L,):
+        raise HipLibraryError(f"{fn}: types {types.shape} for {L} residues")
+    if types.size and (int(types.min()) < 0 or int(types.max()) >= table.shape[0]):
+        raise HipLibraryError(f"{fn}: types must lie in 0 .. {table.shape[0] - 1}, got {int(types.min())} .. {int(types.max())}")
+    _req(ca, name="ca")
+    dev = ca.device
+    q_d, table_d = torch.from_numpy(np.ascontiguousarray(q)).to(dev), torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+    types_d = torch.from_numpy(np.ascontiguousarray(types.astype(np.int32))).to(dev)
+    lib = load_library()
+    intensity = torch.empty(R, Q, dtype=torch.float64, device=dev)
+    inv_r_mean = torch.empty(R, dtype=torch.float64, device=dev)
+    for n, p_ca, *p_out in _row_chunks(R, rows, ca, intensity, inv_r_mean):
+        _check(lib.s2s_ca_scattering(p_ca, n, L, _p(q_d), Q, _p(types_d), _p(table_d), table.shape[0], *p_out, _stream()), "s2s_ca_scattering")
+    return intensity, inv_r_mean
 
 
 def cluster_adjacency(values: torch.Tensor, cutoff: float, at_least: bool = False, row0: int = 0, adj: Optional[torch.Tensor] = None,
