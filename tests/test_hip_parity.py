@@ -651,20 +651,23 @@ def test_pair_kernels_many_tiles_per_workgroup(net_rough, mode, monkeypatch):
             assert torch.equal(out2, out) and torch.equal(bias2, bias) and torch.equal(pz2, pz)
     check(f"edge transition {mode}, 1024 tiles: max |out - float64|", float(max((plain.double() - ref).abs().max(), (out.double() - ref).abs().max())), 1.5e-5)
     assert rel(bias, ipa1.linear_b(out).permute(0, 3, 1, 2)) < 5e-6 and rel(pz, ipa1.down_z(out)) < 5e-6
-    # edge embedding: both kernels agree over many tiles (the fp32 kernel is one-shot per tile)
+    # edge embedding over many tiles: each arithmetic against the float64 statement of the reference formula (tests/ref_embed.py),
+    # on CA clear of the distogram's bin edges (every correct float32 distance picks the same bin): no differing pair is allowed
+    import embed_cases
+    import ref_embed
+
     emb = net_rough.embedder
     ridx = torch.arange(N)[None].repeat(B, 1)
-    args = dict(residue_idx=ridx, t=torch.full((B,), 0.4), fixed_mask=torch.zeros(B, N).to(DEV),
-                self_conditioning_ca=(torch.randn(B, N, 3, generator=gen) * 8).to(DEV))
-    res = {}
-    if mode == "f32":
-        return
-    for md in MODES:
-        with use_arith(net_rough, md):
-            res[md] = emb(**args, next_proj=net_rough.translator.trunk["ipa_0"].pair_proj_weights())
-    d = (res["f16x3"][1] - res["f32"][1]).abs().amax(-1)
-    assert (d > 2e-5).sum() <= 4, ((d > 2e-5).sum(), d.max())   # a distogram-edge pair may flip bins (see the golden test)
-    assert rel(res["f16x3"][2][0], res["f32"][2][0]) < 5e-6 and rel(res["f16x3"][2][1], res["f32"][2][1]) < 5e-6
+    ca, _ = embed_cases.clear_of_bin_edges(torch.randn(B, N, 3, generator=gen) * 8, gen)
+    t, fixed = torch.full((B,), 0.4), torch.zeros(B, N)
+    sd = synth_sd(0, 0.02)
+    with use_arith(net_rough, mode):
+        node_e, edge_e, (bias_e, pz_e) = emb(residue_idx=ridx, t=t, fixed_mask=fixed.to(DEV), self_conditioning_ca=ca.to(DEV),
+                                            next_proj=net_rough.translator.trunk["ipa_0"].pair_proj_weights())
+    node64, edge64 = ref_embed.embedding64(sd, ridx, t, fixed, ca, device=DEV)
+    bias64, pz64 = ref_embed.pair_projection64(sd, embed_cases.IPA0, edge64)
+    for what, got, want in (("node", node_e, node64), ("edge", edge_e, edge64), ("attn_bias", bias_e, bias64), ("pair_z", pz_e, pz64)):
+        check(f"edge embedding {mode}, 1024 tiles: max |{what} - float64|", float((got.double() - want).abs().max()), embed_cases.bound(sd, what, mode))
 
 
 def test_torch_ops_registration(net_rough):
