@@ -23,13 +23,17 @@ ensemble's curve against the measured ``DIR/<target>.dat`` (columns q in 1/Angst
 import logging
 import os
 import sys
+from functools import partial
+from typing import Callable, NamedTuple
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("PROJECT_ROOT", ROOT)
 
+from str2str_amd.metrics import metrics  # noqa: E402
 from str2str_amd.utils import config as C  # noqa: E402
 
 log = logging.getLogger("str2str_amd.eval")
@@ -78,8 +82,6 @@ CLUSTER_COLUMNS = ("n_clusters", "top1_population", "top5_population", "n_single
 
 def cluster_summary(sizes):
     """One row of the clusters csv from the non-increasing cluster sizes: populations are fractions of the ensemble."""
-    import numpy as np
-
     sizes = np.asarray(sizes, dtype=np.int64)
     total = float(sizes.sum())
     return {"n_clusters": int(len(sizes)), "top1_population": np.around(sizes[:1].sum() / total, decimals=4),
@@ -88,9 +90,13 @@ def cluster_summary(sizes):
 
 SS_COLUMNS = ("ss_helix", "ss_strand", "ss_helix_target", "ss_strand_target", "ss_mae", "js_rama")
 SS_CLASSES = ("helix", "strand", "other")
+CONTACT_COLUMNS = ("q_mean", "q_mean_target", "js_q", "contact_mae", "rco", "rco_target")
+SASA_COLUMNS = ("sasa_mean", "sasa_mean_target", "js_sasa", "sasa_mae")
+SAXS_COLUMNS = ("saxs_mae", "rh_mean", "rh_mean_target", "js_rh")
 
 
 def _switch(name, value) -> bool:
+    """``+<name>=...`` as a bool: absent, null and false leave everything as it was."""
     if value is None or isinstance(value, bool):
         return bool(value)
     if isinstance(value, str) and value.strip().lower() in ("true", "false", "1", "0", "yes", "no"):
@@ -98,128 +104,114 @@ def _switch(name, value) -> bool:
     raise ValueError(f"{name} {value!r}: expected true or false")
 
 
-def secondary_structure_switch(value) -> bool:
-    """``+secondary_structure=...`` as a bool: absent, null and false leave everything as it was."""
-    return _switch("secondary_structure", value)
+def _backbones(what, pred_file, target_file):
+    """-> ({"pred": atoms [R, L, 5, 3], "target": the same}, aatype, residue_index) of one target, the sequence being the samples'.  A
+    target without a full backbone (a CA trace) is warned about and left out: its columns stay NaN."""
+    from str2str_amd.common.pdb_utils import extract_backbone_atoms
+
+    atoms, aatype, residue_index = extract_backbone_atoms(pred_file)
+    both = {"pred": atoms}
+    try:
+        t_atoms = extract_backbone_atoms(target_file)[0]
+        if t_atoms.shape[1] != atoms.shape[1]:
+            raise ValueError(f"{t_atoms.shape[1]} residues for the samples' {atoms.shape[1]}")
+        both["target"] = t_atoms
+    except ValueError as e:
+        log.warning(f"{what} of the target {target_file}: {e}")
+    return both, aatype, residue_index
 
 
-CONTACT_COLUMNS = ("q_mean", "q_mean_target", "js_q", "contact_mae", "rco", "rco_target")
+def _row(columns, values):
+    """``columns`` filled with ``values`` from the left; NaN in those left over (the ones that need a target ensemble there is none of)."""
+    return {**dict.fromkeys(columns, float("nan")), **dict(zip(columns, values))}
 
 
-def contacts_switch(value) -> bool:
-    """``+contacts=...`` as a bool: absent, null and false leave everything as it was."""
-    return _switch("contacts", value)
+def _residue_table(residue_index, names, per_residue):
+    """residue_index, then pred_<name> and target_<name> for every name out of {k: [len(names), L]}, rounded to 4 decimals (NaN for an
+    ensemble that is not there)."""
+    return {"residue_index": residue_index,
+            **{f"{k}_{c}": np.around(per_residue[k][q], decimals=4) if k in per_residue else np.full(len(residue_index), np.nan)
+               for k in ("pred", "target") for q, c in enumerate(names)}}
 
 
-def contacts_row(ca):
-    """One row of the contacts csv (CONTACT_COLUMNS) and the table of contact probabilities (i, j, p_pred, p_target: every pair i < j with
-    either above 0) of one target from its CA ensembles {"pred": [R, L, 3], "target": [Rt, L, 3]}.  The native of Q is the first structure
-    of the target ensemble."""
-    import numpy as np
+def secondary_structure_row(t):
+    """One row of the ss csv and the per-residue propensities of both ensembles of the target ``t``."""
+    both, aatype, residue_index = _backbones("secondary structure", t.pred_file, t.target_file)
+    res = {k: metrics.secondary_structure_and_torsions(v, aatype, residue_index) for k, v in both.items()}   # the one launch per ensemble
+    prop = {k: metrics._propensity(r[0].ss) for k, r in res.items()}
+    helix, strand = metrics.ss_content_of(prop)
+    values = (helix["pred"], strand["pred"])
+    if "target" in both:
+        js_rama = metrics.js_of_histograms({k: metrics._rama_histogram(*r[1:]) for k, r in res.items()})
+        values += (helix["target"], strand["target"], metrics.ss_mae_of(prop)["pred"], js_rama["pred"])
+    return _row(SS_COLUMNS, values), _residue_table(residue_index, SS_CLASSES, {k: p.T for k, p in prop.items()})
 
-    from str2str_amd.metrics import metrics
 
-    q = metrics.mean_q(ca, ref_key="target")
-    rco = {k: np.around(float(metrics.contact_order(v).mean()), decimals=4) for k, v in ca.items()}
-    row = {"q_mean": q["pred"], "q_mean_target": q["target"], "js_q": metrics.js_q(ca, ref_key="target")["pred"],
-           "contact_mae": metrics.contact_mae(ca, ref_key="target")["pred"], "rco": rco["pred"], "rco_target": rco["target"]}
-    p = {k: metrics.contact_map(v) for k, v in ca.items()}
+def contacts_row(t):
+    """One row of the contacts csv and the table of contact probabilities (every pair i < j with either above 0) of both CA ensembles of
+    the target ``t``.  The native of Q is the first structure of the target ensemble."""
+    native = metrics.native_contacts(t.ca["target"][0])
+    q = {k: metrics.q_of_contacts(v, *native) for k, v in t.ca.items()}
+    p = {k: metrics.contact_map(v) for k, v in t.ca.items()}
+    q_mean = metrics.mean_of_values(q)
+    rco = metrics.mean_of_values({k: metrics.contact_order(v) for k, v in t.ca.items()})
+    row = (q_mean["pred"], q_mean["target"], metrics.js_q_of(q)["pred"], metrics.contact_mae_of(p)["pred"], rco["pred"], rco["target"])
     i, j = np.nonzero(np.triu((p["pred"] > 0) | (p["target"] > 0)))
-    return row, {"i": i, "j": j, "p_pred": np.around(p["pred"][i, j], decimals=4), "p_target": np.around(p["target"][i, j], decimals=4)}
+    return dict(zip(CONTACT_COLUMNS, row)), {"i": i, "j": j, "p_pred": np.around(p["pred"][i, j], decimals=4), "p_target": np.around(p["target"][i, j], decimals=4)}
 
 
-SASA_COLUMNS = ("sasa_mean", "sasa_mean_target", "js_sasa", "sasa_mae")
-
-
-def sasa_switch(value) -> bool:
-    """``+sasa=...`` as a bool: absent, null and false leave everything as it was."""
-    return _switch("sasa", value)
-
-
-def sasa_row(pred_file, target_file, log=log):
-    """One row of the sasa csv (SASA_COLUMNS) and the per-residue means {"pred": (sasa [L], relative [L]), "target": the same or None} of
-    one target.  A target without a full backbone (a CA trace) leaves NaN in the columns that need it."""
-    import numpy as np
-
-    from str2str_amd.common.pdb_utils import extract_backbone_atoms
-    from str2str_amd.metrics import metrics
-
-    atoms, aatype, residue_index = extract_backbone_atoms(pred_file)
-    both = {"pred": atoms}
-    try:
-        t_atoms, _, _ = extract_backbone_atoms(target_file)
-        if t_atoms.shape[1] != atoms.shape[1]:
-            raise ValueError(f"{t_atoms.shape[1]} residues for the samples' {atoms.shape[1]}")
-        both["target"] = t_atoms
-    except ValueError as e:
-        log.warning(f"solvent accessibility of the target {target_file}: {e}")
-    row = dict.fromkeys(SASA_COLUMNS, float("nan"))
-    per_res = {k: (metrics.solvent_accessibility(v, aatype, residue_index).per_residue.mean(0),
-                   metrics.relative_accessibility(v, aatype, residue_index).mean(0)) for k, v in both.items()}
-    mean = metrics.mean_sasa(both, aatype, residue_index)
-    row["sasa_mean"] = mean["pred"]
+def sasa_row(t):
+    """One row of the sasa csv and the per-residue mean surface and mean relative accessibility of both ensembles of the target ``t``."""
+    both, aatype, residue_index = _backbones("solvent accessibility", t.pred_file, t.target_file)
+    res = {k: metrics.accessibility(v, aatype, residue_index) for k, v in both.items()}                      # the one launch on the chains per ensemble
+    total, relative = {k: r[0].total for k, r in res.items()}, {k: r[1].mean(0) for k, r in res.items()}
+    mean = metrics.mean_of_values(total)
+    values = (mean["pred"],)
     if "target" in both:
-        row["sasa_mean_target"] = mean["target"]
-        row["js_sasa"] = metrics.js_sasa(both, ref_key="target", aatype=aatype, residue_index=residue_index)["pred"]
-        row["sasa_mae"] = np.around(float(np.abs(per_res["pred"][1] - per_res["target"][1]).mean()), decimals=4)
-    return row, {"pred": per_res["pred"], "target": per_res.get("target")}, residue_index
+        values += (mean["target"], metrics.js_of_values(total)["pred"], metrics.against_reference(relative)["pred"])
+    return _row(SASA_COLUMNS, values), _residue_table(residue_index, ("sasa", "relative"), {k: (r[0].per_residue.mean(0), relative[k]) for k, r in res.items()})
 
 
-SAXS_COLUMNS = ("saxs_mae", "rh_mean", "rh_mean_target", "js_rh")
-
-
-def saxs_switch(value) -> bool:
-    """``+saxs=...`` as a bool: absent, null and false leave everything as it was."""
-    return _switch("saxs", value)
-
-
-def saxs_row(ca, data_file=None):
-    """One row of the saxs csv (SAXS_COLUMNS; with ``data_file``, a path, also ``saxs_chi2``) and the table of the curves (q, i_pred,
-    i_target on metrics.SAXS_Q_GRID) of one target from its CA ensembles {"pred": [R, L, 3], "target": [Rt, L, 3]}.  ``saxs_chi2`` is the
-    reduced chi^2 of the sampled ensemble's curve, on the measured file's own q grid and scaled to it by least squares, and NaN where the
-    file does not exist."""
-    import numpy as np
-
-    from str2str_amd.metrics import metrics
-
-    q = metrics.SAXS_Q_GRID
-    curve = {k: metrics.ensemble_saxs(v, q) for k, v in ca.items()}
-    rh = metrics.mean_rh(ca)
-    row = {"saxs_mae": np.around(float((np.abs(curve["pred"] - curve["target"]) / curve["target"]).mean()), decimals=4),
-           "rh_mean": rh["pred"], "rh_mean_target": rh["target"], "js_rh": metrics.js_rh(ca, ref_key="target")["pred"]}
-    if data_file is not None:
+def saxs_row(t):
+    """One row of the saxs csv (with a directory of measured curves also ``saxs_chi2``: the reduced chi^2 of the sampled ensemble's curve
+    on the measured file's own q grid, scaled to it by least squares; NaN where the file does not exist) and the curves of both CA
+    ensembles of the target ``t`` on metrics.SAXS_Q_GRID."""
+    res = {k: metrics.saxs_profile_and_rh(v, metrics.SAXS_Q_GRID) for k, v in t.ca.items()}                   # the one launch per ensemble
+    curve, rh = {k: metrics.mean_curve(r[0]) for k, r in res.items()}, {k: r[1] for k, r in res.items()}
+    rh_mean = metrics.mean_of_values(rh)
+    row = dict(zip(SAXS_COLUMNS, (metrics.saxs_mae_of(curve)["pred"], rh_mean["pred"], rh_mean["target"], metrics.js_of_values(rh)["pred"])))
+    if t.saxs_file is not None:
         row["saxs_chi2"] = float("nan")
-        if os.path.isfile(data_file):
-            q_exp, i_exp, sigma = metrics.read_saxs_dat(data_file)
-            row["saxs_chi2"] = np.around(metrics.saxs_chi2(metrics.ensemble_saxs(ca["pred"], q_exp), i_exp, sigma)[0], decimals=4)
-    return row, {"q": q, "i_pred": np.around(curve["pred"], decimals=4), "i_target": np.around(curve["target"], decimals=4)}
+        if os.path.isfile(t.saxs_file):
+            q_exp, i_exp, sigma = metrics.read_saxs_dat(t.saxs_file)
+            row["saxs_chi2"] = np.around(metrics.saxs_chi2(metrics.ensemble_saxs(t.ca["pred"], q_exp), i_exp, sigma)[0], decimals=4)
+    return row, {"q": metrics.SAXS_Q_GRID, "i_pred": np.around(curve["pred"], decimals=4), "i_target": np.around(curve["target"], decimals=4)}
 
 
-def secondary_structure_row(pred_file, target_file, log=log):
-    """One row of the ss csv (SS_COLUMNS) and the per-residue propensities {"pred": [L, 3], "target": [L, 3] or None} of one target.  A
-    target without a full backbone (a CA trace) leaves NaN in the columns that need it."""
-    import numpy as np
+class Report(NamedTuple):
+    """An optional report of ``evaluate_prediction``: ``+<name>=true`` switches it on, ``<name>/<target>.csv`` receives the table of every
+    target and ``<prefix>_<tag>_<mmdd-HH-MM>.csv`` one row per target, with the mean row where ``mean_row`` says so."""
+    name: str
+    prefix: str
+    columns: tuple
+    row: Callable          # (the target: its files and CA ensembles) -> (row {column: value}, table {column: values})
+    mean_row: bool
 
-    from str2str_amd.common.pdb_utils import extract_backbone_atoms
-    from str2str_amd.metrics import metrics
 
-    atoms, aatype, residue_index = extract_backbone_atoms(pred_file)
-    both = {"pred": atoms}
-    try:
-        t_atoms, t_aatype, t_index = extract_backbone_atoms(target_file)
-        if t_atoms.shape[1] != atoms.shape[1]:
-            raise ValueError(f"{t_atoms.shape[1]} residues for the samples' {atoms.shape[1]}")
-        both["target"] = t_atoms
-    except ValueError as e:
-        log.warning(f"secondary structure of the target {target_file}: {e}")
-    row = dict.fromkeys(SS_COLUMNS, float("nan"))
-    prop = metrics.ss_propensity(both, aatype, residue_index)
-    row["ss_helix"], row["ss_strand"] = (np.around(float(prop["pred"][:, q].mean()), decimals=4) for q in (0, 1))
-    if "target" in both:
-        row["ss_helix_target"], row["ss_strand_target"] = (np.around(float(prop["target"][:, q].mean()), decimals=4) for q in (0, 1))
-        row["ss_mae"] = np.around(float((0.5 * np.abs(prop["pred"] - prop["target"]).sum(1)).mean()), decimals=4)
-        row["js_rama"] = metrics.js_rama(both, ref_key="target", residue_index=residue_index)["pred"]
-    return row, {"pred": prop["pred"], "target": prop.get("target")}, residue_index
+REPORTS = (Report("secondary_structure", "ss", SS_COLUMNS, secondary_structure_row, False), Report("contacts", "contacts", CONTACT_COLUMNS, contacts_row, True),
+           Report("sasa", "sasa", SASA_COLUMNS, sasa_row, True), Report("saxs", "saxs", SAXS_COLUMNS, saxs_row, True))
+secondary_structure_switch, contacts_switch, sasa_switch, saxs_switch = (partial(_switch, r.name) for r in REPORTS)
+
+
+def _write_summary(output_dir, prefix, tag, rows, columns, mean_row):
+    """``<prefix>_<tag>_<mmdd-HH-MM>.csv``: one row per target."""
+    import pandas as pd
+    from time import strftime
+
+    frame = pd.DataFrame.from_dict(rows, orient="index", columns=list(columns))
+    if mean_row:
+        frame.loc["mean"] = np.around(frame.mean(), decimals=4)
+    frame.to_csv(os.path.join(output_dir, f"{prefix}_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
 
 
 def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None, cluster_cutoff=None,
@@ -228,31 +220,27 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's).
     ``cluster_cutoff`` (A; None: nothing of this happens): the ``pred`` ensemble of every target is clustered by ``metrics.cluster_rmsd``;
     ``clusters/<target>.pdb`` receives the centres' MODELs, most populated first, and ``clusters_<tag>_<mmdd-HH-MM>.csv`` one row per
-    target (CLUSTER_COLUMNS), both next to the metrics csv.  ``secondary_structure`` (true; otherwise nothing of this happens): the
-    states of the ``pred`` and the ``target`` ensemble of every target; ``ss_<tag>_<mmdd-HH-MM>.csv`` receives one row per target
-    (SS_COLUMNS) and ``secondary_structure/<target>.csv`` the per-residue propensities of both.  ``contacts`` (true; otherwise nothing of
-    this happens): ``contacts_<tag>_<mmdd-HH-MM>.csv`` receives one row per target (CONTACT_COLUMNS) and the mean row, and
-    ``contacts/<target>.csv`` the contact probabilities of both ensembles.  ``sasa`` (true; otherwise nothing of this happens):
-    ``sasa_<tag>_<mmdd-HH-MM>.csv`` receives one row per target (SASA_COLUMNS) and the mean row, and ``sasa/<target>.csv`` the per-residue
-    mean surface and mean relative accessibility of both ensembles.  ``saxs`` (true; otherwise nothing of this happens):
-    ``saxs_<tag>_<mmdd-HH-MM>.csv`` receives one row per target (SAXS_COLUMNS, and ``saxs_chi2`` against ``<saxs_data>/<target>.dat`` when
-    the directory ``saxs_data`` is given) and the mean row, and ``saxs/<target>.csv`` the scattering curves of both ensembles."""
+    target (CLUSTER_COLUMNS), both next to the metrics csv.  ``secondary_structure``, ``contacts``, ``sasa``, ``saxs`` (true; otherwise
+    nothing of it happens): the REPORTS on the ``pred`` and the ``target`` ensemble of every target.  Next to the metrics csv,
+    ``ss_<tag>_<mmdd-HH-MM>.csv`` (SS_COLUMNS) and ``secondary_structure/<target>.csv`` receive the states' content and the per-residue
+    propensities; ``contacts_...csv`` (CONTACT_COLUMNS) and ``contacts/<target>.csv`` the native-contact and contact-order summaries and
+    the contact probabilities; ``sasa_...csv`` (SASA_COLUMNS) and ``sasa/<target>.csv`` the surface summaries and the per-residue mean
+    surface and mean relative accessibility; ``saxs_...csv`` (SAXS_COLUMNS, and ``saxs_chi2`` against ``<saxs_data>/<target>.dat`` when
+    the directory ``saxs_data`` is given) and ``saxs/<target>.csv`` the scattering summaries and the curves.  All but the ss csv end
+    with the mean row."""
     columns = metric_columns(extra_metrics)
-    secondary_structure = secondary_structure_switch(secondary_structure)
-    contacts = contacts_switch(contacts)
-    sasa = sasa_switch(sasa)
-    saxs = saxs_switch(saxs)
-    if saxs_data is not None and not saxs:
+    switches = dict(secondary_structure=secondary_structure, contacts=contacts, sasa=sasa, saxs=saxs)
+    reports = [r for r in REPORTS if _switch(r.name, switches[r.name])]
+    if saxs_data is not None and not _switch("saxs", saxs):
         raise ValueError(f"saxs_data {saxs_data}: needs saxs=true")
     if cluster_cutoff is not None and not 0.0 < float(cluster_cutoff) < float("inf"):
         raise ValueError(f"cluster_cutoff {cluster_cutoff}: expected a positive finite RMSD in Angstrom")
     from time import strftime
+    from types import SimpleNamespace
 
-    import numpy as np
     import pandas as pd
 
     from str2str_amd.common.pdb_utils import extract_backbone_atoms, extract_backbone_coords, select_pdb_models
-    from str2str_amd.metrics import metrics
 
     if target_dir is None or not os.path.isdir(target_dir):
         log.warning(f"target_dir {target_dir} does not exist. Skip evaluation.")
@@ -266,12 +254,12 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
            "div_rmsd": metrics.diversity_rmsd, "div_tm": metrics.diversity_tm, "div_lddt": metrics.diversity_lddt}
     coverage = {"rmsd": metrics.coverage_rmsd, "tm": metrics.coverage_tm, "lddt": metrics.coverage_lddt}
     eval_res = {k: {} for k in columns}
-    clusters, ss_rows, contact_rows, sasa_rows, saxs_rows = {}, {}, {}, {}, {}
+    clusters, rows = {}, {r.name: {} for r in reports}
     for target in targets:
-        pred_file = os.path.join(pred_dir, f"{target}.pdb")
+        pred_file, target_file = os.path.join(pred_dir, f"{target}.pdb"), os.path.join(target_dir, f"{target}.pdb")
         if not os.path.isfile(pred_file):
             continue
-        ca = {"target": extract_backbone_coords(os.path.join(target_dir, f"{target}.pdb")), "pred": extract_backbone_coords(pred_file)}
+        ca = {"target": extract_backbone_coords(target_file), "pred": extract_backbone_coords(pred_file)}
         shared = {}                            # what several columns read: computed once per target, when the first of them asks
         for name in columns:
             family, _, part = name.rpartition("_")
@@ -296,51 +284,19 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
             res = metrics.cluster_rmsd(ca["pred"], float(cluster_cutoff))
             select_pdb_models(pred_file, res.centres, os.path.join(output_dir, "clusters", f"{target}.pdb"))
             clusters[target] = cluster_summary(res.sizes)
-        if secondary_structure:
-            ss_rows[target], prop, numbers = secondary_structure_row(pred_file, os.path.join(target_dir, f"{target}.pdb"))
-            table = {"residue_index": numbers}
-            for k in ("pred", "target"):
-                for q, c in enumerate(SS_CLASSES):
-                    table[f"{k}_{c}"] = np.full(len(numbers), np.nan) if prop[k] is None else np.around(prop[k][:, q], decimals=4)
-            os.makedirs(os.path.join(output_dir, "secondary_structure"), exist_ok=True)
-            pd.DataFrame(table).to_csv(os.path.join(output_dir, "secondary_structure", f"{target}.csv"), index=False, sep="\t")
-        if contacts:
-            contact_rows[target], table = contacts_row(ca)
-            os.makedirs(os.path.join(output_dir, "contacts"), exist_ok=True)
-            pd.DataFrame(table).to_csv(os.path.join(output_dir, "contacts", f"{target}.csv"), index=False, sep="\t")
-        if sasa:
-            sasa_rows[target], per_res, numbers = sasa_row(pred_file, os.path.join(target_dir, f"{target}.pdb"))
-            table = {"residue_index": numbers}
-            for k in ("pred", "target"):
-                for q, c in enumerate(("sasa", "relative")):
-                    table[f"{k}_{c}"] = np.full(len(numbers), np.nan) if per_res[k] is None else np.around(per_res[k][q], decimals=4)
-            os.makedirs(os.path.join(output_dir, "sasa"), exist_ok=True)
-            pd.DataFrame(table).to_csv(os.path.join(output_dir, "sasa", f"{target}.csv"), index=False, sep="\t")
-        if saxs:
-            saxs_rows[target], table = saxs_row(ca, None if saxs_data is None else os.path.join(str(saxs_data), f"{target}.dat"))
-            os.makedirs(os.path.join(output_dir, "saxs"), exist_ok=True)
-            pd.DataFrame(table).to_csv(os.path.join(output_dir, "saxs", f"{target}.csv"), index=False, sep="\t")
+        files = SimpleNamespace(ca=ca, pred_file=pred_file, target_file=target_file,
+                                saxs_file=None if saxs_data is None else os.path.join(str(saxs_data), f"{target}.dat"))
+        for r in reports:
+            rows[r.name][target], table = r.row(files)
+            os.makedirs(os.path.join(output_dir, r.name), exist_ok=True)
+            pd.DataFrame(table).to_csv(os.path.join(output_dir, r.name, f"{target}.csv"), index=False, sep="\t")
     df = pd.DataFrame.from_dict(eval_res)
     df.loc["mean"] = np.around(df.mean(), decimals=4)
     df.to_csv(os.path.join(output_dir, f"metrics_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
     if cluster_cutoff is not None:
-        pd.DataFrame.from_dict(clusters, orient="index", columns=list(CLUSTER_COLUMNS)).to_csv(
-            os.path.join(output_dir, f"clusters_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
-    if secondary_structure:
-        pd.DataFrame.from_dict(ss_rows, orient="index", columns=list(SS_COLUMNS)).to_csv(
-            os.path.join(output_dir, f"ss_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
-    if contacts:
-        cf = pd.DataFrame.from_dict(contact_rows, orient="index", columns=list(CONTACT_COLUMNS))
-        cf.loc["mean"] = np.around(cf.mean(), decimals=4)
-        cf.to_csv(os.path.join(output_dir, f"contacts_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
-    if sasa:
-        sf = pd.DataFrame.from_dict(sasa_rows, orient="index", columns=list(SASA_COLUMNS))
-        sf.loc["mean"] = np.around(sf.mean(), decimals=4)
-        sf.to_csv(os.path.join(output_dir, f"sasa_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
-    if saxs:
-        xf = pd.DataFrame.from_dict(saxs_rows, orient="index", columns=list(SAXS_COLUMNS) + ([] if saxs_data is None else ["saxs_chi2"]))
-        xf.loc["mean"] = np.around(xf.mean(), decimals=4)
-        xf.to_csv(os.path.join(output_dir, f"saxs_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
+        _write_summary(output_dir, "clusters", tag, clusters, CLUSTER_COLUMNS, False)
+    for r in reports:
+        _write_summary(output_dir, r.prefix, tag, rows[r.name], r.columns + (("saxs_chi2",) if r.name == "saxs" and saxs_data is not None else ()), r.mean_row)
     return df.loc["mean"]
 
 

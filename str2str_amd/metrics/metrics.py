@@ -37,6 +37,7 @@ the comparison with a measured curve.
 from __future__ import annotations
 
 import math
+from functools import partial
 from typing import Callable, NamedTuple
 
 import numpy as np
@@ -66,11 +67,7 @@ def _js(p: np.ndarray, q: np.ndarray) -> float:
 
 def validity(ca_coords_dict, ca_vdw_radius=1.7, allowable_overlap=0.4, k_exclusion=0):
     bar = 2 * ca_vdw_radius - allowable_overlap
-    out = {}
-    for k, v in ca_coords_dict.items():
-        n_clash, _, _ = ops.ca_sample_stats(_dev(v), bar, k_exclusion)
-        out[k] = np.around(1.0 - float((n_clash > 0).double().mean()), decimals=4)
-    return out
+    return {k: np.around(1.0 - float((ops.ca_sample_stats(_dev(v), bar, k_exclusion)[0] > 0).double().mean()), decimals=4) for k, v in ca_coords_dict.items()}
 
 
 def bonding_validity(ca_coords_dict, ref_key="target", eps=1e-6):
@@ -87,6 +84,38 @@ def _weights(weights, ca_coords_dict):
         if w[k].shape != (len(v),):
             raise ValueError(f"weights[{k!r}] has shape {w[k].shape} for {len(v)} samples")
     return w
+
+
+def _host(v, dtype=None) -> np.ndarray:
+    """A tensor on any device, an array or a list as a host array."""
+    return np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=dtype)
+
+
+# ---- summaries of per-structure values: a dict-in / dict-out metric below is "values per structure, per ensemble", then one of these ----
+def against_reference(summaries, ref_key="target", distance=lambda p, ref: np.abs(p - ref).mean()):
+    """{k: an ensemble's histogram or profile} -> {k: ``distance`` from the reference's (default: mean absolute difference; 0.0 if empty)}."""
+    return {**{k: np.around(float(distance(v, summaries[ref_key])) if v.size else 0.0, decimals=4) for k, v in summaries.items() if k != ref_key}, ref_key: 0.0}
+
+
+def js_of_values(values, ref_key="target", n_bins=50, weights=None, value_range=None):
+    """{k: float64 [R_k], a number per structure} -> {k: JS distance from the reference's}: histograms of ``n_bins`` bins over
+    ``value_range`` (None: the reference's smallest to largest value) with per-structure ``weights`` by key and PSEUDO_C."""
+    w = _weights(weights, values)
+    lo, hi = (values[ref_key].min(), values[ref_key].max()) if value_range is None else value_range
+    return js_of_histograms({k: np.histogram(v, bins=n_bins, weights=w[k], range=(lo, hi))[0] + PSEUDO_C for k, v in values.items()}, ref_key)
+
+
+def mean_of_values(values, weights=None):
+    """{k: float64 [R_k], a number per structure} -> {k: their (weighted) mean, rounded to 4 decimals}."""
+    w = _weights(weights, values)
+    return {k: np.around(float(np.average(v, weights=w[k])), decimals=4) for k, v in values.items()}
+
+
+# what js_rama, js_q, ss_mae and saxs_mae are of the histograms, fractions of native contacts, propensities and curves one already has
+js_of_histograms = partial(against_reference, distance=_js)
+js_q_of = partial(js_of_values, value_range=(0.0, 1.0))
+ss_mae_of = partial(against_reference, distance=lambda p, ref: (0.5 * np.abs(p - ref).sum(1)).mean())
+saxs_mae_of = partial(against_reference, distance=lambda c, ref: (np.abs(c - ref) / ref).mean())
 
 
 def js_pwd(ca_coords_dict, ref_key="target", n_bins=50, pwd_offset=3, weights=None):
@@ -108,12 +137,7 @@ def radius_of_gyration(coords):
 def js_rg(ca_coords_dict, ref_key="target", n_bins=50, weights=None):
     w = _weights(weights, ca_coords_dict)
     # the reference's Rg is float64 (float32 squared distances x float64 weights, metrics.py:62-78) and so are its histogram edges
-    rg = {k: np.asarray(radius_of_gyration(v), dtype=np.float64) for k, v in ca_coords_dict.items()}
-    d_min, d_max = rg[ref_key].min(), rg[ref_key].max()
-    binned = {k: np.histogram(v, bins=n_bins, weights=w[k], range=(d_min, d_max))[0] + PSEUDO_C for k, v in rg.items()}
-    out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
-    out[ref_key] = 0.0
-    return out
+    return js_of_values({k: np.asarray(radius_of_gyration(v), dtype=np.float64) for k, v in ca_coords_dict.items()}, ref_key, n_bins, w)
 
 
 def pairwise_distance_ca(coords, k=1) -> np.ndarray:
@@ -179,9 +203,7 @@ def js_tica(ca_coords_dict, ref_key="target", n_bins=50, lagtime=20, return_tic=
     d_min, d_max = ca_dr2d[ref_key].min(axis=0), ca_dr2d[ref_key].max(axis=0)
     binned = {k: np.stack([np.histogram(v[:, c], bins=n_bins, weights=w[k], range=(d_min[c], d_max[c]))[0] + PSEUDO_C for c in range(v.shape[1])], 1)
               for k, v in ca_dr2d.items()}      # [n_bins, 2]
-    results = {k: np.around(np.mean([_js(v[:, c], binned[ref_key][:, c]) for c in range(v.shape[1])]), decimals=4)
-               for k, v in binned.items() if k != ref_key}
-    results[ref_key] = 0.0
+    results = against_reference(binned, ref_key, lambda v, ref: np.mean([_js(v[:, c], ref[:, c]) for c in range(v.shape[1])]))
     if return_tic:
         return results, ca_dr2d
     return results
@@ -397,7 +419,12 @@ def fraction_native_contacts(coords, native, soft=True, beta=5.0, lam=1.2, cutof
     x, nat = _dev(coords), _dev(native)[0]
     if nat.shape[0] != x.shape[1]:
         raise ValueError(f"native has {nat.shape[0]} residues for the ensemble's {x.shape[1]}")
-    q_soft, q_hard, _ = ops.ca_native_q(x, *ops.ca_native_contacts(nat, cutoff, min_seq_sep), beta, lam)
+    return q_of_contacts(x, *ops.ca_native_contacts(nat, cutoff, min_seq_sep), soft, beta, lam)
+
+
+def q_of_contacts(coords, pairs, d0, soft=True, beta=5.0, lam=1.2) -> np.ndarray:
+    """``fraction_native_contacts`` against a native contact list one already has (``native_contacts``'s arrays, or device tensors)."""
+    q_soft, q_hard, _ = ops.ca_native_q(_dev(coords), *(torch.as_tensor(t, device="cuda") for t in (pairs, d0)), beta, lam)
     return (q_soft if soft else q_hard).cpu().numpy()
 
 
@@ -405,18 +432,17 @@ def contact_mae(ca_coords_dict, ref_key="target", cutoff=8.0, min_seq_sep=3, wei
     """The mean absolute difference of each ensemble's contact-probability map from the reference ensemble's, over the pairs at least
     ``min_seq_sep`` apart (0.0 when there is none).  ``weights``: per-structure weights by key, as in ``js_pwd``."""
     w = _weights(weights, ca_coords_dict) if weights else {}
-    maps = {k: contact_map(v, cutoff, min_seq_sep, w.get(k)) for k, v in ca_coords_dict.items()}
-    upper = np.triu_indices(maps[ref_key].shape[0], k=min_seq_sep)
-    out = {k: np.around(float(np.abs(m[upper] - maps[ref_key][upper]).mean()) if len(upper[0]) else 0.0, decimals=4)
-           for k, m in maps.items() if k != ref_key}
-    out[ref_key] = 0.0
-    return out
+    return contact_mae_of({k: contact_map(v, cutoff, min_seq_sep, w.get(k)) for k, v in ca_coords_dict.items()}, ref_key, min_seq_sep)
+
+
+def contact_mae_of(maps, ref_key="target", min_seq_sep=3):
+    """``contact_mae`` of contact-probability maps {k: [L, L]} one already has."""
+    return against_reference({k: m[np.triu_indices(len(m), k=min_seq_sep)] for k, m in maps.items()}, ref_key)
 
 
 def _q_by_key(ca_coords_dict, ref_key, native, **q_args):
     """Q of every ensemble against ``native`` (None: the first structure of the reference ensemble) -> {k: float64 [len(v)]}."""
-    native = ca_coords_dict[ref_key][0] if native is None else native
-    return {k: fraction_native_contacts(v, native, **q_args) for k, v in ca_coords_dict.items()}
+    return {k: fraction_native_contacts(v, ca_coords_dict[ref_key][0] if native is None else native, **q_args) for k, v in ca_coords_dict.items()}
 
 
 def js_q(ca_coords_dict, ref_key="target", native=None, n_bins=50, weights=None, **q_args):
@@ -424,22 +450,23 @@ def js_q(ca_coords_dict, ref_key="target", native=None, n_bins=50, weights=None,
     histograms of ``n_bins`` bins over the fixed range [0, 1].  ``native`` [L, 3]: None takes the first structure of the reference
     ensemble; ``q_args``: the arguments of ``fraction_native_contacts``."""
     w = _weights(weights, ca_coords_dict)
-    q = _q_by_key(ca_coords_dict, ref_key, native, **q_args)
-    binned = {k: np.histogram(v, bins=n_bins, weights=w[k], range=(0.0, 1.0))[0] + PSEUDO_C for k, v in q.items()}
-    out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
-    out[ref_key] = 0.0
-    return out
+    return js_q_of(_q_by_key(ca_coords_dict, ref_key, native, **q_args), ref_key, n_bins, w)
 
 
 def mean_q(ca_coords_dict, ref_key="target", native=None, weights=None, **q_args):
     """The (weighted) mean fraction of native contacts of each ensemble; the arguments of ``js_q``."""
     w = _weights(weights, ca_coords_dict)
-    return {k: np.around(float(np.average(v, weights=w[k])), decimals=4) for k, v in _q_by_key(ca_coords_dict, ref_key, native, **q_args).items()}
+    return mean_of_values(_q_by_key(ca_coords_dict, ref_key, native, **q_args), w)
 
 
 # ---- backbone violations: inside each structure (csrc/ensemble_violations.hip; the definition of src/models/loss.py:714-1017, 1237-1314) ----
 GLY = 7                                       # aatype of glycine in the reference's residue order: no CB
 ATOM37_BACKBONE = (0, 1, 2, 4, 3)             # atom37 slots of N, CA, C, O, CB (atom14 slots 0 .. 4)
+
+
+def _atom_exists(aatype: np.ndarray) -> np.ndarray:
+    """aatype [L] -> uint8 [L, 5]: which of N, CA, C, O, CB a residue has (a GLY has no CB)."""
+    return ((np.arange(5) < 4) | (aatype != GLY)[:, None]).astype(np.uint8)
 
 
 class BackboneViolations(NamedTuple):
@@ -481,14 +508,10 @@ def backbone_violations(atoms, aatype=None, residue_index=None, tolerance_factor
     numbered ``residue_index`` [L] (default: 0 .. L - 1; a jump in the numbers is a chain break).  The tolerances are the reference's
     defaults."""
     x = _backbone_dev(atoms)
-    L = x.shape[1]
-    aatype, residue_index = _sequence_arrays("backbone_violations", L, aatype, residue_index)
-    exists = np.ones((L, 5), dtype=np.uint8)
-    exists[aatype == GLY, 4] = 0
-    losses, fractions, per_res, bond_mask, clash_mask, n_pairs = ops.backbone_violations(x, exists, aatype, residue_index, tolerance_factor,
-                                                                                         clash_tolerance, max_structures)
-    losses, fractions = losses.cpu().numpy(), fractions.cpu().numpy()
-    return BackboneViolations(*losses.T, *fractions.T, per_res.cpu().numpy(), bond_mask.cpu().numpy().astype(bool),
+    aatype, residue_index = _sequence_arrays("backbone_violations", x.shape[1], aatype, residue_index)
+    losses, fractions, per_res, bond_mask, clash_mask, n_pairs = ops.backbone_violations(x, _atom_exists(aatype), aatype, residue_index,
+                                                                                         tolerance_factor, clash_tolerance, max_structures)
+    return BackboneViolations(*losses.cpu().numpy().T, *fractions.cpu().numpy().T, per_res.cpu().numpy(), bond_mask.cpu().numpy().astype(bool),
                               clash_mask.cpu().numpy().astype(bool), n_pairs.cpu().numpy())
 
 
@@ -532,8 +555,8 @@ class SecondaryStructure(NamedTuple):
 
 def _sequence_arrays(fn, L, aatype, residue_index):
     """The defaults of the per-sequence arguments: all ALA, numbered 0 .. L - 1."""
-    aatype = np.zeros(L, dtype=np.int64) if aatype is None else np.asarray(aatype.cpu() if torch.is_tensor(aatype) else aatype).reshape(-1)
-    residue_index = np.arange(L) if residue_index is None else np.asarray(residue_index.cpu() if torch.is_tensor(residue_index) else residue_index).reshape(-1)
+    aatype = np.zeros(L, dtype=np.int64) if aatype is None else _host(aatype).reshape(-1)
+    residue_index = np.arange(L) if residue_index is None else _host(residue_index).reshape(-1)
     if aatype.shape != (L,) or residue_index.shape != (L,):
         raise ValueError(f"{fn}: aatype {aatype.shape} and residue_index {residue_index.shape} for {L} residues")
     return aatype, residue_index
@@ -544,10 +567,17 @@ def secondary_structure(atoms, aatype=None, residue_index=None, max_structures=N
     bridges, ladders, bends; the energy threshold alone makes a bond and beta-bulges are not merged: include/str2str_hip.h) of ``atoms``
     [R, L, 5, 3] or atom37 [R, L, 37, 3], for the one sequence ``aatype`` [L] (default: all ALA; a PRO has no amide hydrogen) numbered
     ``residue_index`` [L] (default: 0 .. L - 1; a jump in the numbers is a chain break)."""
+    return secondary_structure_and_torsions(atoms, aatype, residue_index, max_structures)[0]
+
+
+def secondary_structure_and_torsions(atoms, aatype=None, residue_index=None, max_structures=None, fn="secondary_structure"):
+    """One launch -> (what ``secondary_structure`` returns, the two results of ``backbone_torsions``: they do not depend on ``aatype``)."""
     x = _backbone_dev(atoms)
-    aatype, residue_index = _sequence_arrays("secondary_structure", x.shape[1], aatype, residue_index)
-    ss, n_hbonds, energy, partner, _ = ops.secondary_structure(x, aatype, residue_index, max_structures)
-    return SecondaryStructure(ss.cpu().numpy().view("S1"), n_hbonds.cpu().numpy(), energy.cpu().numpy(), partner.cpu().numpy())
+    aatype, residue_index = _sequence_arrays(fn, x.shape[1], aatype, residue_index)
+    ss, n_hbonds, energy, partner, angles = ops.secondary_structure(x, aatype, residue_index, max_structures)
+    conn = np.append(False, np.diff(residue_index.astype(np.int64)) == 1)   # residue i follows i - 1 in the numbering
+    return (SecondaryStructure(ss.cpu().numpy().view("S1"), n_hbonds.cpu().numpy(), energy.cpu().numpy(), partner.cpu().numpy()),
+            angles.cpu().numpy(), np.stack([conn, np.append(conn[1:], False), conn], axis=1))
 
 
 def ss_strings(result) -> list:
@@ -560,13 +590,7 @@ def backbone_torsions(atoms, residue_index=None):
     """-> (angles float64 [R, L, 3]: phi, psi, omega in radians in (-pi, pi], IUPAC sign, omega_i being the bond before residue i;
     mask bool [L, 3]: phi and omega are defined where residue i follows i - 1 in the numbering, psi where i + 1 follows i; an undefined
     angle is 0.0)."""
-    x = _backbone_dev(atoms)
-    L = x.shape[1]
-    _, residue_index = _sequence_arrays("backbone_torsions", L, None, residue_index)
-    angles = ops.secondary_structure(x, np.zeros(L, dtype=np.int64), residue_index)[4].cpu().numpy()
-    conn = np.zeros(L, dtype=bool)
-    conn[1:] = residue_index[1:].astype(np.int64) == residue_index[:-1].astype(np.int64) + 1
-    return angles, np.stack([conn, np.append(conn[1:], False), conn], axis=1)
+    return secondary_structure_and_torsions(atoms, None, residue_index, fn="backbone_torsions")[1:]
 
 
 def _propensity(ss: np.ndarray) -> np.ndarray:
@@ -582,21 +606,21 @@ def ss_propensity(atoms_dict, aatype=None, residue_index=None):
 
 def ss_content(atoms_dict, aatype=None, residue_index=None):
     """-> (helix, strand): per ensemble the mean fraction of residues in helix (H, G, I) and in strand (E, B)."""
-    prop = ss_propensity(atoms_dict, aatype, residue_index)
-    return ({k: np.around(float(p[:, 0].mean()), decimals=4) for k, p in prop.items()},
-            {k: np.around(float(p[:, 1].mean()), decimals=4) for k, p in prop.items()})
+    return ss_content_of(ss_propensity(atoms_dict, aatype, residue_index))
+
+
+def ss_content_of(prop):
+    """``ss_content`` of propensities {k: [L, 3]} one already has."""
+    return tuple({k: np.around(float(p[:, c].mean()), decimals=4) for k, p in prop.items()} for c in (0, 1))
 
 
 def ss_mae(atoms_dict, ref_key="target", aatype=None, residue_index=None):
     """Per ensemble the mean over the residues of half the L1 distance of its (helix, strand, other) propensities from the reference
     ensemble's: 0 for equal propensities, 1 where every residue is in another class."""
-    prop = ss_propensity(atoms_dict, aatype, residue_index)
-    out = {k: np.around(float((0.5 * np.abs(p - prop[ref_key]).sum(1)).mean()), decimals=4) for k, p in prop.items() if k != ref_key}
-    out[ref_key] = 0.0
-    return out
+    return ss_mae_of(ss_propensity(atoms_dict, aatype, residue_index), ref_key)
 
 
-def _rama_histogram(angles: np.ndarray, mask: np.ndarray, n_bins: int) -> np.ndarray:
+def _rama_histogram(angles: np.ndarray, mask: np.ndarray, n_bins: int = 36) -> np.ndarray:
     """The phi / psi histogram over [-pi, pi)^2 of every structure's residues with both angles defined, flattened, with PSEUDO_C."""
     both = mask[:, 0] & mask[:, 1]
     phi, psi = angles[:, both, 0].reshape(-1), angles[:, both, 1].reshape(-1)
@@ -608,10 +632,7 @@ def _rama_histogram(angles: np.ndarray, mask: np.ndarray, n_bins: int) -> np.nda
 def js_rama(atoms_dict, ref_key="target", n_bins=36, residue_index=None):
     """Jensen-Shannon distance of the Ramachandran (phi, psi) histograms, n_bins x n_bins over [-pi, pi)^2, pooled over all structures
     and all residues with both angles defined.  The angles come from the device; the histogram tail is numpy, as for ``js_rg``."""
-    binned = {k: _rama_histogram(*backbone_torsions(v, residue_index), n_bins) for k, v in atoms_dict.items()}
-    out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
-    out[ref_key] = 0.0
-    return out
+    return js_of_histograms({k: _rama_histogram(*backbone_torsions(v, residue_index), n_bins) for k, v in atoms_dict.items()}, ref_key)
 
 
 # ---- solvent accessibility (csrc/ensemble_sasa.hip; Shrake & Rupley 1973, include/str2str_hip.h has the definition) ----
@@ -626,29 +647,13 @@ class SolventAccessibility(NamedTuple):
     total: np.ndarray
 
 
-def _sasa_inputs(fn, atoms, aatype, radii):
-    """-> (device atoms [R, L, 5, 3], atom_exists uint8 [L, 5]: a GLY has no CB, radii float64 [L, 5]: SASA_RADII by default)."""
-    x = _backbone_dev(atoms)
-    L = x.shape[1]
-    aatype, _ = _sequence_arrays(fn, L, aatype, None)
-    exists = np.ones((L, 5), dtype=np.uint8)
-    exists[aatype == GLY, 4] = 0
-    radii = np.tile(np.asarray(SASA_RADII, dtype=np.float64), (L, 1)) if radii is None else np.asarray(radii.cpu() if torch.is_tensor(radii) else radii, dtype=np.float64)
-    if radii.shape != (L, 5):
-        raise ValueError(f"{fn}: radii {radii.shape} for {L} residues, expected [{L}, 5]")
-    return x, exists, radii
-
-
 def solvent_accessibility(atoms, aatype=None, residue_index=None, radii=None, probe=1.4, n_points=96, max_structures=None) -> SolventAccessibility:
     """How much of each residue, and of the chain, does the solvent reach?  Shrake and Rupley's surface (``n_points`` test points on every
     atom's sphere of radius ``radii + probe``; include/str2str_hip.h) of ``atoms`` [R, L, 5, 3] or atom37 [R, L, 37, 3], for the one
     sequence ``aatype`` [L] (default: all ALA; a GLY has no CB).  ``radii`` [L, 5]: SASA_RADII for every residue by default.
     ``residue_index`` is accepted like its siblings' and not used: a surface knows no chain breaks.  NOT an all-atom surface: there are no
     side chains beyond CB, so absolute values overstate the exposure of large residues."""
-    x, exists, radii = _sasa_inputs("solvent_accessibility", atoms, aatype, radii)
-    _sequence_arrays("solvent_accessibility", x.shape[1], None, residue_index)
-    counts, per_res, total = ops.backbone_sasa(x, exists, radii, probe, n_points, max_structures)
-    return SolventAccessibility(counts.cpu().numpy(), per_res.cpu().numpy(), total.cpu().numpy())
+    return accessibility(atoms, aatype, residue_index, radii, probe, n_points, max_structures, False, "solvent_accessibility")[0]
 
 
 def relative_accessibility(atoms, aatype=None, residue_index=None, radii=None, probe=1.4, n_points=96, max_structures=None) -> np.ndarray:
@@ -656,10 +661,22 @@ def relative_accessibility(atoms, aatype=None, residue_index=None, radii=None, p
     conformation of its five atoms, the rest of the chain taken away), the share of its own surface that the rest of the chain leaves
     exposed (NaN for a residue none of whose atoms exists).  The denominator comes from the same kernel on the residues as one-residue
     structures.  NOT the relative accessibility against tabulated Gly-X-Gly maxima: no such table is in the tree."""
-    x, exists, radii = _sasa_inputs("relative_accessibility", atoms, aatype, radii)
-    _sequence_arrays("relative_accessibility", x.shape[1], None, residue_index)
+    return accessibility(atoms, aatype, residue_index, radii, probe, n_points, max_structures, True, "relative_accessibility")[1]
+
+
+def accessibility(atoms, aatype=None, residue_index=None, radii=None, probe=1.4, n_points=96, max_structures=None, relative=True, fn="accessibility"):
+    """One launch on the chains -> (what ``solvent_accessibility`` returns, what ``relative_accessibility`` returns or None without ``relative``)."""
+    x = _backbone_dev(atoms)
     R, L = x.shape[:2]
-    in_chain = ops.backbone_sasa(x, exists, radii, probe, n_points, max_structures)[1]
+    aatype, _ = _sequence_arrays(fn, L, aatype, residue_index)
+    exists = _atom_exists(aatype)
+    radii = np.tile(np.asarray(SASA_RADII, dtype=np.float64), (L, 1)) if radii is None else _host(radii, np.float64)
+    if radii.shape != (L, 5):
+        raise ValueError(f"{fn}: radii {radii.shape} for {L} residues, expected [{L}, 5]")
+    counts, in_chain, total = ops.backbone_sasa(x, exists, radii, probe, n_points, max_structures)
+    res = SolventAccessibility(counts.cpu().numpy(), in_chain.cpu().numpy(), total.cpu().numpy())
+    if not relative:
+        return res, None
     alone = torch.empty_like(in_chain)
     kinds, kind_of = np.unique(np.concatenate([radii, exists.astype(np.float64)], axis=1), axis=0, return_inverse=True)
     for q in range(len(kinds)):                                 # the residues that share radii and existing atoms share a launch sequence
@@ -667,58 +684,48 @@ def relative_accessibility(atoms, aatype=None, residue_index=None, radii=None, p
         own = x[:, idx].reshape(-1, 1, 5, 3).contiguous()
         r0 = int(idx[0])
         alone[:, idx] = ops.backbone_sasa(own, exists[r0:r0 + 1], radii[r0:r0 + 1], probe, n_points, max_structures)[1].reshape(R, len(idx))
-    return (in_chain / alone).cpu().numpy()
+    return res, (in_chain / alone).cpu().numpy()
 
 
 def mean_sasa(atoms_dict, aatype=None, residue_index=None, **sasa_args):
-    """Per ensemble the mean total solvent-accessible surface of its structures in square Angstrom; ``sasa_args``: the arguments of
-    ``solvent_accessibility``."""
-    return {k: np.around(float(solvent_accessibility(v, aatype, residue_index, **sasa_args).total.mean()), decimals=4) for k, v in atoms_dict.items()}
+    """Per ensemble the mean total solvent-accessible surface of its structures in square Angstrom; ``sasa_args``: those of ``solvent_accessibility``."""
+    return mean_of_values({k: solvent_accessibility(v, aatype, residue_index, **sasa_args).total for k, v in atoms_dict.items()})
 
 
 def sasa_mae(atoms_dict, ref_key="target", aatype=None, residue_index=None, **sasa_args):
-    """Per ensemble the mean over the residues of the absolute difference of its mean relative accessibility from the reference
-    ensemble's."""
-    rel = {k: relative_accessibility(v, aatype, residue_index, **sasa_args).mean(0) for k, v in atoms_dict.items()}
-    out = {k: np.around(float(np.abs(v - rel[ref_key]).mean()), decimals=4) for k, v in rel.items() if k != ref_key}
-    out[ref_key] = 0.0
-    return out
+    """Per ensemble the mean over the residues of the absolute difference of its mean relative accessibility from the reference ensemble's."""
+    return against_reference({k: relative_accessibility(v, aatype, residue_index, **sasa_args).mean(0) for k, v in atoms_dict.items()}, ref_key)
 
 
 def js_sasa(atoms_dict, ref_key="target", n_bins=50, weights=None, aatype=None, residue_index=None, **sasa_args):
-    """Jensen-Shannon distance of the histograms of the structures' total surface, ``n_bins`` bins over the range of the reference
-    ensemble, as ``js_rg`` does it for the radius of gyration."""
+    """``js_of_values`` of the structures' total surface: histograms of ``n_bins`` bins over the range of the reference ensemble, as in ``js_rg``."""
     w = _weights(weights, atoms_dict)
-    total = {k: solvent_accessibility(v, aatype, residue_index, **sasa_args).total for k, v in atoms_dict.items()}
-    d_min, d_max = total[ref_key].min(), total[ref_key].max()
-    binned = {k: np.histogram(v, bins=n_bins, weights=w[k], range=(d_min, d_max))[0] + PSEUDO_C for k, v in total.items()}
-    out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
-    out[ref_key] = 0.0
-    return out
+    return js_of_values({k: solvent_accessibility(v, aatype, residue_index, **sasa_args).total for k, v in atoms_dict.items()}, ref_key, n_bins, w)
 
 
 # ---- solution scattering (csrc/ensemble_saxs.hip; Debye 1915, Kirkwood 1954; include/str2str_hip.h has the definition) ----
 SAXS_Q_GRID = np.arange(51) / 100.0           # 0.00, 0.01, ..., 0.50 per Angstrom: the grid of eval.py, inside the range of the CA-bead approximation
 
 
-def _saxs_call(coords, q, aatype, form_factors, max_structures):
-    """-> (intensity [R, Q], inv_r_mean [R]) numpy float64: ``ops.ca_scattering`` walked over the q-list in runs of ops.SAXS_MAX_Q (whole
-    tiles, so every column has the bytes of a single call)."""
+def saxs_profile_and_rh(coords, q, aatype=None, form_factors=None, max_structures=None):
+    """-> (what ``saxs_profile`` returns, what ``hydrodynamic_radius`` returns: it depends neither on ``q`` nor on the form factors):
+    ``ops.ca_scattering`` walked over the q-list in runs of ops.SAXS_MAX_Q (whole tiles, so every column has the bytes of a single call)."""
     x = _dev(coords)
-    q = np.asarray(q.cpu() if torch.is_tensor(q) else q, dtype=np.float64)
+    q = _host(q, np.float64)
     if q.ndim != 1 or q.size < 1:
         raise ValueError(f"q has shape {q.shape}, expected [Q] with Q >= 1")
     table = types = None
     if form_factors is not None:
-        table = np.asarray(form_factors.cpu() if torch.is_tensor(form_factors) else form_factors, dtype=np.float64)
+        table = _host(form_factors, np.float64)
         if table.ndim != 2 or table.shape[1] != q.size:
             raise ValueError(f"form_factors has shape {table.shape} for {q.size} q-values, expected [n_types, {q.size}]")
-        types = None if aatype is None else np.asarray(aatype.cpu() if torch.is_tensor(aatype) else aatype)
+        types = None if aatype is None else _host(aatype)
         if types is not None and types.shape != (x.shape[1],):
             raise ValueError(f"aatype has shape {types.shape} for {x.shape[1]} residues")
     runs = [ops.ca_scattering(x, q[k:k + ops.SAXS_MAX_Q], types, None if table is None else table[:, k:k + ops.SAXS_MAX_Q], max_structures)
             for k in range(0, q.size, ops.SAXS_MAX_Q)]
-    return np.concatenate([r[0].cpu().numpy() for r in runs], axis=1), runs[0][1].cpu().numpy()
+    with np.errstate(divide="ignore"):
+        return np.concatenate([r[0].cpu().numpy() for r in runs], axis=1), 1.0 / runs[0][1].cpu().numpy()
 
 
 def saxs_profile(coords, q, aatype=None, form_factors=None, max_structures=None) -> np.ndarray:
@@ -727,27 +734,27 @@ def saxs_profile(coords, q, aatype=None, form_factors=None, max_structures=None)
     point scatterer (f = 1, I(0) = L^2), the usual CA-bead approximation, good for q <~ 0.3 / Angstrom.  A caller with residue form factors
     passes ``form_factors`` [n_types, Q] (any sign: contrast can be negative) and ``aatype`` [L] (the row of every residue; without
     ``form_factors`` it is not used).  NOT here: a hydration shell, an excluded-volume term, a built-in form-factor table, side chains."""
-    return _saxs_call(coords, q, aatype, form_factors, max_structures)[0]
+    return saxs_profile_and_rh(coords, q, aatype, form_factors, max_structures)[0]
 
 
 def ensemble_saxs(coords, q, weights=None, aatype=None, form_factors=None, max_structures=None) -> np.ndarray:
     """The curve of the ensemble -> float64 [Q]: the (``weights`` [R]: weighted) mean of the structures' *intensities*, which is what a
     solution of them scatters."""
-    rows = saxs_profile(coords, q, aatype, form_factors, max_structures)
-    if weights is None:
-        return rows.mean(axis=0)
-    w = np.asarray(weights, dtype=np.float64)
-    if w.shape != (len(rows),):
+    return mean_curve(saxs_profile(coords, q, aatype, form_factors, max_structures), weights)
+
+
+def mean_curve(rows, weights=None) -> np.ndarray:
+    """``ensemble_saxs`` of the structures' intensities [R, Q] one already has."""
+    w = None if weights is None else np.asarray(weights, dtype=np.float64)
+    if w is not None and w.shape != (len(rows),):
         raise ValueError(f"weights has shape {w.shape} for {len(rows)} structures")
-    return np.average(rows, axis=0, weights=w)
+    return np.average(rows, axis=0, weights=w)   # (None: the plain mean)
 
 
 def hydrodynamic_radius(coords, max_structures=None) -> np.ndarray:
     """Kirkwood's hydrodynamic radius of the CA beads of every structure of ``coords`` [R, L, 3] -> float64 [R] in Angstrom:
     1 / Rh = (1 / L^2) sum_{i != j} 1 / r_ij.  inf for a single bead, 0 where two beads coincide.  No Nygaard or other correction."""
-    inv = _saxs_call(coords, [0.0], None, None, max_structures)[1]
-    with np.errstate(divide="ignore"):
-        return 1.0 / inv
+    return saxs_profile_and_rh(coords, [0.0], None, None, max_structures)[1]
 
 
 def saxs_mae(ca_coords_dict, ref_key="target", q=None, weights=None, **saxs_args):
@@ -755,28 +762,19 @@ def saxs_mae(ca_coords_dict, ref_key="target", q=None, weights=None, **saxs_args
     the reference ensemble's.  ``weights``: per-structure weights by key, as in ``js_pwd``; ``saxs_args``: ``aatype``, ``form_factors``."""
     q = SAXS_Q_GRID if q is None else q
     w = _weights(weights, ca_coords_dict) if weights else {}
-    curve = {k: ensemble_saxs(v, q, w.get(k), **saxs_args) for k, v in ca_coords_dict.items()}
-    out = {k: np.around(float((np.abs(c - curve[ref_key]) / curve[ref_key]).mean()), decimals=4) for k, c in curve.items() if k != ref_key}
-    out[ref_key] = 0.0
-    return out
+    return saxs_mae_of({k: ensemble_saxs(v, q, w.get(k), **saxs_args) for k, v in ca_coords_dict.items()}, ref_key)
 
 
 def mean_rh(ca_coords_dict, weights=None):
     """The (weighted) mean hydrodynamic radius of each ensemble in Angstrom."""
     w = _weights(weights, ca_coords_dict)
-    return {k: np.around(float(np.average(hydrodynamic_radius(v), weights=w[k])), decimals=4) for k, v in ca_coords_dict.items()}
+    return mean_of_values({k: hydrodynamic_radius(v) for k, v in ca_coords_dict.items()}, w)
 
 
 def js_rh(ca_coords_dict, ref_key="target", n_bins=50, weights=None):
-    """Jensen-Shannon distance of the histograms of the structures' hydrodynamic radius, ``n_bins`` bins over the range of the reference
-    ensemble, as ``js_rg`` does it for the radius of gyration."""
+    """``js_of_values`` of the structures' hydrodynamic radius: histograms of ``n_bins`` bins over the range of the reference ensemble, as in ``js_rg``."""
     w = _weights(weights, ca_coords_dict)
-    rh = {k: hydrodynamic_radius(v) for k, v in ca_coords_dict.items()}
-    d_min, d_max = rh[ref_key].min(), rh[ref_key].max()
-    binned = {k: np.histogram(v, bins=n_bins, weights=w[k], range=(d_min, d_max))[0] + PSEUDO_C for k, v in rh.items()}
-    out = {k: np.around(_js(v, binned[ref_key]), decimals=4) for k, v in binned.items() if k != ref_key}
-    out[ref_key] = 0.0
-    return out
+    return js_of_values({k: hydrodynamic_radius(v) for k, v in ca_coords_dict.items()}, ref_key, n_bins, w)
 
 
 def saxs_chi2(intensity, i_exp, sigma, background=False):

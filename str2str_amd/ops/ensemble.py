@@ -102,18 +102,48 @@ def _mobile_target(fn: str, mobile, target, what: str = "mobile", on_device: boo
     return mobile.shape[0], mobile.shape[1]
 
 
+def _integer(fn: str, name: str, v, lo: int = 1, hi: Optional[int] = None) -> int:
+    """The parameter ``name`` of ``fn`` as an int: an integer (not a bool) >= ``lo``, and <= ``hi`` where there is one."""
+    if isinstance(v, bool) or int(v) != v or v < lo or (hi is not None and v > hi):
+        raise HipLibraryError(f"{fn}: {name} must be an integer {f'>= {lo}' if hi is None else f'in {lo} .. {hi}'}, got {v}")
+    return int(v)
+
+
+def _positive(v, message: str) -> float:
+    """``v`` as a float when it is positive and finite; otherwise the error ``message`` with the float in its ``{}``."""
+    v = float(v)
+    if not 0.0 < v < float("inf"):
+        raise HipLibraryError(message.format(v))
+    return v
+
+
+def _structures(fn: str, x, what: str, tail: tuple, max_res: int):
+    """One ensemble ``x`` [R, L, *tail] of ``fn`` (named ``what`` in its messages) of at most ``max_res`` residues, checked but for the
+    device -> (R, L)."""
+    if not isinstance(x, torch.Tensor):
+        raise HipLibraryError(f"{fn}: expected tensors, got {type(x).__name__} for {what}")
+    if x.ndim != 2 + len(tail) or x.shape[2:] != tail or x.shape[0] < 1 or x.shape[1] < 1:
+        raise HipLibraryError(f"{fn}: {what} {tuple(x.shape)}, expected [R, L, {', '.join(map(str, tail))}]")
+    if x.shape[1] > max_res:
+        raise HipLibraryError(f"{fn}: at most {max_res} residues, got {x.shape[1]}")
+    return x.shape[0], x.shape[1]
+
+
+def _ca_ensemble(fn: str, ca, max_res: int):
+    """``ca`` [R, L, 3], the CA coordinates of one ensemble -> (R, L)."""
+    return _structures(fn, ca, "coordinates ca", (3,), max_res)
+
+
+def _launch_structures(fn: str, max_structures, launch_structures: int) -> int:
+    """``max_structures`` (None or an integer >= 1) of ``fn`` -> the structures per launch."""
+    return launch_structures if max_structures is None else min(_integer(fn, "max_structures", max_structures), launch_structures)
+
+
 def _backbone_ensemble(fn: str, atoms, max_res: int, max_structures, launch_structures: int) -> int:
-    """``atoms`` [R, L, 5, 3] of at most ``max_res`` residues and ``max_structures`` (None or an integer >= 1) of ``fn``, checked but for
-    the device -> the structures per launch."""
-    if not isinstance(atoms, torch.Tensor):
-        raise HipLibraryError(f"{fn}: expected a tensor, got {type(atoms).__name__}")
-    if atoms.ndim != 4 or atoms.shape[2:] != (5, 3) or atoms.shape[0] < 1 or atoms.shape[1] < 1:
-        raise HipLibraryError(f"{fn}: atoms {tuple(atoms.shape)}, expected [R, L, 5, 3]")
-    if atoms.shape[1] > max_res:
-        raise HipLibraryError(f"{fn}: at most {max_res} residues, got {atoms.shape[1]}")
-    if max_structures is not None and (isinstance(max_structures, bool) or int(max_structures) != max_structures or max_structures < 1):
-        raise HipLibraryError(f"{fn}: max_structures must be an integer >= 1, got {max_structures}")
-    return launch_structures if max_structures is None else min(int(max_structures), launch_structures)
+    """``atoms`` [R, L, 5, 3] of at most ``max_res`` residues and ``max_structures`` of ``fn``, checked but for the device -> the
+    structures per launch."""
+    _structures(fn, atoms, "atoms", (5, 3), max_res)
+    return _launch_structures(fn, max_structures, launch_structures)
 
 
 def _pair_out(fn: str, out, n_a: int, n_b: int, device) -> torch.Tensor:
@@ -192,10 +222,7 @@ def _tm_d0(d0) -> float:
     """The C ABI's encoding: 0 selects the length formula.  An explicit d0 must be a positive finite number."""
     if d0 is None:
         return 0.0
-    d0 = float(d0)
-    if not 0.0 < d0 < float("inf"):
-        raise HipLibraryError(f"d0: expected a positive finite length in Angstrom (None = the formula of the chain length), got {d0}")
-    return d0
+    return _positive(d0, "d0: expected a positive finite length in Angstrom (None = the formula of the chain length), got {}")
 
 
 def ca_tm_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, d0: Optional[float] = None, max_pairs: Optional[int] = None,
@@ -237,14 +264,11 @@ def lddt_workspace_bytes(n_a: int, n_res: int) -> int:
 
 
 def _lddt_args(what: str, L: int, cutoff, min_seq_sep):
-    cutoff = float(cutoff)
-    if not 0.0 < cutoff < float("inf"):
-        raise HipLibraryError(f"{what}: cutoff must be a positive finite distance in Angstrom, got {cutoff}")
-    if isinstance(min_seq_sep, bool) or int(min_seq_sep) != min_seq_sep or min_seq_sep < 1:
-        raise HipLibraryError(f"{what}: min_seq_sep must be an integer >= 1, got {min_seq_sep}")
+    cutoff = _positive(cutoff, what + ": cutoff must be a positive finite distance in Angstrom, got {}")
+    min_seq_sep = _integer(what, "min_seq_sep", min_seq_sep)
     if L > LDDT_MAX_RES:
         raise HipLibraryError(f"{what}: at most {LDDT_MAX_RES} residues, got {L}")
-    return cutoff, int(min_seq_sep)
+    return cutoff, min_seq_sep
 
 
 def ca_lddt_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, cutoff: float = 15.0, min_seq_sep: int = 1,
@@ -282,22 +306,11 @@ def ca_lddt_per_residue(model: torch.Tensor, target: torch.Tensor, cutoff: float
     return per_res, total
 
 
-def _contact_args(what: str, L: int, min_seq_sep=None, **positive):
-    """The parameters of a contact function ``what`` on chains of ``L`` residues, checked -> the ``positive`` ones as floats, in order,
-    then ``min_seq_sep`` (unless None) as an int."""
-    out = []
-    for name, v in positive.items():
-        v = float(v)
-        if not 0.0 < v < float("inf"):
-            raise HipLibraryError(f"{what}: {name} must be positive and finite, got {v}")
-        out.append(v)
-    if min_seq_sep is not None:
-        if isinstance(min_seq_sep, bool) or int(min_seq_sep) != min_seq_sep or min_seq_sep < 1:
-            raise HipLibraryError(f"{what}: min_seq_sep must be an integer >= 1, got {min_seq_sep}")
-        out.append(int(min_seq_sep))
-    if L > CONTACT_MAX_RES:
-        raise HipLibraryError(f"{what}: at most {CONTACT_MAX_RES} residues, got {L}")
-    return out
+def _contact_args(what: str, min_seq_sep=None, **positive):
+    """The parameters of a contact function ``what``, checked -> the ``positive`` ones as floats, in order, then ``min_seq_sep`` (unless
+    None) as an int."""
+    out = [_positive(v, f"{what}: {name} must be positive and finite, got {{}}") for name, v in positive.items()]
+    return out if min_seq_sep is None else out + [_integer(what, "min_seq_sep", min_seq_sep)]
 
 
 def ca_contact_map(ca: torch.Tensor, cutoff: float = 8.0, min_seq_sep: int = 3, weights: Optional[torch.Tensor] = None):
@@ -306,8 +319,8 @@ def ca_contact_map(ca: torch.Tensor, cutoff: float = 8.0, min_seq_sep: int = 3, 
     contact, symmetric, zero inside the band; weighted [L, L] fp64, or None without ``weights``: the sum of ``weights`` [R] (fp64 device
     tensor) over those structures, in ascending structure order).  The contact probability is ``counts / R`` or ``weighted /
     weights.sum()``.  R is walked in launches of CONTACT_LAUNCH_STRUCTURES; both results are bit for bit the same for any such size."""
-    ca, _, R, L, _ = _ensemble_pair("ca_contact_map", ca, None, on_device=False)
-    cutoff, min_seq_sep = _contact_args("ca_contact_map", L, min_seq_sep, cutoff=cutoff)
+    R, L = _ca_ensemble("ca_contact_map", ca, CONTACT_MAX_RES)
+    cutoff, min_seq_sep = _contact_args("ca_contact_map", min_seq_sep, cutoff=cutoff)
     if weights is not None and (not isinstance(weights, torch.Tensor) or weights.shape != (R,)):
         raise HipLibraryError(f"ca_contact_map: weights {tuple(getattr(weights, 'shape', ()))} for {R} structures")
     _req(ca, name="ca")
@@ -325,8 +338,8 @@ def ca_contact_map(ca: torch.Tensor, cutoff: float = 8.0, min_seq_sep: int = 3, 
 def ca_contact_stats(ca: torch.Tensor, cutoff: float = 8.0, min_seq_sep: int = 3):
     """Per structure of ca [R, L, 3] (fp32 device tensor) -> (n_contacts [R] int32; sep_sum [R] int64: the sum of j - i over its contacts).
     The relative contact order is ``sep_sum / (L * n_contacts)``, 0.0 for a structure without contacts."""
-    ca, _, R, L, _ = _ensemble_pair("ca_contact_stats", ca, None, on_device=False)
-    cutoff, min_seq_sep = _contact_args("ca_contact_stats", L, min_seq_sep, cutoff=cutoff)
+    R, L = _ca_ensemble("ca_contact_stats", ca, CONTACT_MAX_RES)
+    cutoff, min_seq_sep = _contact_args("ca_contact_stats", min_seq_sep, cutoff=cutoff)
     _req(ca, name="ca")
     n_contacts = torch.empty(R, dtype=torch.int32, device=ca.device)
     sep_sum = torch.empty(R, dtype=torch.int64, device=ca.device)
@@ -344,7 +357,9 @@ def ca_native_contacts(native: torch.Tensor, cutoff: float = 8.0, min_seq_sep: i
     if native.ndim != 2 or native.shape[1] != 3 or native.shape[0] < 1:
         raise HipLibraryError(f"ca_native_contacts: native {tuple(native.shape)}, expected [L, 3]")
     L = native.shape[0]
-    cutoff, min_seq_sep = _contact_args("ca_native_contacts", L, min_seq_sep, cutoff=cutoff)
+    cutoff, min_seq_sep = _contact_args("ca_native_contacts", min_seq_sep, cutoff=cutoff)
+    if L > CONTACT_MAX_RES:
+        raise HipLibraryError(f"ca_native_contacts: at most {CONTACT_MAX_RES} residues, got {L}")
     _req(native, name="native")
     slots = max(1, L * (L - 1) // 2)                           # S2S_CONTACT_LIST_SLOTS
     pairs = torch.empty(slots, 2, dtype=torch.int32, device=native.device)
@@ -360,8 +375,8 @@ def ca_native_q(ca: torch.Tensor, pairs: torch.Tensor, d0: torch.Tensor, beta: f
     fp64) of ``ca_native_contacts`` -> (q_soft [R] fp64: the mean of 1 / (1 + exp(beta (d - lam d0))), Best, Hummer and Eaton 2013; q_hard
     [R] fp64: hits / n; hits [R] int32: the entries with d < lam d0).  An empty list gives 1.0.  A structure's values are bit for bit the
     same in any launch."""
-    ca, _, R, L, _ = _ensemble_pair("ca_native_q", ca, None, on_device=False)
-    beta, lam = _contact_args("ca_native_q", L, beta=beta, lam=lam)
+    R, L = _ca_ensemble("ca_native_q", ca, CONTACT_MAX_RES)
+    beta, lam = _contact_args("ca_native_q", beta=beta, lam=lam)
     if not (isinstance(pairs, torch.Tensor) and isinstance(d0, torch.Tensor)) or pairs.ndim != 2 or pairs.shape[1] != 2 or d0.shape != pairs.shape[:1]:
         raise HipLibraryError(f"ca_native_q: pairs {tuple(getattr(pairs, 'shape', ()))} and d0 {tuple(getattr(d0, 'shape', ()))}, expected [n, 2] and [n]")
     n_pairs = pairs.shape[0]
@@ -377,7 +392,7 @@ def ca_native_q(ca: torch.Tensor, pairs: torch.Tensor, d0: torch.Tensor, beta: f
     return q_soft, q_hard, hits
 
 
-def _viol_small(what: str, v, shape, dtype, fn: str = "backbone_violations") -> torch.Tensor:
+def _sequence_input(what: str, v, shape, dtype, fn: str = "backbone_violations") -> torch.Tensor:
     """A per-sequence input of ``fn`` (a few KB; tensor, array or list), checked, as a contiguous tensor of the C ABI's type."""
     t = torch.as_tensor(v)
     if t.shape != shape or t.is_floating_point() or t.is_complex():
@@ -403,9 +418,9 @@ def backbone_violations(atoms: torch.Tensor, atom_exists, aatype, residue_index,
     tolerance_factor, clash_tolerance = float(tolerance_factor), float(clash_tolerance)
     if not (abs(tolerance_factor) < float("inf") and abs(clash_tolerance) < float("inf")):
         raise HipLibraryError(f"backbone_violations: tolerances must be finite, got {tolerance_factor} and {clash_tolerance}")
-    exists = _viol_small("atom_exists", atom_exists, (L, 5), torch.uint8)
-    aatype = _viol_small("aatype", aatype, (L,), torch.int32)
-    residue_index = _viol_small("residue_index", residue_index, (L,), torch.int32)
+    exists = _sequence_input("atom_exists", atom_exists, (L, 5), torch.uint8)
+    aatype = _sequence_input("aatype", aatype, (L,), torch.int32)
+    residue_index = _sequence_input("residue_index", residue_index, (L,), torch.int32)
     _req(atoms, name="atoms")
     dev = atoms.device
     exists, aatype, residue_index = exists.to(dev), aatype.to(dev), residue_index.to(dev)
@@ -431,8 +446,8 @@ def secondary_structure(atoms: torch.Tensor, aatype, residue_index, max_structur
     structure's results are bit for bit the same for any value."""
     rows = _backbone_ensemble("secondary_structure", atoms, SS_MAX_RES, max_structures, SS_MAX_STRUCTURES)
     R, L = atoms.shape[:2]
-    aatype = _viol_small("aatype", aatype, (L,), torch.int32, "secondary_structure")
-    residue_index = _viol_small("residue_index", residue_index, (L,), torch.int32, "secondary_structure")
+    aatype = _sequence_input("aatype", aatype, (L,), torch.int32, "secondary_structure")
+    residue_index = _sequence_input("residue_index", residue_index, (L,), torch.int32, "secondary_structure")
     _req(atoms, name="atoms")
     dev = atoms.device
     aatype, residue_index = aatype.to(dev), residue_index.to(dev)
@@ -450,9 +465,7 @@ def secondary_structure(atoms: torch.Tensor, aatype, residue_index, max_structur
 def sphere_points(n_points: int) -> np.ndarray:
     """The unit sphere of the Shrake-Rupley test: the golden spiral of include/str2str_hip.h -> float64 [n_points, 3].  Built on the host
     in numpy so that the kernel and a numpy statement of the definition read the same bits."""
-    if isinstance(n_points, bool) or int(n_points) != n_points or not 1 <= n_points <= SASA_MAX_POINTS:
-        raise HipLibraryError(f"sphere_points: n_points must be an integer in 1 .. {SASA_MAX_POINTS}, got {n_points}")
-    P = int(n_points)
+    P = _integer("sphere_points", "n_points", n_points, 1, SASA_MAX_POINTS)
     k = np.arange(P, dtype=np.float64)
     y = (k * (2.0 / P) - 1.0) + 1.0 / P
     r = np.sqrt(1.0 - y * y)
@@ -469,7 +482,7 @@ def backbone_sasa(atoms: torch.Tensor, atom_exists, radii, probe: float = 1.4, n
     results are bit for bit the same for any value."""
     rows = _backbone_ensemble("backbone_sasa", atoms, SASA_MAX_RES, max_structures, SASA_MAX_STRUCTURES)
     R, L = atoms.shape[:2]
-    exists = _viol_small("atom_exists", atom_exists, (L, 5), torch.uint8, "backbone_sasa")
+    exists = _sequence_input("atom_exists", atom_exists, (L, 5), torch.uint8, "backbone_sasa")
     radii = torch.as_tensor(radii)
     if radii.shape != (L, 5) or radii.is_complex():
         raise HipLibraryError(f"backbone_sasa: radii: expected numbers of shape {(L, 5)}, got {radii.dtype} {tuple(radii.shape)}")
@@ -514,16 +527,8 @@ def ca_scattering(ca: torch.Tensor, q, types=None, table=None, max_structures: O
     bead, 0 for coincident beads).  No hydration shell, no excluded volume, no built-in form factors, no side chains.  ``max_structures``
     bounds the structures of one launch; a structure's results are bit for bit the same for any value."""
     fn = "ca_scattering"
-    if not isinstance(ca, torch.Tensor):
-        raise HipLibraryError(f"{fn}: expected a tensor, got {type(ca).__name__}")
-    if ca.ndim != 3 or ca.shape[2] != 3 or ca.shape[0] < 1 or ca.shape[1] < 1:
-        raise HipLibraryError(f"{fn}: ca {tuple(ca.shape)}, expected [R, L, 3]")
-    R, L = ca.shape[:2]
-    if L > SAXS_MAX_RES:
-        raise HipLibraryError(f"{fn}: at most {SAXS_MAX_RES} residues, got {L}")
-    if max_structures is not None and (isinstance(max_structures, bool) or int(max_structures) != max_structures or max_structures < 1):
-        raise HipLibraryError(f"{fn}: max_structures must be an integer >= 1, got {max_structures}")
-    rows = SAXS_MAX_STRUCTURES if max_structures is None else min(int(max_structures), SAXS_MAX_STRUCTURES)
+    R, L = _ca_ensemble(fn, ca, SAXS_MAX_RES)
+    rows = _launch_structures(fn, max_structures, SAXS_MAX_STRUCTURES)
     q = _host_array(fn, "q", q, np.float64).astype(np.float64)
     if q.ndim != 1 or not 1 <= q.size <= SAXS_MAX_Q:
         raise HipLibraryError(f"{fn}: q {q.shape}, expected [Q] with 1 <= Q <= {SAXS_MAX_Q}")

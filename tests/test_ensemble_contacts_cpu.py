@@ -12,7 +12,6 @@ import torch
 import contact_cases as cases
 import ref_contacts as ref
 from conftest import ROOT
-from ensemble_cases import load_eval_entry
 
 NAMES = ("s2s_ca_contact_map", "s2s_ca_contact_stats", "s2s_ca_native_contacts", "s2s_ca_native_q")
 
@@ -284,25 +283,3 @@ def test_argument_checks_fire_before_the_device(monkeypatch):
     for call in (lambda: metrics.native_contacts(np.zeros((2, 8, 3))), lambda: metrics.fraction_native_contacts(np.zeros((4, 8, 3)), np.zeros((1, 8, 3)))):
         with pytest.raises(ValueError, match="native"):
             call()
-
-
-# -------------------------------------------------------------------------------------------------------------------------- eval.py
-def test_eval_switch_and_columns():
-    entry = load_eval_entry("s2s_eval_entry_contacts_cpu")
-    assert entry.EXTRA_METRICS == ("val_bb_bond", "val_bb_clash", "viol_per_residue", "div_rmsd", "rmsd_recall", "rmsd_precision", "div_tm",
-                                   "tm_recall", "tm_precision", "div_lddt", "lddt_recall", "lddt_precision")
-    assert entry.CONTACT_COLUMNS == ("q_mean", "q_mean_target", "js_q", "contact_mae", "rco", "rco_target")
-    assert not set(entry.CONTACT_COLUMNS) & (set(entry.EXTRA_METRICS) | set(entry.SS_COLUMNS) | set(entry.CLUSTER_COLUMNS))
-    assert not set(entry.CONTACT_COLUMNS) & set(entry.metric_columns(None))
-    for value, want in ((None, False), (False, False), (True, True), ("true", True), ("false", False), (" True ", True), ("0", False), ("yes", True)):
-        assert entry.contacts_switch(value) is want
-    for bad in ("maybe", 2, 1.0, [True]):
-        with pytest.raises(ValueError, match="contacts"):
-            entry.contacts_switch(bad)
-    with pytest.raises(ValueError, match="contacts"):          # rejected before anything is read or written
-        entry.evaluate_prediction("/nonexistent/pred", "/nonexistent/target", contacts="maybe")
-    with pytest.raises(ValueError, match="secondary_structure"):
-        entry.secondary_structure_switch("maybe")
-    import inspect
-
-    assert inspect.signature(entry.evaluate_prediction).parameters["contacts"].default is None

@@ -14,7 +14,6 @@ import ref_sasa as ref
 import sasa_cases as cases
 import ss_cases
 from conftest import ROOT
-from ensemble_cases import load_eval_entry
 
 ULP = 2.0 ** -52
 MARGIN = 1e-9
@@ -260,24 +259,3 @@ def test_ensemble_metrics_are_the_plain_numpy_tails(monkeypatch):
     by_residue = cases.case("L31_R9_radii_by_residue")
     got = metrics.relative_accessibility(by_residue.atoms[:2], by_residue.aatype, radii=by_residue.radii)
     assert (got == ref.relative(by_residue.atoms[:2], by_residue.exists, by_residue.radii)).all()
-
-
-# ---------------------------------------------------------------------------------------------------------------------- eval.py
-def test_sasa_columns_and_the_switch(monkeypatch):
-    from str2str_amd.utils import config as C
-
-    entry = load_eval_entry("s2s_eval_entry_sasa_cpu")
-    assert entry.SASA_COLUMNS == ("sasa_mean", "sasa_mean_target", "js_sasa", "sasa_mae")
-    assert not set(entry.SASA_COLUMNS) & set(entry.EXTRA_METRICS) and len(entry.EXTRA_METRICS) == 12
-    assert not set(entry.SASA_COLUMNS) & (set(entry.SS_COLUMNS) | set(entry.CONTACT_COLUMNS))
-    monkeypatch.setenv("TEST_DATA", "/nonexistent")
-    compose = lambda *args: C.compose(os.path.join(ROOT, "configs"), "eval.yaml", list(args))   # noqa: E731
-    assert entry.sasa_switch(compose("+sasa=true").get("sasa")) is True
-    assert entry.sasa_switch(compose("+sasa=false").get("sasa")) is False
-    assert compose().get("sasa") is None
-    for value, want in ((None, False), (True, True), (False, False), ("true", True), ("False", False)):
-        assert entry.sasa_switch(value) is want
-    for bad in ("maybe", 2.5, [True]):
-        with pytest.raises(ValueError):
-            entry.sasa_switch(bad)
-    assert inspect.signature(entry.evaluate_prediction).parameters["sasa"].default is None

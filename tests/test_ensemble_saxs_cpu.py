@@ -14,7 +14,6 @@ import torch
 import ref_saxs as ref
 import saxs_cases as cases
 from conftest import ROOT
-from ensemble_cases import load_eval_entry
 
 ULP = 2.0 ** -52
 
@@ -374,30 +373,3 @@ def test_read_saxs_dat(tmp_path):
     empty = tmp_path / "empty.dat"
     empty.write_text("# nothing\n")
     assert [len(a) for a in metrics.read_saxs_dat(str(empty))] == [0, 0, 0]
-
-
-# ---------------------------------------------------------------------------------------------------------------------- eval.py
-def test_saxs_columns_and_the_switch(monkeypatch):
-    from str2str_amd.utils import config as C
-
-    entry = load_eval_entry("s2s_eval_entry_saxs_cpu")
-    assert entry.SAXS_COLUMNS == ("saxs_mae", "rh_mean", "rh_mean_target", "js_rh")
-    others = set(entry.EXTRA_METRICS) | set(entry.SS_COLUMNS) | set(entry.CONTACT_COLUMNS) | set(entry.SASA_COLUMNS) | set(entry.CLUSTER_COLUMNS)
-    assert not (set(entry.SAXS_COLUMNS) | {"saxs_chi2"}) & (others | set(entry.metric_columns(None))) and len(entry.EXTRA_METRICS) == 12
-    monkeypatch.setenv("TEST_DATA", "/nonexistent")
-    compose = lambda *args: C.compose(os.path.join(ROOT, "configs"), "eval.yaml", list(args))   # noqa: E731
-    assert entry.saxs_switch(compose("+saxs=true").get("saxs")) is True
-    assert entry.saxs_switch(compose("+saxs=false").get("saxs")) is False
-    assert compose().get("saxs") is None and compose().get("saxs_data") is None
-    assert compose("+saxs=true", "+saxs_data=/some/dir").get("saxs_data") == "/some/dir"
-    for value, want in ((None, False), (True, True), (False, False), ("true", True), ("False", False)):
-        assert entry.saxs_switch(value) is want
-    for bad in ("maybe", 2.5, [True]):
-        with pytest.raises(ValueError, match="saxs"):
-            entry.saxs_switch(bad)
-    with pytest.raises(ValueError, match="saxs"):               # rejected before anything is read or written
-        entry.evaluate_prediction("/nonexistent/pred", "/nonexistent/target", saxs="maybe")
-    with pytest.raises(ValueError, match="saxs_data"):
-        entry.evaluate_prediction("/nonexistent/pred", "/nonexistent/target", saxs_data="/some/dir")
-    params = inspect.signature(entry.evaluate_prediction).parameters
-    assert params["saxs"].default is None and params["saxs_data"].default is None

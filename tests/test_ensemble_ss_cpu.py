@@ -13,7 +13,6 @@ import torch
 import ref_ss as ref
 import ss_cases as cases
 from conftest import GOLDEN, ROOT, golden, record_margin
-from ensemble_cases import load_eval_entry
 
 ALA = lambda L: (np.zeros(L, dtype=np.int64), np.arange(L))   # noqa: E731
 
@@ -273,25 +272,3 @@ def test_propensity_strings_and_ramachandran_tails():
     counts = np.rint(h - metrics.PSEUDO_C).astype(int)
     # structure 0: (-pi, 0) -> bin (0, 2); (0, pi) -> (2, 0): pi wraps to -pi; (pi, -pi) -> (0, 0); structure 1: three times (0, 0) -> (2, 2)
     assert counts[0, 2] == 1 and counts[2, 0] == 1 and counts[0, 0] == 1 and counts[2, 2] == 3
-
-
-# ---------------------------------------------------------------------------------------------------------------------- eval.py
-def test_ss_columns_and_the_switch(monkeypatch):
-    from str2str_amd.utils import config as C
-
-    entry = load_eval_entry("s2s_eval_entry_ss_cpu")
-    assert entry.SS_COLUMNS == ("ss_helix", "ss_strand", "ss_helix_target", "ss_strand_target", "ss_mae", "js_rama")
-    assert not set(entry.SS_COLUMNS) & set(entry.EXTRA_METRICS) and len(entry.EXTRA_METRICS) == 12 and len(entry.BACKBONE_METRICS) == 3
-    monkeypatch.setenv("TEST_DATA", "/nonexistent")
-    cfg = C.compose(os.path.join(ROOT, "configs"), "eval.yaml", ["+secondary_structure=true"])
-    assert entry.secondary_structure_switch(cfg.get("secondary_structure")) is True
-    assert entry.secondary_structure_switch(C.compose(os.path.join(ROOT, "configs"), "eval.yaml", ["+secondary_structure=false"]).get("secondary_structure")) is False
-    assert C.compose(os.path.join(ROOT, "configs"), "eval.yaml", []).get("secondary_structure") is None
-    for value, want in ((None, False), (True, True), (False, False), ("true", True), ("False", False)):
-        assert entry.secondary_structure_switch(value) is want
-    for bad in ("maybe", 2.5, [True]):
-        with pytest.raises(ValueError):
-            entry.secondary_structure_switch(bad)
-    import inspect
-
-    assert inspect.signature(entry.evaluate_prediction).parameters["secondary_structure"].default is None
