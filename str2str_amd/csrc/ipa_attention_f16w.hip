@@ -12,7 +12,8 @@
 // QK^T accumulator (the query points are pre-scaled by w_h / c1, c1 = sqrt(1/(3C)) the scalar-logit scale), the two squared
 // norms are per-residue fp32 scalars from the point kernel.  (ipa_attention.hip forms explicit differences on the VALU; the
 // expansion costs ~1e-6 absolute in a logit at protein coordinates / 10 -- see DESIGN.md -- and removes 900 VALU
-// instructions per key tile.)
+// instructions per key tile.  The points are taken relative to a per-sample origin, sample_origin() below, so that this holds
+// wherever the chain lies.)
 //   q_xp, k_xp : packed planes [row tile][16 H k-steps][2][64][8] of the q / k projections (s2s_node_linear out_xp)
 //   v_vf       : [row tile][H][8 col tiles][2][2][64][8] A fragments of the v projection (s2s_node_linear_vfrag)
 //   qp_xp, kp_xp [row tile][H][2][2][64][8], vp_vf [row tile][H][2][2][2][64][8], q2 / k2 [row tile][H][32]: the point kernel
@@ -56,6 +57,19 @@ __device__ __forceinline__ void split8(const float* v, f16x8& ph, f16x8& pl) {  
 // residues, head): the 8 + 8 + 12 global-frame points of every residue go through LDS, then 512 (fragment, lane) items are
 // split and stored.  Coordinate k of a point row = 3 p + d (24 of the 32 columns of two k-steps; the rest zero).
 constexpr int PQ = 8, PV = 12;
+
+// The points of a sample are formed relative to an origin of its own: the mean of the translations of its first, middle and last
+// residue (three loads: no reduction over the chain, and the attention kernels below recompute it bit for bit).  The logits see only
+// differences of points, and o_pt is taken back to the local frame with the same origin (the probabilities sum to one), so nothing
+// changes in exact arithmetic -- but q.k + q2 + k2 then cancels at the chain's own extent and not at its distance from the coordinate
+// origin: with uncentred frames 100 A away a logit was off by 1e-4 (tests/test_attention_parity.py, the moved families).
+__device__ __forceinline__ Vec3<float> sample_origin(const float* __restrict__ rig_sample, int n_res) {
+    const float* a = rig_sample + 4;
+    const float* b = rig_sample + (long long)(n_res >> 1) * 7 + 4;
+    const float* c = rig_sample + (long long)(n_res - 1) * 7 + 4;
+    const float third = 1.0f / 3.0f;
+    return Vec3<float>{(a[0] + b[0] + c[0]) * third, (a[1] + b[1] + c[1]) * third, (a[2] + b[2] + c[2]) * third};
+}
 
 __global__ void __launch_bounds__(256) ipa_prep_f16_kernel(const float* __restrict__ rig, const float* __restrict__ qp_lin,
                                                               const float* __restrict__ kvp_lin, const float* __restrict__ head_w,
@@ -106,6 +120,8 @@ __global__ void __launch_bounds__(256) ipa_prep_f16_kernel(const float* __restri
         const long long r = smp * n_res + (pad ? n_res - 1 : n);
         Quat<float> q; Vec3<float> t;
         load7(rig + r * 7, q, t);
+        const Vec3<float> org = sample_origin(rig + smp * n_res * 7, n_res);
+        t.x -= org.x; t.y -= org.y; t.z -= org.z;
         const Mat3<float> R = quat_to_rot<float>(q);
         const int HPq = H * PQ, HPkv = H * (PQ + PV);
         const float* ql = qp_lin + r * 3 * HPq;
@@ -692,7 +708,8 @@ __global__ void __launch_bounds__(256) ipa_attention_f16w_kernel(PlaneArgs a) {
         const int feat = H * (256 + 4 * PV + 32);
         const float* f = a.rigids7 + row_i * 7;
         const float qa = f[0], qb_ = f[1], qc = f[2], qd = f[3];
-        const float tx = f[4], ty = f[5], tz = f[6];
+        const Vec3<float> org = sample_origin(a.rigids7 + (long long)b * N * 7, N);   // the origin the points were formed in
+        const float tx = f[4] - org.x, ty = f[5] - org.y, tz = f[6] - org.z;
         const float r00 = qa * qa + qb_ * qb_ - qc * qc - qd * qd, r01 = 2 * qb_ * qc - 2 * qa * qd, r02 = 2 * qb_ * qd + 2 * qa * qc;
         const float r10 = 2 * qb_ * qc + 2 * qa * qd, r11 = qa * qa - qb_ * qb_ + qc * qc - qd * qd, r12 = 2 * qc * qd - 2 * qa * qb_;
         const float r20 = 2 * qb_ * qd - 2 * qa * qc, r21 = 2 * qc * qd + 2 * qa * qb_, r22 = qa * qa - qb_ * qb_ - qc * qc + qd * qd;
@@ -905,7 +922,8 @@ __global__ void __launch_bounds__(256, 1) ipa_attention_short_kernel(PlaneArgs a
         const int feat = H * (256 + 4 * PV + 32);
         const float* f = a.rigids7 + row_i * 7;
         const float qa = f[0], qb_ = f[1], qc = f[2], qd = f[3];
-        const float tx = f[4], ty = f[5], tz = f[6];
+        const Vec3<float> org = sample_origin(a.rigids7 + (long long)b * N * 7, N);   // the origin the points were formed in
+        const float tx = f[4] - org.x, ty = f[5] - org.y, tz = f[6] - org.z;
         const float r00 = qa * qa + qb_ * qb_ - qc * qc - qd * qd, r01 = 2 * qb_ * qc - 2 * qa * qd, r02 = 2 * qb_ * qd + 2 * qa * qc;
         const float r10 = 2 * qb_ * qc + 2 * qa * qd, r11 = qa * qa - qb_ * qb_ + qc * qc - qd * qd, r12 = 2 * qc * qd - 2 * qa * qb_;
         const float r20 = 2 * qb_ * qd - 2 * qa * qc, r21 = 2 * qc * qd + 2 * qa * qb_, r22 = qa * qa - qb_ * qb_ - qc * qc + qd * qd;

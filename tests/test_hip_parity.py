@@ -390,9 +390,11 @@ def _ipa_case(B, N, seed_off=200):
 
 # Every length runs the default f16 kernel (csrc/ipa_attention_f16w.hip).  32 / 64 = one / two key tiles (the short-stream paths of
 # the two-phase pipeline), 96 = odd tile count (a wave without a tile of its own), 256 / 512 = the BASELINE lengths, (3, 64) =
-# several work items per persistent workgroup chain; 7 / 37 / 40 / 73 / 300 = ragged lengths (operands padded per sample to whole
-# tiles: a single partial tile, a partial second tile, samples whose rows straddle row tiles of the flat [B N] layout, three query
-# blocks + two chunks in s2s_ipa_opair)
+# three samples in one launch of the short kernel (24 (sample, head) pairs: no persistent workgroup sees a second work item here --
+# the largest case, (1, 512), has 32 items on one workgroup per CU; batches with more items than workgroups are
+# tests/test_attention_parity.py::test_ipa_more_items_than_workgroups); 7 / 37 / 40 / 73 / 300 = ragged lengths (operands padded per
+# sample to whole tiles: a single partial tile, a partial second tile, samples whose rows straddle row tiles of the flat [B N]
+# layout, three query blocks + two chunks in s2s_ipa_opair)
 @pytest.mark.parametrize("B,N", [(1, 7), (2, 32), (3, 37), (2, 40), (2, 73), (1, 96), (3, 64), (1, 256), (1, 300), (1, 512)])
 def test_ipa_vs_oracle(net_rough, B, N):
     from oracle import geometry as OG
@@ -979,10 +981,14 @@ def test_range_guard_flags_every_f16_producer():
     assert flags(lambda: emb(**args)) == 0
     emb.edge_embed[0].weight.mul_(1.0e5)                           # first-layer rows (gathered tables) beyond the range
     assert flags(lambda: emb(**args)) & 8
-    r7 = torch.zeros(1, 32, 7, device=DEV); r7[..., 0] = 1; r7[..., 4:] = 4.0e4      # translations of 40 000 (nm / 10): the points overflow
+    # the points are formed relative to an origin of the sample's own (csrc/ipa_attention_f16w.hip, sample_origin): a whole chain at
+    # 40 000 (nm / 10) stays in range, one residue 80 000 away from the rest of its chain does not -- its points overflow
+    r7 = torch.zeros(1, 32, 7, device=DEV); r7[..., 0] = 1; r7[..., 4:] = 4.0e4
     ipa = net.translator.trunk["ipa_0"]
     d = ipa._derived()
     qp = torch.zeros(32, 192, device=DEV); kvp = torch.zeros(32, 480, device=DEV)
+    assert flags(lambda: ops.ipa_prep_points_f16(r7, qp, kvp, d["hw"])) == 0
+    r7[0, 5, 4:] = -4.0e4
     assert flags(lambda: ops.ipa_prep_points_f16(r7, qp, kvp, d["hw"])) == 16
     qkv = torch.randn(64, 960, generator=g).to(DEV)
     for ar in MODES:   # the exact kernel reports what it writes as planes, the f16x3 kernel also the q / k / v it splits
