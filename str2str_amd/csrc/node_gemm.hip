@@ -126,21 +126,29 @@ __device__ __forceinline__ void node_epilogue(f32x16 (&acc)[TG], const GemmArgs&
         }
     }
     if (a.ln_gamma) {  // LayerNorm over the TG*32 columns of the row (half here, half in lane ^ 32)
+        // A plain sum of n values c + O(1) rounds every partial sum at n c 2^-24: for c = 30 (a row with a common offset 30 x its
+        // spread) the mean alone put 5.0e-6 .. 5.4e-6 of the row's scale into the output (tests/test_node_parity.py, offset family).
+        // The variance pass therefore also sums the deviations d = v - m0 from that first mean, which carry the spread only:
+        // mean = m0 + sum(d) / n, and the variance about it is sum(d d) / n - (sum(d) / n)^2 (the correction is ~1e-10 of it: no
+        // cancellation).  One more accumulator in the loop that was there, nothing new live across the epilogue.
         float sum = 0.f;
 #pragma unroll
         for (int t = 0; t < TG; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) sum += acc[t][r];
-        const float mean = xhalf_sum(sum) * (1.0f / (TG * 32));
-        float var = 0.f;
+        const float m0 = xhalf_sum(sum) * (1.0f / (TG * 32));
+        float var = 0.f, dev = 0.f;
 #pragma unroll
         for (int t = 0; t < TG; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float d = acc[t][r] - mean;
+                const float d = acc[t][r] - m0;
+                dev += d;
                 var += d * d;
             }
-        const float rstd = 1.0f / sqrtf(xhalf_sum(var) * (1.0f / (TG * 32)) + a.ln_eps);
+        const float dm = xhalf_sum(dev) * (1.0f / (TG * 32));
+        const float mean = m0 + dm;
+        const float rstd = 1.0f / sqrtf(xhalf_sum(var) * (1.0f / (TG * 32)) - dm * dm + a.ln_eps);
         fetch4(a.ln_gamma + col_base + 4 * h, 0, qb[0]);
         fetch4(a.ln_beta + col_base + 4 * h, 0, qr[0]);
 #pragma unroll
