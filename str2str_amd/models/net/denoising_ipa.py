@@ -22,7 +22,7 @@ from ...arith import default_arith
 from ...common.all_atom import compute_backbone
 from ...common.rigid_utils import Rigid
 from .ipa import TranslationIPA  # noqa: F401  (re-exported like the reference module)
-from .layers import ParamCache
+from .layers import DerivedCache
 
 
 def get_positional_embedding(indices: torch.Tensor, embedding_dim: int, max_len: int = 2056) -> torch.Tensor:
@@ -44,6 +44,8 @@ def get_timestep_embedding(timesteps: torch.Tensor, embedding_dim: int, max_len:
 
 
 class EmbeddingModule(nn.Module):
+    launch_switches = ("arith", "node_arith")   # attributes set below that select launches: part of sampler._graph_key
+
     def __init__(self, init_embed_size: int, node_embed_size: int, edge_embed_size: int, num_bins: int = 22,
                  min_bin: float = 1e-5, max_bin: float = 20.0, self_conditioning: bool = True):
         super().__init__()
@@ -64,15 +66,9 @@ class EmbeddingModule(nn.Module):
         self.time_embed = partial(get_timestep_embedding, embedding_dim=t_embed_size)
         self.position_embed = partial(get_positional_embedding, embedding_dim=pos_embed_size)
         self._dims = (init_embed_size, num_bins, float(min_bin), float(max_bin), edge_embed_size)
-        self._wcache = ParamCache()
-        self._w16cache = ParamCache()
-        self._proj_cache = ParamCache()
+        self._wcache, self._w16cache, self._proj_cache, self._idx_cache, self._fixed_cache = (DerivedCache() for _ in range(5))
         self.arith = default_arith()   # edge embedding kernels: "f16x3" (split-f16 MFMA, default) | "f32" (exact fp32 MFMA), str2str_amd/arith.py
         self.node_arith = default_arith()   # the node MLP (node-stream family: follows the trunk)
-        self._idx_key = None
-        self._idx_val = None
-        self._idx_src = None
-        self.node_embed_act = None  # the last node embedding in the node stream's activation format (read by the trunk)
 
     # ---- derived tensors
     def _weights(self):
@@ -117,15 +113,13 @@ class EmbeddingModule(nn.Module):
         """Per-target constants of the first layers that do not depend on t: (node MLP: fixed-mask column + positional image [B,L,256],
         edge row term [B,L,128], (edge column term in the f16x3 kernel's gather layout [B,32,L,4], the same row-major)).  Cached on
         the mask tensor, the positional image and the weights."""
-        key = (fixed_mask.data_ptr(), tuple(fixed_mask.shape), fixed_mask._version, str(fixed_mask.device), w["wn_f"].data_ptr(), w["wn_f"]._version,
-               node_pos.data_ptr(), node_pos._version)
-        if key != getattr(self, "_fx_key", None) or getattr(self, "_fx_src", None) is not fixed_mask:
+        def build():
             fixed = fixed_mask.to(dev)[..., None].float()
             B, L = fixed.shape[:2]
-            self._fx_val = ((fixed * w["wn_f"] + node_pos).contiguous(), (fixed * w["w_row_f"]).contiguous(),
-                            ((fixed[:, None] * w["w_col_f"].view(1, 32, 1, 4)).expand(B, 32, L, 4).contiguous(), (fixed * w["w_col_f"]).contiguous()))
-            self._fx_key, self._fx_src = key, fixed_mask
-        return self._fx_val
+            return ((fixed * w["wn_f"] + node_pos).contiguous(), (fixed * w["w_row_f"]).contiguous(),
+                    ((fixed[:, None] * w["w_col_f"].view(1, 32, 1, 4)).expand(B, 32, L, 4).contiguous(), (fixed * w["w_col_f"]).contiguous()))
+
+        return self._fixed_cache.get([fixed_mask, w["wn_f"], node_pos], build)
 
     def time_images(self, t_emb: torch.Tensor) -> torch.Tensor:
         """[n, 32] timestep embeddings -> [n, 512] first-layer images + biases [node MLP | edge row | edge column] (one row per
@@ -138,30 +132,34 @@ class EmbeddingModule(nn.Module):
     def _index_tables(self, residue_idx: torch.Tensor, w_rel: torch.Tensor, wn_pos: torch.Tensor):
         """Per-target constants: first-layer image of the node positional features and the relative-position
         table rel_tab[d + off] = W_rel . posemb(d).  Cached on the index tensor (one host sync per target)."""
-        key = (residue_idx.data_ptr(), tuple(residue_idx.shape), residue_idx._version, w_rel.data_ptr(), w_rel._version,
-               wn_pos.data_ptr(), wn_pos._version)
-        # the key is the tensor's identity, so the tensor itself is kept alive with the cached tables: a later target
-        # can then never be allocated at the same (recycled) address and hit tables built for other residue numbering
-        if key != self._idx_key or self._idx_src is not residue_idx:
-            self._idx_src = residue_idx
+        return self._tables(residue_idx, w_rel, wn_pos)[:4]
+
+    def _tables(self, residue_idx, w_rel, wn_pos):
+        """``_index_tables`` + the relative-position table in the f16x3 kernel's column-blocked gather layout."""
+        def build():
             idx_cpu = residue_idx.detach().cpu()
             span = int(idx_cpu.max() - idx_cpu.min())
             d = torch.arange(-span, span + 1)
             dev = w_rel.device
             rel = _table_linear(self.position_embed(d).float().to(dev), w_rel)
             node_pos = _table_linear(self.position_embed(idx_cpu).float().to(dev), wn_pos)  # [B, L, node width]
-            self._idx_val = (rel, span, node_pos, residue_idx.to(dev).contiguous())
-            self._rel_cb = ops.column_blocked(rel)
-            self._idx_key = key
-        return self._idx_val
+            return rel, span, node_pos, residue_idx.to(dev).contiguous(), ops.column_blocked(rel)
 
-    def forward(self, residue_idx, t, fixed_mask, self_conditioning_ca, node_mask: Optional[torch.Tensor] = None,
-                next_proj=None, t_emb: Optional[torch.Tensor] = None, edge_layout: str = "rowmajor", t_img: Optional[torch.Tensor] = None):
-        """-> node_embed [B,N,D_node], edge_embed [B,N,N,D_edge] (reference :107-159; ``edge_layout`` "tiled": as an ``ops.PairTiled``
-        for the trunk's f16x3 pair kernels, arithmetic "f16x3" only).  ``t`` may live on
+        return self._idx_cache.get([residue_idx, w_rel, wn_pos], build)
+
+    def forward(self, *args, **kw):
+        """``embed`` in the reference's shape (:107-159) -> node_embed, edge_embed (, (attn_bias, pair_z) with ``next_proj``)."""
+        node_embed, _, edge_embed, proj = self.embed(*args, **kw)
+        return (node_embed, edge_embed) if proj is None else (node_embed, edge_embed, proj)
+
+    def embed(self, residue_idx, t, fixed_mask, self_conditioning_ca, node_mask: Optional[torch.Tensor] = None,
+              next_proj=None, t_emb: Optional[torch.Tensor] = None, edge_layout: str = "rowmajor", t_img: Optional[torch.Tensor] = None):
+        """-> node_embed [B,N,D_node], the same in the node stream's activation format (what the trunk's first projections and every
+        skip_embed read), edge_embed [B,N,N,D_edge], projections or None (reference :107-159; ``edge_layout`` "tiled": as an
+        ``ops.PairTiled`` for the trunk's f16x3 pair kernels, arithmetic "f16x3" only).  ``t`` may live on
         the host (the sampler knows it there): its embedding is then computed on the host and uploaded.
         ``node_mask`` optionally fuses DenoisingNet's mask multiplies (reference :186-187); ``next_proj`` (packed
-        pair-projection weights of the first IPA block) adds (attn_bias, pair_z) as a third return value."""
+        pair-projection weights of the first IPA block) makes the last value the block's (attn_bias, pair_z)."""
         w = self._weights()
         dev = w["b0"].device
         if dev.type != "cuda":
@@ -169,7 +167,7 @@ class EmbeddingModule(nn.Module):
         if self._dims[4] != 128:
             raise ops.HipLibraryError("edge_embed kernel is built for edge_embed_size=128")
         B, L = residue_idx.shape
-        rel_tab, span, node_pos, idx_dev = self._index_tables(residue_idx, w["w_rel"], w["wn_pos"])
+        rel_tab, span, node_pos, idx_dev, rel_cb = self._tables(residue_idx, w["w_rel"], w["wn_pos"])
         # [B, 32]; evaluated once per DISTINCT t (a sampler chunk shares one t, and the host sin/cos of arguments up to 1e4 rad
         # costs ~40 us per element): same values, row for row
         if t_img is not None:   # the sampler's form: the timestep block's first-layer image of this step, computed with the schedule
@@ -206,8 +204,8 @@ class EmbeddingModule(nn.Module):
         # layers 2, 3 + LayerNorm (+ DenoisingNet's node mask) on the fused node kernels; the packed planes of the result are
         # what the trunk's first projections and every skip_embed read
         nw = w["node_mlp"]
-        node_embed, self.node_embed_act = ops.node_apply_chain(h_act, nw, M, (True, False), ln=(ne[5].weight, ne[5].bias, ne[5].eps),
-                                                               post_mask=None if mask is None else mask.reshape(M), want_xp=True)
+        node_embed, node_act = ops.node_apply_chain(h_act, nw, M, (True, False), ln=(ne[5].weight, ne[5].bias, ne[5].eps),
+                                                          post_mask=None if mask is None else mask.reshape(M), want_xp=True)
         node_embed = node_embed.view(B, L, -1)
         if not single_t:
             node_a = (tl(w["w_row_t"], w["b0"])[:, None, :] + fixed * w["w_row_f"]).expand(B, L, -1).contiguous()
@@ -224,7 +222,7 @@ class EmbeddingModule(nn.Module):
             if next_proj is not None:  # 5-stage stream: W2 | W3 | the first IPA block's projection stage
                 stream = self._proj_cache.get([ws, next_proj["wp_f16x2"]], lambda: torch.cat([ws, next_proj["wp_f16x2"]]))
                 proj = (stream, next_proj["b64"])
-            edge_embed = ops.edge_embed_f16x3(node_a, node_b, self._rel_cb, w["bin_tab_cb"], w["bin_lower"], idx_dev, ca, ws, e2.bias,
+            edge_embed = ops.edge_embed_f16x3(node_a, node_b, rel_cb, w["bin_tab_cb"], w["bin_lower"], idx_dev, ca, ws, e2.bias,
                                               e4.bias, ln.weight, ln.bias, mask, span, ln.eps, proj=proj, column_blocked_tables=True,
                                               out_layout=edge_layout)
         else:
@@ -235,8 +233,8 @@ class EmbeddingModule(nn.Module):
                                         proj=None if next_proj is None else (next_proj["wp"], next_proj["b64"]))
         if next_proj is not None:
             edge_embed, *proj = edge_embed
-            return node_embed, edge_embed, tuple(proj)
-        return node_embed, edge_embed
+            return node_embed, node_act, edge_embed, tuple(proj)
+        return node_embed, node_act, edge_embed, None
 
 
 def _table_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -278,16 +276,15 @@ class DenoisingNet(nn.Module):
         # (producer and consumer both on their f16x3 kernels; the consumer of the embedding's pair tensor is EdgeTransition 0)
         et0 = self.translator.trunk["edge_transition_0"] if "edge_transition_0" in getattr(self.translator, "trunk", {}) else None
         tiled = fuse and getattr(self.embedder, "arith", None) == "f16x3" and getattr(et0, "arith", None) == "f16x3"
-        emb = self.embedder(residue_idx=batch["residue_idx"], t=batch["t"], fixed_mask=fixed_mask,
-                            self_conditioning_ca=batch["sc_ca_t"], node_mask=node_mask, t_emb=batch.get("t_emb"), t_img=batch.get("t_img"),
-                            next_proj=self.translator.trunk["ipa_0"].pair_proj_weights() if fuse else None,
-                            **({"edge_layout": "tiled"} if tiled else {}))
-        node_embed, edge_embed = emb[0], emb[1]
+        node_embed, node_act, edge_embed, first_proj = self.embedder.embed(
+            residue_idx=batch["residue_idx"], t=batch["t"], fixed_mask=fixed_mask, self_conditioning_ca=batch["sc_ca_t"], node_mask=node_mask,
+            t_emb=batch.get("t_emb"), t_img=batch.get("t_img"), next_proj=self.translator.trunk["ipa_0"].pair_proj_weights() if fuse else None,
+            **({"edge_layout": "tiled"} if tiled else {}))
         tb = dict(batch)
         tb["residue_mask"], tb["fixed_mask"] = node_mask, fixed_mask
         tb["rigids_t"] = batch["rigids_t"].to(dev)
-        tb["_node_embed_act"] = getattr(self.embedder, "node_embed_act", None)
-        model_out = self.translator(node_embed, edge_embed, tb, **({"_first_proj": emb[2]} if fuse else {}))
+        tb["_node_embed_act"] = node_act
+        model_out = self.translator(node_embed, edge_embed, tb, **({"_first_proj": first_proj} if fuse else {}))
         if model_out.get("psi_blended") or defer_psi_blend:     # (the torsion head's kernel blends float32 features in its own launch)
             psi_pred = model_out["psi"]
         else:

@@ -26,24 +26,12 @@ import torch.nn.functional as F
 from ... import ops
 from ...arith import default_arith
 from ...common.rigid_utils import Rigid, Rotation
-from .layers import BackboneUpdate, EdgeTransition, Linear, NodeTransition, ParamCache, TorsionAngleHead
-
-
-class _LazyPack(dict):
-    """dict whose named entries are built when first read."""
-
-    def __init__(self, eager: dict, **lazy):
-        super().__init__(eager)
-        self._lazy = lazy
-
-    def __missing__(self, key):
-        if key not in self._lazy:
-            raise KeyError(key)
-        self[key] = self._lazy[key]()
-        return self[key]
+from .layers import BackboneUpdate, DerivedCache, EdgeTransition, Linear, NodeTransition, TorsionAngleHead
 
 
 class InvariantPointAttention(nn.Module):
+    launch_switches = ("arith", "fold")   # attributes set below that select launches: part of sampler._graph_key
+
     def __init__(self, c_s: int, c_z: int, c_hidden: int, no_heads: int, no_qk_points: int, no_v_points: int,
                  inf: float = 1e5, eps: float = 1e-8):
         super().__init__()
@@ -64,8 +52,7 @@ class InvariantPointAttention(nn.Module):
         self.arith = default_arith()   # "f16x3" (s2s_ipa_attention_f16w) | "f32" (s2s_ipa_attention), see str2str_amd/arith.py
         self.fold = os.environ.get("S2S_IPA_FOLD", "1") != "0"   # f16 path: K = V = s, W_k / W_v folded into q' and linear_out (_folded_packs)
         self._last_folded = False
-        self._cache = ParamCache()
-        self._packs = ParamCache()
+        self._cache, self._packs = DerivedCache(), DerivedCache()
 
     def _derived(self):
         def build():
@@ -78,8 +65,8 @@ class InvariantPointAttention(nn.Module):
             wcat64[: wcat.shape[0]] = wcat
             # "wp_f16x2" (the projection as one f16x3 weight stage) is packed on first use: the packing refuses weights beyond f16's
             # range (ops.WeightRangeError), and the exact kernels -- the fallback for exactly that case -- must not trip over it
-            return _LazyPack({"wp": ops.pack_weight(wcat), "b64": b64.contiguous(), "hw": hw.contiguous()},
-                             wp_f16x2=lambda: ops.pack_f16x2_layer(wcat64, "chain").reshape(-1).view(torch.int16).contiguous())
+            return ops.LazyDict({"wp": ops.pack_weight(wcat), "b64": b64.contiguous(), "hw": hw.contiguous()},
+                                wp_f16x2=lambda d: ops.pack_f16x2_layer(wcat64, "chain").reshape(-1).view(torch.int16).contiguous())
 
         return self._cache.get([self.linear_b.weight, self.linear_b.bias, self.down_z.weight, self.down_z.bias,
                                 self.head_weights], build)
@@ -243,6 +230,8 @@ class InvariantPointAttention(nn.Module):
 
 
 class TranslationIPA(nn.Module):
+    launch_switches = ("exact_padding", "fuse_pair_projection", "arith")   # attributes set below that select launches: sampler._graph_key
+
     def __init__(self, c_s: int, c_z: int, coordinate_scaling: float, no_ipa_blocks: int, skip_embed_size: int,
                  transformer_num_heads: int = 4, transformer_num_layers: int = 2, c_hidden: int = 256, no_heads: int = 8,
                  no_qk_points: int = 8, no_v_points: int = 12, dropout: float = 0.0):
@@ -269,7 +258,7 @@ class TranslationIPA(nn.Module):
                 self.trunk[f"edge_transition_{b}"] = EdgeTransition(node_embed_size=c_s, edge_embed_in=c_z,
                                                                     edge_embed_out=c_z)
         self.torsion_pred = TorsionAngleHead(c_s, 1)
-        self._wcache = ParamCache()
+        self._wcache, self._mask_cache = DerivedCache(), DerivedCache()
         # Padding semantics of the encoder layers.  False = the reference's: the FLOAT key-padding mask (1 - node_mask) is ADDED to
         # the logits, as PyTorch does for float masks -- a no-op for the all-ones masks of every reference
         # run.  True (set by the mixed-length sampler) removes padded keys (-inf), which is what a padded batch needs to
@@ -304,9 +293,7 @@ class TranslationIPA(nn.Module):
     def _mask_terms(self, residue_mask: torch.Tensor, fixed_mask: torch.Tensor):
         """(node mask, diffuse mask = (1 - fixed) * node mask, the encoder layers' key bias, fixed mask flat), all float32: constants of a
         chunk, cached on the two mask tensors (five tiny launches per evaluation otherwise)."""
-        key = (residue_mask.data_ptr(), residue_mask._version, tuple(residue_mask.shape), residue_mask.dtype, fixed_mask.data_ptr(),
-               fixed_mask._version, fixed_mask.dtype, bool(self.exact_padding))
-        if key != getattr(self, "_mk_key", None) or self._mk_src[0] is not residue_mask or self._mk_src[1] is not fixed_mask:
+        def build():
             node_mask = residue_mask.type(torch.float).contiguous()
             fixed = fixed_mask.type(torch.float).contiguous()
             diffuse_mask = ((1 - fixed) * node_mask).contiguous()
@@ -314,9 +301,9 @@ class TranslationIPA(nn.Module):
             # float key-padding mask of the encoder layers: ADDED to the logits (PyTorch semantics, a no-op for all-ones masks);
             # exact-padding mode removes padded keys instead
             key_bias = (torch.where(pad > 0, float("-inf"), 0.0) if self.exact_padding else pad).float().contiguous()
-            self._mk_val = (node_mask, diffuse_mask, key_bias, fixed.reshape(-1))
-            self._mk_key, self._mk_src = key, (residue_mask, fixed_mask)
-        return self._mk_val
+            return node_mask, diffuse_mask, key_bias, fixed.reshape(-1)
+
+        return self._mask_cache.get([residue_mask, fixed_mask], build, bool(self.exact_padding))
 
     def forward(self, node_embed: torch.Tensor, edge_embed: torch.Tensor, batch: dict, _first_proj=None) -> dict:
         """reference :331-387.  Frames travel as one [B,N,7] tensor between the fused kernels; node activations as packed f16

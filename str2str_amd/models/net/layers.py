@@ -11,6 +11,7 @@ reference's module API (torch ops), kept for callers outside the sampler.
 from __future__ import annotations
 
 import math
+import operator
 import os
 from typing import Optional
 
@@ -31,9 +32,34 @@ def _trunc_normal_(w: torch.Tensor, scale: float):
         nn.init.trunc_normal_(w, mean=0.0, std=std, a=-2.0 * std, b=2.0 * std)
 
 
+class DerivedCache:
+    """One slot for device tensors derived from other tensors (packed / concatenated weights, per-target tables, mask terms): the
+    only way module state may hold a derived device tensor, because ``sampler._graph_read_tensors`` pins exactly what these hold.
+    The key is every source's (data_ptr, _version, shape, dtype, device) plus ``extra`` hashable scalars, and a hit also needs the
+    very same source objects -- the slot keeps them alive, so a recycled address can never hit; load_state_dict / .to() / an
+    in-place write invalidate it."""
+
+    def __init__(self):
+        self._key = self._val = None
+        self._src = ()
+
+    def get(self, sources, build, *extra):
+        key = (tuple([(p.data_ptr(), p._version, p.shape, p.dtype, p.device) for p in sources]), extra)
+        if key != self._key or any(map(operator.is_not, self._src, sources)):
+            with torch.no_grad():
+                self._val = build()
+            self._key, self._src = key, tuple(sources)
+        return self._val
+
+    def held(self):
+        """(value, sources): everything the slot keeps alive (a captured HIP graph pins it beyond the next rebuild)."""
+        return self._val, self._src
+
+
 class Linear(nn.Linear):
     def __init__(self, in_dim: int, out_dim: int, bias: bool = True, init: str = "default", init_fn=None):
         super().__init__(in_dim, out_dim, bias=bias)
+        self._pack = DerivedCache()
         with torch.no_grad():
             if bias:
                 self.bias.fill_(0)
@@ -63,36 +89,13 @@ class Linear(nn.Linear):
         if not x.is_cuda:
             raise ops.HipLibraryError("Linear.forward runs on the HIP device only (the package has no CPU / BLAS matrix path; "
                                       "CPU restatements live under oracle/ for the tests)")
-        if not hasattr(self, "_pack"):
-            self._pack = ParamCache()
-        bias = self.bias if self.bias is not None else torch.zeros(self.out_features, device=x.device)
-        layer = self._pack.get([self.weight, bias], lambda: ops.pack_node_layer(self.weight, bias))
+        srcs = [self.weight] if self.bias is None else [self.weight, self.bias]
+        layer = self._pack.get(srcs, lambda: ops.pack_node_layer(self.weight, self.bias))
         if self.in_features % 32:
             raise ops.HipLibraryError(f"Linear.forward: the node kernel wants in_features in multiples of 32 (got {self.in_features})")
         lead, M = x.shape[:-1], x.numel() // x.shape[-1]
         y, _ = ops.node_apply(ops.to_act(x.reshape(M, x.shape[-1]).float().contiguous(), default_arith()), layer, M)
         return y[:, : self.out_features].reshape(*lead, self.out_features)
-
-
-class ParamCache:
-    """Derived device tensors (packed / concatenated weights) keyed on the source parameters'
-    storage and version counters, so load_state_dict / .to() invalidate them."""
-
-    def __init__(self):
-        self._key = None
-        self._val = None
-
-    def get(self, params, build):
-        key = tuple((p.data_ptr(), p._version, p.device) for p in params)
-        if key != self._key:
-            with torch.no_grad():
-                self._val = build()
-            self._key = key
-        return self._val
-
-    def pinned(self):
-        """The cached value (a captured HIP graph keeps it alive beyond the next rebuild; sampler._GraphedNet)."""
-        return self._val
 
 
 class NodeTransition(nn.Module):
@@ -112,6 +115,8 @@ class NodeTransition(nn.Module):
 
 
 class EdgeTransition(nn.Module):
+    launch_switches = ("arith", "prescale_exp")   # attributes set below that select launches: part of sampler._graph_key
+
     def __init__(self, node_embed_size: int, edge_embed_in: int, edge_embed_out: int, num_layers: int = 2,
                  node_dilation: int = 2):
         super().__init__()
@@ -125,10 +130,7 @@ class EdgeTransition(nn.Module):
         self.final_layer = Linear(hidden, edge_embed_out, init="final")
         self.layer_norm = nn.LayerNorm(edge_embed_out)
         self._shape = (edge_embed_in, bias_embed_size, hidden, edge_embed_out, num_layers)
-        self._cache = ParamCache()
-        self._cache32 = ParamCache()
-        self._proj_cache = ParamCache()   # (a captured HIP graph keeps pointing at its stream: sampler._GraphedNet pins it)
-        self._node_cache = ParamCache()
+        self._cache, self._cache32, self._proj_cache, self._node_cache, self._c32 = (DerivedCache() for _ in range(5))
         self.arith = default_arith()      # "f16x3" (csrc/pair_mlp_f16.hip) | "f32" (csrc/pair_mlp.hip): see str2str_amd/arith.py
         self.prescale_exp = 0             # f16x3: block exponent of the hidden activations (planes hold 2^-e x the value; the sampler raises
         #                                   it when the range guard reports activations of 2^15 and beyond: sampler.denoise_loop)
@@ -178,12 +180,11 @@ class EdgeTransition(nn.Module):
 
         return self._node_cache.get([w1.weight, w1.bias, ie.weight, ie.bias, wf.weight, wf.bias], build)
 
-    @staticmethod
-    def ab16_specs(nl: dict, from_s: bool, n_rows: int, device):
+    def ab16_specs(self, nl: dict, from_s: bool, n_rows: int, device):
         """node_ab in the f16x3 pair kernel's form [A_i + b1 | 32 B_j | 32 G_j] as two layers into one buffer -> (buffer [M, 896], specs
         for ``ops.node_apply_multi`` / ``ops.node_apply``)."""
         ab = torch.empty(n_rows, 896, device=device, dtype=torch.float32)
-        c32 = ops.const_rows(n_rows, 32.0, device)
+        c32 = self._c32.get([], lambda: torch.full((n_rows,), 32.0, device=device, dtype=torch.float32), int(n_rows), str(device))
         ka, kb = ("ab_sA", "ab_sB") if from_s else ("abA", "abB")
         return ab, [(nl[ka], dict(out_f32=ab, out_col0=0)), (nl[kb], dict(out_f32=ab, out_col0=384, pre_scale=c32))]
 

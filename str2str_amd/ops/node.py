@@ -5,7 +5,7 @@ from typing import Optional
 import torch
 
 from .binding import HipLibraryError, _check, _int_arg, _p, _req, _req_all, _req_opt, _stream, _timed, load_library
-from .packing import pack_node_weight, vf_alloc, xp_alloc
+from .packing import vf_alloc, xp_alloc
 from .range_guard import range_flag
 
 SMALL_ROWS = 8192        # at or below: a long contraction with a row-normalising epilogue runs as narrow GEMM + LayerNorm (node_apply)
@@ -13,7 +13,6 @@ NARROW_MAX_WORK = 24 << 20   # rows x output columns up to which the narrow colu
 #   (tools/node_gemm_bench.py --tg 2 against the default, profiles/r04_node_gemm_small_m.txt: 2048 columns win up to ~10 k rows and
 #    lose from ~24 k, 512 .. 960 columns still win at 24 k rows)
 CHAIN_WIDTHS = (256, 320)    # output widths s2s_node_chain is instantiated for
-_CONST_ROWS = {}             # cache of ``const_rows`` (mutated in place, never rebound)
 
 
 def _ln_args(ln, name=None):
@@ -161,8 +160,6 @@ def node_apply(x, layer: dict, n_rows: int, *, out_f32=None, out_col0: int = 0, 
         # a long contraction on few rows whose epilogue normalises over the row (linear_out, K = 2688): one column block per row tile
         # is K / 16 serial k-steps of 24 MFMAs on 1 / 6 of the chip; GEMM in narrow blocks + the LayerNorm on its own is the same
         # arithmetic (s2s_row_layernorm) in a third of the time
-        if "w_n" not in layer:
-            layer["w_n"] = pack_node_weight(layer._w.float(), 2)
         pre = torch.empty(n_rows, layer["n"], device=x.device, dtype=torch.float32)
         T.node_linear(x, layer["w_n"], layer["b"], n_rows, layer["k"], layer["n"], 2, *flat[:4], None, None, 0.0, None, pre)
         return T.row_layernorm(pre, n_rows, layer["n"], g, b, eps, flat[7], *outs)
@@ -331,22 +328,6 @@ def node_apply_chain(x, layers, n_rows: int, relu, **kw):
                                             kw.get("out_f32"), kw.get("out_col0", 0), kw.get("want_f32", True), kw.get("out_xp"),
                                             _int_arg(kw.get("out_xp_k")), kw.get("out_xp_k0", 0), kw.get("want_xp", False), k0, first_res,
                                             first_out, *_ln_args(first_ln))
-
-
-def const_rows(n_rows: int, value: float, device) -> torch.Tensor:
-    """A cached [n_rows] float32 device tensor of ``value`` (a constant ``pre_scale`` of a node layer)."""
-    key = (int(n_rows), float(value), str(device))
-    t = _CONST_ROWS.get(key)
-    if t is None:
-        if len(_CONST_ROWS) > 64:
-            _CONST_ROWS.clear()
-        t = _CONST_ROWS[key] = torch.full((n_rows,), float(value), device=device, dtype=torch.float32)
-    return t
-
-
-def const_rows_cached() -> list:
-    """The tensors ``const_rows`` holds now (the sampler pins them for graph capture: the bounded cache may drop them later)."""
-    return list(_CONST_ROWS.values())
 
 
 def node_apply_multi(x, specs, n_rows: int):

@@ -197,25 +197,28 @@ def pack_node_layer(w: torch.Tensor, bias, whole_row: bool = False) -> dict:
     # block wins (every weight stage serves more MFMAs).  A layer that needs the whole row in one block (LayerNorm) has no choice.
     t = n_pad // 32
     tg_s = tg if whole_row else (2 if t % 2 == 0 else tg)
-    return _NodeLayer({"b": b.contiguous(), "n": n_pad, "k": k, "tg": tg, "tg_s": tg_s}, w.detach())
+    w = w.detach()
+
+    def blocks(d, tiles):   # the f16 fragments in column blocks of ``tiles`` tiles (the default grouping's blob is shared)
+        return d["w"] if tiles == tg else pack_node_weight(w.float(), tiles)
+
+    # "w_row": one column block = the whole row (s2s_node_chain); "w_n": narrow blocks of two tiles (node_apply's GEMM + LayerNorm form)
+    return LazyDict({"b": b.contiguous(), "n": n_pad, "k": k, "tg": tg, "tg_s": tg_s}, w=lambda d: pack_node_weight(w.float(), tg),
+                    w_s=lambda d: blocks(d, tg_s), w_row=lambda d: blocks(d, t), w_n=lambda d: blocks(d, 2),
+                    w32=lambda d: pack_node_weight_f32(w.float(), tg))
 
 
-class _NodeLayer(dict):
-    def __init__(self, d, w):
-        super().__init__(d)
-        self._w = w
+class LazyDict(dict):
+    """dict whose named entries are built when first read (``lazy``: key -> builder, called with the dict)."""
+
+    def __init__(self, eager: dict, **lazy):
+        super().__init__(eager)
+        self._lazy = lazy
 
     def __missing__(self, key):
-        if key == "w":
-            self[key] = pack_node_weight(self._w.float(), self["tg"])
-        elif key == "w_s":
-            self[key] = self["w"] if self["tg_s"] == self["tg"] else pack_node_weight(self._w.float(), self["tg_s"])
-        elif key == "w_row":   # one column block = the whole row (s2s_node_chain)
-            self[key] = self["w"] if self["tg"] == self["n"] // 32 else pack_node_weight(self._w.float(), self["n"] // 32)
-        elif key == "w32":
-            self[key] = pack_node_weight_f32(self._w.float(), self["tg"])
-        else:
+        if key not in self._lazy:
             raise KeyError(key)
+        self[key] = self._lazy[key](self)
         return self[key]
 
 

@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .arith import FAMILIES, family_slots, net_arith, use_arith
+from .arith import FAMILIES, net_arith, use_arith
 from .common.all_atom import compute_backbone
 from .common.rigid_utils import Rigid
 
@@ -71,9 +71,8 @@ class _GraphedNet:
             self.out = _net_eval(net, self.feats, True)
         # The captured kernels hold raw pointers to every tensor the evaluation read.  Those allocated INSIDE the capture live in the
         # graph's private pool; the ones built by the warm-up outside it must be kept alive by THIS object, because their only other
-        # owner is a single-slot cache that the next evaluation of another shape overwrites: the embedder's per-target tables
-        # (relative-position table, its column-blocked copy, positional node image, device residue indices) and the packed /
-        # derived weights of the modules' parameter caches.
+        # owner is a single-slot cache (layers.DerivedCache) that the next evaluation of another shape or target overwrites:
+        # per-target tables, mask terms, constant rows, packed / derived weights.
         self._pinned = _graph_read_tensors(net)
 
     def __call__(self, feats):
@@ -84,8 +83,9 @@ class _GraphedNet:
 
 
 def _graph_read_tensors(net):
-    """Every tensor held by a replaceable cache slot of the network's modules (index tables of the embedder, ParamCache entries)."""
-    from .models.net.layers import ParamCache
+    """Every tensor (values and their sources) held by the ``DerivedCache`` slots of the network's modules -- by construction all the
+    derived device tensors that module state holds."""
+    from .models.net.layers import DerivedCache
 
     def tensors(x, out):
         if torch.is_tensor(x):
@@ -100,13 +100,9 @@ def _graph_read_tensors(net):
 
     keep = []
     for m in net.modules():
-        for name in ("_idx_val", "_rel_cb", "_idx_src", "_fx_val", "_fx_src", "_mk_val", "_mk_src", "node_embed_act"):
-            if hasattr(m, name):
-                tensors(getattr(m, name), keep)
         for v in vars(m).values():
-            if isinstance(v, ParamCache):
-                tensors(v.pinned(), keep)
-    keep += ops.const_rows_cached()   # constant pre-scale rows of the node layers (a bounded cache that may drop them later)
+            if isinstance(v, DerivedCache):
+                tensors(v.held(), keep)
     return keep
 
 
@@ -130,13 +126,10 @@ def _graph_key(net, feats, b, N):
         if k in ("rigids_t", "sc_ca_t", "t_img", "t") or not torch.is_tensor(v):
             continue  # per-step inputs are copied into the static buffers at every replay
         h.update(k.encode()); h.update(str(tuple(v.shape)).encode()); h.update(v.detach().cpu().numpy().tobytes())
-    tr = getattr(net, "translator", None)
-    # which kernels were captured: the arithmetic / kernel selectors of the modules
-    modes = tuple(str(getattr(m, a)) for m, a in family_slots(net))   # per switch, in module order: a mixed network has many forms
-    modes += tuple(int(m.prescale_exp) for m in net.modules() if hasattr(m, "prescale_exp"))   # block exponents are launch arguments
-    modes += tuple(bool(m.fold) for m in net.modules() if hasattr(m, "fold"))                 # folded / per-head attention operands (A/B switch)
-    return (id(net), sum(p._version for p in net.parameters()), b, N, bool(getattr(tr, "exact_padding", False)),
-            bool(getattr(tr, "fuse_pair_projection", False)), modes, h.hexdigest())
+    # which kernels were captured: every switch the module classes declare (``launch_switches``: arithmetic, block exponents, folded
+    # attention operands, padding semantics, ...), per module in module order -- a mixed network has many forms
+    modes = tuple((type(m).__name__, a, getattr(m, a)) for m in net.modules() for a in getattr(type(m), "launch_switches", ()))
+    return (id(net), sum(p._version for p in net.parameters()), b, N, modes, h.hexdigest())
 
 
 def _maybe_graph(net, feats, b, N, trace, n_steps):

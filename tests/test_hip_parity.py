@@ -1244,6 +1244,70 @@ def test_hip_graph_cache_survives_other_shapes(net_smooth, diffuser, monkeypatch
     assert len(sampler._GRAPH_CACHE) == 2
     assert torch.equal(a1, eager_a) and torch.equal(b1, eager_b) and torch.equal(a2, eager_a)
 
+
+def test_graph_pins_every_derived_tensor_of_the_modules(net_smooth, diffuser, monkeypatch):
+    """After a real (eager) evaluation, every tensor that module state holds -- reachable from any module's ``vars()`` through dicts, lists
+    and tuples -- and that is no parameter or buffer is one ``sampler._graph_read_tensors`` pins, by identity: module state keeps derived
+    device tensors in ``layers.DerivedCache`` slots only.  A bare cached attribute (which a captured graph would read after the next
+    evaluation freed it) fails here."""
+    from str2str_amd import sampler
+    from str2str_amd.common.rigid_utils import Rigid
+    from str2str_amd.synth import synth_chain
+
+    def tensors(x, out):
+        if torch.is_tensor(x):
+            out.append(x)
+        elif isinstance(x, (dict, list, tuple)):
+            for v in (x.values() if isinstance(x, dict) else x):
+                tensors(v, out)
+        return out
+
+    N, B = 12, 2
+    feats = synth_chain(N)
+    rig0 = Rigid.from_tensor_4x4(feats["rigidgroups_gt_frames"][..., 0, :, :].repeat(B, 1, 1, 1))
+    monkeypatch.setenv("S2S_HIP_GRAPH", "0")
+    torch.manual_seed(3)
+    assert torch.isfinite(sampler.forward_backward(net_smooth, diffuser, feats, rig0, 1.0, num_timesteps=2, device=DEV)).all()
+    own = {id(t) for t in list(net_smooth.parameters()) + list(net_smooth.buffers())}
+    pinned = {id(t) for t in sampler._graph_read_tensors(net_smooth)}
+    assert len(pinned) > 100
+    loose = [(type(m).__name__, name, tuple(t.shape)) for m in net_smooth.modules() for name, v in vars(m).items()
+             for t in tensors(v, []) if id(t) not in own and id(t) not in pinned]
+    assert not loose, loose
+
+
+def test_hip_graph_key_separates_a_launch_switch(net_smooth, diffuser, monkeypatch):
+    """A switch that selects kernels (``fold`` of the IPA blocks, declared in ``launch_switches``) is part of the graph key: flipping it
+    captures a second graph instead of replaying the first, and each replay is its own eager run bit for bit."""
+    from str2str_amd import sampler
+    from str2str_amd.common.rigid_utils import Rigid
+    from str2str_amd.synth import synth_chain
+
+    N, B = 20, 3
+    feats = synth_chain(N)
+    rig0 = Rigid.from_tensor_4x4(feats["rigidgroups_gt_frames"][..., 0, :, :].repeat(B, 1, 1, 1))
+    ipas = [m for m in net_smooth.modules() if type(m).__name__ == "InvariantPointAttention"]
+    keep = [m.fold for m in ipas]
+
+    def run(mode, fold):
+        monkeypatch.setenv("S2S_HIP_GRAPH", mode)
+        for m, k in zip(ipas, keep):
+            m.fold = k if fold else False
+        torch.manual_seed(7)
+        return sampler.forward_backward(net_smooth, diffuser, feats, rig0, 1.0, num_timesteps=5, device=DEV).clone()
+
+    assert len(ipas) == 4 and all(keep)
+    sampler._GRAPH_CACHE.clear()
+    try:
+        graph_default = run("1", True)
+        graph_unfolded = run("1", False)
+        assert len(sampler._GRAPH_CACHE) == 2
+        eager_unfolded, eager_default = run("0", False), run("0", True)
+    finally:
+        for m, k in zip(ipas, keep):
+            m.fold = k
+    assert torch.isfinite(graph_default).all() and torch.equal(graph_unfolded, eager_unfolded) and torch.equal(graph_default, eager_default)
+
 def test_cfg4_shape_n512_arithmetics_agree_and_shard(net_smooth, diffuser):
     """BASELINE configs[3] shape (N = 512), properties that need no reference (the reference-generated N = 512 evaluation and
     trajectory are in test_denoising_net_golden / test_free_running_trajectory_rmsd[n512_s10]): the default f16x3 arithmetic and

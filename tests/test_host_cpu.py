@@ -583,3 +583,114 @@ def test_bench_dump_outputs_writes_float32_within_the_cap(tmp_path, monkeypatch)
     assert np.array_equal(sample, x.numpy().reshape(-1, 5, 3)[rows.astype(np.int64)])
     for f in files:
         assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
+def _tensors_in(x, out=None):
+    """Every tensor reachable from ``x`` through dicts, lists and tuples."""
+    out = [] if out is None else out
+    if torch.is_tensor(x):
+        out.append(x)
+    elif isinstance(x, dict):
+        for v in x.values():
+            _tensors_in(v, out)
+    elif isinstance(x, (list, tuple)):
+        for v in x:
+            _tensors_in(v, out)
+    return out
+
+
+@pytest.fixture(scope="module")
+def cpu_net():
+    from str2str_amd.factory import build_net
+
+    return build_net()
+
+
+def test_derived_cache_semantics():
+    """layers.DerivedCache: one slot keyed on every source's (data_ptr, _version, shape, dtype, device) and the extra scalars; a hit
+    also needs the very same source objects; what it reports as held is the value and the sources themselves."""
+    from str2str_amd.models.net.layers import DerivedCache
+
+    cache, builds = DerivedCache(), []
+
+    def get(srcs, *extra):
+        def build():
+            builds.append(extra)
+            return {"twice": srcs[0] * 2, "more": [srcs[0] + 1, (srcs[0].float(),)]}
+        return cache.get(srcs, build, *extra)
+
+    x = torch.arange(6.0)
+    first = get([x])
+    assert get([x]) is first and len(builds) == 1                       # same sources: same object, one build
+    x.add_(1)
+    assert get([x]) is not first and len(builds) == 2                   # an in-place write to a source
+    assert get([x]) is get([x]) and len(builds) == 2
+    y = x.clone()
+    assert torch.equal(x, y) and get([y]) is get([y]) and len(builds) == 3    # another tensor object with equal contents
+    v2, v3 = x[:2], x[:3]
+    assert v2.data_ptr() == v3.data_ptr() and v2._version == v3._version
+    get([v2]); get([v3])
+    assert len(builds) == 5                                             # a view of the same storage with another shape
+    p = torch.zeros(4)
+    get([p]); get([p])
+    assert len(builds) == 6
+    p.data = p.data[:3]                                                 # the SAME object: another shape at the same address
+    get([p]); get([p])
+    assert len(builds) == 7
+    p.data = p.data.double()                                            # ... and another dtype (what module.double() does)
+    held_before = get([p])
+    assert len(builds) == 8 and held_before["twice"].dtype == torch.float64
+    assert get([p], 1) is not held_before and get([p], 1) is get([p], 1) and len(builds) == 9      # an ``extra`` change
+    get([p], 2); get([p], 2, "cpu"); get([p], 2, "cpu")
+    assert len(builds) == 11
+    q = torch.ones(3)
+    val = get([p, q], 2)
+    held = {id(t) for t in _tensors_in(cache.held())}
+    assert {id(t) for t in _tensors_in(val)} | {id(p), id(q)} <= held and len(_tensors_in(val)) == 3
+
+
+def test_every_derived_tensor_is_pinned_by_construction(cpu_net):
+    """Whatever the model's builders of derived tensors return lives in a DerivedCache, so ``sampler._graph_read_tensors`` -- which
+    knows no attribute name -- holds every tensor of it by identity (2 x 12 masks; the pure-torch builders run on the CPU)."""
+    from str2str_amd import sampler
+
+    B, N = 2, 12
+    emb, tr = cpu_net.embedder, cpu_net.translator
+    residue_mask, fixed_mask = torch.ones(B, N), torch.zeros(B, N)
+    built = [getattr(m, name)() for m in cpu_net.modules() for name in ("_derived", "node_packs", "node_layers", "_packed")
+             if hasattr(m, name)]
+    w = emb._weights()
+    built += [tr._node_weights(), tr._mask_terms(residue_mask, fixed_mask), w,
+              emb._fixed_terms(fixed_mask, w, torch.device("cpu"), torch.randn(B, N, 256))]
+    assert len(built) == 4 * 2 + 3 * 2 + 4        # 4 IPA blocks x (_derived, node_packs), 3 EdgeTransitions x (node_layers, _packed)
+    pinned = {id(t) for t in sampler._graph_read_tensors(cpu_net)}
+    tensors = _tensors_in(built)
+    assert len(tensors) > 100 and all(id(t) in pinned for t in tensors)
+    assert {id(residue_mask), id(fixed_mask)} <= pinned            # the sources too
+
+
+def test_graph_key_covers_every_declared_launch_switch(cpu_net):
+    """``launch_switches`` of the module classes: exactly the six switches that select launches, each present on the modules that declare
+    it, and flipping any of them on one module changes the key under which a captured evaluation is replayed."""
+    from str2str_amd import sampler
+    from str2str_amd.synth import synth_chain
+
+    feats = synth_chain(12)
+    first = {}
+    for m in cpu_net.modules():
+        for a in getattr(type(m), "launch_switches", ()):
+            assert hasattr(m, a), (type(m).__name__, a)
+            first.setdefault((type(m).__name__, a), m)
+    assert {a for _, a in first} == {"arith", "node_arith", "prescale_exp", "fold", "exact_padding", "fuse_pair_projection"}
+    assert {c for c, _ in first} == {"EmbeddingModule", "EdgeTransition", "InvariantPointAttention", "TranslationIPA"}
+    base = sampler._graph_key(cpu_net, feats, 2, 12)
+    assert base == sampler._graph_key(cpu_net, feats, 2, 12)
+    for (cls, a), m in first.items():
+        old = getattr(m, a)
+        new = (not old) if isinstance(old, bool) else old + 5 if isinstance(old, int) else {"f16x3": "f32", "f32": "f16x3"}[old]
+        setattr(m, a, new)
+        try:
+            assert sampler._graph_key(cpu_net, feats, 2, 12) != base, (cls, a)
+        finally:
+            setattr(m, a, old)
+    assert sampler._graph_key(cpu_net, feats, 2, 12) == base
