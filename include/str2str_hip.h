@@ -84,7 +84,17 @@ int s2s_edge_transition(const float* edge, const float* node_ab, const float* no
  *   (layers.py:181), and the part of it that depends on node j alone, Wf[:,256:384].n'_j + bf, does not have to be added to the
  *   hidden values of every pair.  (The i-side residual n'_i is still added in the kernel: node_p [B,N,128] = n'.)  All factors are
  *   powers of two: the caller folds them into the per-node layers that produce node_ab (EdgeTransition.ab16_specs) or scales a plain
- *   node_ab (ops.edge_transition_f16x3 does, unless told that node_ab has this form already). */
+ *   node_ab (ops.edge_transition_f16x3 does, unless told that node_ab has this form already).
+ *   CENTRED FINAL LAYER.  LayerNorm(Wf x + bf) = LayerNorm(C Wf x + C bf) exactly for C = I - 1 1^T / 128, so the kernel is handed
+ *   the final layer without the component common to its 128 output channels: the Wf stages of weight_stream are packed from C Wf
+ *   and G_j is C (Wf[:,256:384].n'_j + bf) -- both centred in float64 on the host where they are packed (EdgeTransition._packed,
+ *   .node_layers; ops.edge_transition_f16x3 centres a plain node_ab's third group).  y then has channel mean 0 up to rounding for
+ *   every pair: the LayerNorm's plain mean has nothing to lose, and the accumulators that start at 2^5 G_j round at the spread's
+ *   magnitude, not at an offset's (a trained checkpoint's common component is unconstrained: the loss has no gradient on it).  The
+ *   kernel itself does not depend on it -- uncentred operands give the same function with an error that grows with
+ *   |channel mean| / channel spread (measured at 30: 1.9e-5 of the row's scale through the start value, 2.6e-5 through the fp32
+ *   kernel's mean).  The same holds for s2s_edge_transition (wf_packed, bf centred: EdgeTransition._packed_f32, ._bf_centred) and
+ *   for the last layer of both edge-embedding kernels (w3_packed / the W3 stages and b3: EmbeddingModule._weights). */
 int s2s_edge_transition_f16x3(const float* edge, const float* node_ab, const float* node_p, const void* weight_stream,
                               const float* b2, const float* ln_gamma, const float* ln_beta,
                               const float* mask, float* out, int n_samples, int n_res, float ln_eps, int io_layout,

@@ -22,7 +22,7 @@ from ...arith import default_arith
 from ...common.all_atom import compute_backbone
 from ...common.rigid_utils import Rigid
 from .ipa import TranslationIPA  # noqa: F401  (re-exported like the reference module)
-from .layers import DerivedCache
+from .layers import DerivedCache, centred
 
 
 def get_positional_embedding(indices: torch.Tensor, embedding_dim: int, max_len: int = 2056) -> torch.Tensor:
@@ -93,7 +93,9 @@ class EmbeddingModule(nn.Module):
                 # of one elementwise product + row sum instead of three of each
                 "w_t_cat": torch.cat([wn[:, :ie], w0[:, :ie], w0[:, t1:t1 + ie]], dim=0).contiguous(),
                 "b_t_cat": torch.cat([n0.bias.float(), e0.bias.float(), torch.zeros_like(e0.bias.float())]).contiguous(),
-                "w2p": ops.pack_weight(e2.weight.float()), "w3p": ops.pack_weight(e4.weight.float()),
+                # the last layer stands in front of the LayerNorm: weights and bias centred over the output channels (layers.centred)
+                "w3c": centred(e4.weight), "b3c": centred(e4.bias),
+                "w2p": ops.pack_weight(e2.weight.float()), "w3p": ops.pack_weight(centred(e4.weight)),
                 "node_mlp": [ops.pack_node_layer(self.node_embed[2].weight, self.node_embed[2].bias),
                              ops.pack_node_layer(self.node_embed[4].weight, self.node_embed[4].bias, True)],
             }
@@ -106,7 +108,7 @@ class EmbeddingModule(nn.Module):
             return out
 
         ne = self.node_embed
-        return self._wcache.get([e0.weight, e0.bias, e2.weight, e4.weight, ne[0].weight, ne[0].bias, ne[2].weight, ne[2].bias,
+        return self._wcache.get([e0.weight, e0.bias, e2.weight, e4.weight, e4.bias, ne[0].weight, ne[0].bias, ne[2].weight, ne[2].bias,
                                  ne[4].weight, ne[4].bias], build)
 
     def _fixed_terms(self, fixed_mask: torch.Tensor, w: dict, dev, node_pos: torch.Tensor):
@@ -216,20 +218,20 @@ class EmbeddingModule(nn.Module):
         ca = self_conditioning_ca.to(dev).float().contiguous() if self.self_conditioning else node_a.new_zeros(B, L, 3)
         e2, e4, ln = self.edge_embed[2], self.edge_embed[4], self.edge_embed[5]
         if f16:
-            e2w, e4w = e2.weight, e4.weight
-            ws = self._w16cache.get([e2w, e4w], lambda: ops.pack_f16x3_embed_stream(e2w.float(), e4w.float()))
+            e2w = e2.weight
+            ws = self._w16cache.get([e2w, w["w3c"]], lambda: ops.pack_f16x3_embed_stream(e2w.float(), w["w3c"]))
             proj = None
             if next_proj is not None:  # 5-stage stream: W2 | W3 | the first IPA block's projection stage
                 stream = self._proj_cache.get([ws, next_proj["wp_f16x2"]], lambda: torch.cat([ws, next_proj["wp_f16x2"]]))
                 proj = (stream, next_proj["b64"])
             edge_embed = ops.edge_embed_f16x3(node_a, node_b, rel_cb, w["bin_tab_cb"], w["bin_lower"], idx_dev, ca, ws, e2.bias,
-                                              e4.bias, ln.weight, ln.bias, mask, span, ln.eps, proj=proj, column_blocked_tables=True,
+                                              w["b3c"], ln.weight, ln.bias, mask, span, ln.eps, proj=proj, column_blocked_tables=True,
                                               out_layout=edge_layout)
         else:
             if edge_layout != "rowmajor":
                 raise ops.HipLibraryError("EmbeddingModule: the tiled pair layout belongs to the f16x3 kernels")
             edge_embed = ops.edge_embed(node_a, node_b, rel_tab, w["bin_tab"], w["bin_lower"], idx_dev, ca, w["w2p"],
-                                        w["w3p"], e2.bias, e4.bias, ln.weight, ln.bias, mask, span, ln.eps,
+                                        w["w3p"], e2.bias, w["b3c"], ln.weight, ln.bias, mask, span, ln.eps,
                                         proj=None if next_proj is None else (next_proj["wp"], next_proj["b64"]))
         if next_proj is not None:
             edge_embed, *proj = edge_embed

@@ -56,6 +56,14 @@ class DerivedCache:
         return self._val, self._src
 
 
+def centred(w: torch.Tensor) -> torch.Tensor:
+    """C w with C = I - 1 1^T / n over dim 0 (the output channels), in float64 on the host, rounded once to float32.
+    LayerNorm(W x + b) = LayerNorm(C W x + C b) exactly, so a layer in front of a LayerNorm is packed centred: the kernels then
+    never see the component common to all channels -- neither in the LayerNorm's mean nor as an accumulator's start value."""
+    w64 = w.detach().double().cpu()
+    return (w64 - w64.mean(dim=0, keepdim=True)).float().to(w.device).contiguous()
+
+
 class Linear(nn.Linear):
     def __init__(self, in_dim: int, out_dim: int, bias: bool = True, init: str = "default", init_fn=None):
         super().__init__(in_dim, out_dim, bias=bias)
@@ -130,17 +138,18 @@ class EdgeTransition(nn.Module):
         self.final_layer = Linear(hidden, edge_embed_out, init="final")
         self.layer_norm = nn.LayerNorm(edge_embed_out)
         self._shape = (edge_embed_in, bias_embed_size, hidden, edge_embed_out, num_layers)
-        self._cache, self._cache32, self._proj_cache, self._node_cache, self._c32 = (DerivedCache() for _ in range(5))
+        self._cache, self._cache32, self._proj_cache, self._node_cache, self._c32, self._bf_cache = (DerivedCache() for _ in range(6))
         self.arith = default_arith()      # "f16x3" (csrc/pair_mlp_f16.hip) | "f32" (csrc/pair_mlp.hip): see str2str_amd/arith.py
         self.prescale_exp = 0             # f16x3: block exponent of the hidden activations (planes hold 2^-e x the value; the sampler raises
         #                                   it when the range guard reports activations of 2^15 and beyond: sampler.denoise_loop)
 
     def _packed(self):
-        """Weight stream of the split-f16 kernel."""
+        """Weight stream of the split-f16 kernel.  The final layer stands in front of the LayerNorm and is packed centred (``centred``),
+        here and in ``_packed_f32``, ``node_layers`` (G_j) and ``_bf_centred``: y has channel mean 0 up to rounding for every pair."""
         w1, w2, wf = self.trunk[0], self.trunk[2], self.final_layer
         ce = self._shape[0]
         return self._cache.get([w1.weight, w2.weight, wf.weight], lambda: {
-            "wstream_f16": ops.pack_f16x3_stream(w1.weight[:, :ce].float(), w2.weight.float(), wf.weight.float())})
+            "wstream_f16": ops.pack_f16x3_stream(w1.weight[:, :ce].float(), w2.weight.float(), centred(wf.weight))})
 
     def _packed_f32(self):
         w1, w2, wf = self.trunk[0], self.trunk[2], self.final_layer
@@ -148,19 +157,26 @@ class EdgeTransition(nn.Module):
         return self._cache32.get([w1.weight, w2.weight, wf.weight], lambda: {
             "w1p": ops.pack_weight(w1.weight[:, :ce].float(), tile_major=True),
             "w2p": ops.pack_weight(w2.weight.float(), tile_major=True),
-            "wfp": ops.pack_weight(wf.weight.float(), tile_major=True)})
+            "wfp": ops.pack_weight(centred(wf.weight), tile_major=True)})
+
+    def _bf_centred(self):
+        """The final layer's bias of the fp32 kernel, centred like its weights."""
+        bf = self.final_layer.bias
+        return self._bf_cache.get([bf], lambda: centred(bf))
 
     def node_layers(self):
         """The per-node parts as node-stream layers: n' = initial_embed(node) and everything a pair (i, j) takes from ONE of its nodes
         through a linear layer, [W1[:, ce:ce+cb] n' + b1 | W1[:, ce+cb:] n' | Wf[:, ce+cb:] n' + bf]  (384 + 384 + 128 columns): the row
         half A_i and the column half B_j of the first hidden layer, and G_j = the j-side residual of the final layer's input
-        x = h2 + [e | n'_i | n'_j] (reference layers.py:181) taken through that layer, its bias included."""
+        x = h2 + [e | n'_i | n'_j] (reference layers.py:181) taken through that layer, its bias included -- both centred over the 128
+        output channels (``centred``: the LayerNorm behind the layer removes that component anyway)."""
         w1, ie, wf = self.trunk[0], self.initial_embed, self.final_layer
 
         def build():
             ce, cb = self._shape[0], self._shape[1]
-            w_ab = torch.cat([w1.weight[:, ce:ce + cb], w1.weight[:, ce + cb:], wf.weight[:, ce + cb:]], dim=0).float().contiguous()
-            b_ab = torch.cat([w1.bias, torch.zeros_like(w1.bias), wf.bias]).float().contiguous()
+            # (the third group is the final layer's: centred over its 128 output channels, see ``_packed``)
+            w_ab = torch.cat([w1.weight[:, ce:ce + cb].float(), w1.weight[:, ce + cb:].float(), centred(wf.weight[:, ce + cb:])], dim=0).contiguous()
+            b_ab = torch.cat([w1.bias.float(), torch.zeros_like(w1.bias).float(), centred(wf.bias)]).contiguous()
             # "ab_s": the same vectors straight from s -- W_ab (W_ie s + b_ie) + b_ab = (W_ab W_ie) s + (W_ab b_ie + b_ab), folded in float64 on
             # the host -- so that both per-node parts read the block's node activations and run in ONE launch with the backbone update
             w64, ie64 = w_ab.detach().double().cpu(), ie.weight.detach().double().cpu()
@@ -238,7 +254,7 @@ class EdgeTransition(nn.Module):
             raise ops.HipLibraryError("EdgeTransition: the tiled pair layout and the scaled node_ab belong to the f16x3 kernels")
         pk = self._packed_f32()
         return ops.edge_transition(edge_embed.contiguous(), node_ab[..., :768].contiguous(), n_p, pk["w1p"], pk["w2p"], pk["wfp"],
-                                   self.trunk[2].bias, self.final_layer.bias, self.layer_norm.weight,
+                                   self.trunk[2].bias, self._bf_centred(), self.layer_norm.weight,
                                    self.layer_norm.bias, mask, self.layer_norm.eps,
                                    proj=None if next_proj is None else (next_proj["wp"], next_proj["b64"]))
 

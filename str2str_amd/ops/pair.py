@@ -28,7 +28,9 @@ def edge_transition_f16x3(edge, node_ab, node_p, wstream, b2, gamma, beta, mask,
     ``node_ab`` [B,N,896] = [W1[:,128:256] n' + b1 | W1[:,256:] n' | Wf[:,256:] n' + bf] as ``EdgeTransition.node_parts`` gives it (the
     pair's per-node linear parts: row half and column half of the first layer, the j-side residual taken through the final layer incl.
     its bias); ``ab_kernel_form``: the column half and the third group already carry the accumulators' 2^5 (the trunk's per-node layers
-    produce them so: no extra launch), see the C header."""
+    produce them so: no extra launch), see the C header.  A plain ``node_ab``'s third group is centred over its 128 channels here (the
+    LayerNorm removes a common component anyway, and as the accumulators' start value it would cost every accumulation its
+    rounding); the kernel form must arrive centred, as ``EdgeTransition.node_layers`` produces it."""
     lib = load_library()
     B, N = edge.shape[0], edge.shape[1]
     in_tiled = isinstance(edge, PairTiled)
@@ -46,6 +48,10 @@ def edge_transition_f16x3(edge, node_ab, node_p, wstream, b2, gamma, beta, mask,
         sc[384:768] = 1.0 if ab_kernel_form else 32.0
         sc[768:] = (1.0 if ab_kernel_form else 32.0) * 2.0 ** -int(prescale_exp)
         node_ab = node_ab * sc
+        if not ab_kernel_form:
+            # G_j starts the final layer's accumulators, in front of the LayerNorm: a component common to its 128 channels would only
+            # cost every accumulation its rounding.  Given vectors are centred here; the kernel form arrives centred (EdgeTransition.node_layers)
+            node_ab[..., 768:] -= node_ab[..., 768:].mean(dim=-1, keepdim=True)
     if out_layout not in ("rowmajor", "tiled", "none") or (out_layout == "none" and proj is None):
         raise HipLibraryError(f"edge_transition_f16x3: out_layout {out_layout!r}" + (" needs proj" if out_layout == "none" else ""))
     _req(edge.buf if in_tiled else edge, name="edge")

@@ -67,9 +67,10 @@ def sd_of(family):
     return trained_sd() if family == "trained-like" else synth_sd(0, 0.02)
 
 
-def mask_pattern(M, g):
-    """By row count: isolated zeros | a zero prefix | all zero."""
-    kind = ROWS.index(M) % 3 if M in ROWS else 0
+def mask_pattern(M, g, kind=None):
+    """By row count (or ``kind`` 0 | 1 | 2): isolated zeros | a zero prefix | all zero."""
+    if kind is None:
+        kind = ROWS.index(M) % 3 if M in ROWS else 0
     m = torch.ones(M)
     if kind == 0:
         m = (torch.rand(M, generator=g) >= 0.3).float()
@@ -190,15 +191,25 @@ def nanmax(t):
 
 def floors(trace):
     """Per record of a float64 trace: [M, n] absolute error bound of the f16x3 format (module docstring), earlier layers' floors
-    taken along (a record's ``x`` / ``residual`` that IS an earlier record's output carries that output's floor)."""
+    taken along (a record's ``x`` / ``residual`` that IS an earlier record's output carries that output's floor; so does an ``x`` that
+    is the sum of an earlier output, named by the record's ``x_from``, and a given tensor).  A record's ``exp`` = e scales the
+    activation term: planes of 2^-e x the value round to 2^(e-25) below 2^e x 0.25."""
     err, out = {}, []
     for rec in trace:
         x, w = rec["x"], rec["w"]
         ax, aw = x.abs(), w.abs()
         n = w.shape[0]
-        f = EPS_X * (((ax < X_LOW) & (ax > 0)).double() @ aw.t()) + EPS_W * (ax @ ((aw < W_LOW) & (aw > 0)).double().t())
-        if id(x) in err:
-            f = f + err[id(x)] @ aw.t()
+        k = 2.0 ** rec.get("exp", 0)      # a block exponent e: the planes hold 2^-e x the value (tests/ref_pair.py)
+        f = k * EPS_X * (((ax < k * X_LOW) & (ax > 0)).double() @ aw.t()) + EPS_W * (ax @ ((aw < W_LOW) & (aw > 0)).double().t())
+        src = rec.get("x_from", x)        # an input that is an earlier output PLUS a given tensor carries that output's floor
+        if id(src) in err:
+            f = f + err[id(src)] @ aw.t()
+        for t, idx, c0 in rec.get("x_add_from", ()):      # ... and a given tensor that is rows ``idx`` of an earlier output, at columns c0..
+            if id(t) in err:
+                f = f + err[id(t)][idx] @ aw[:, c0:c0 + err[id(t)].shape[1]].t()
+        for t, idx in rec.get("b_from", ()):              # a per-row bias gathered from rows ``idx`` of an earlier output
+            if id(t) in err:
+                f = f + err[id(t)][idx]
         if rec["pre_scale"] is not None:
             f = f * rec["pre_scale"].abs()[:, None]
         if rec["pre_mask"] is not None:

@@ -166,19 +166,27 @@ def backbone_update(sd, b, s1, diffuse_mask, dtype=torch.float64, L=layer, trace
     return L(s1, *lin(sd, f"{TRUNK}bb_update_{b}.linear"), pre_scale=diffuse_mask, dtype=dtype, trace=trace)
 
 
-def edge_node_parts(sd, b, s1, dtype=torch.float64, L=layer, trace=None):
+def edge_node_parts(sd, b, s1, dtype=torch.float64, L=layer, trace=None, prefix=None):
     """The EdgeTransition's per-node parts from the unfolded formula (reference layers.py:170-185; EdgeTransition.node_layers):
-    n' = initial_embed(s'), A = W1[:, ce:ce+cb] n' + b1, B = W1[:, ce+cb:] n', G = Wf[:, ce+cb:] n' + bf.
+    n' = initial_embed(s'), A = W1[:, ce:ce+cb] n' + b1, B = W1[:, ce+cb:] n', G = C (Wf[:, ce+cb:] n' + bf) with the centring
+    C = I - 1 1^T / 128 over the final layer's output channels: the layer stands in front of a LayerNorm, which removes the common
+    component, and the product packs it centred (layers.centred; ``centre``).
     -> (n' [M, 128], [A | 32 B | 32 G] [M, 896]: the form the f16x3 pair kernel reads)."""
-    p = f"{TRUNK}edge_transition_{b}."
+    p = f"{TRUNK}edge_transition_{b}." if prefix is None else prefix
     n_p = L(s1, *lin(sd, p + "initial_embed"), dtype=dtype, trace=trace)
     cb = n_p.shape[-1]
     (w1, b1), (wf, bf) = lin(sd, p + "trunk.0"), lin(sd, p + "final_layer")
     ce = w1.shape[1] - 2 * cb
     A = L(n_p, w1[:, ce:ce + cb], b1, dtype=dtype, trace=trace)
     Bc = L(n_p, w1[:, ce + cb:], None, dtype=dtype, trace=trace)
-    G = L(n_p, wf[:, ce + cb:], bf, dtype=dtype, trace=trace)
+    G = L(n_p, centre(wf[:, ce + cb:]), centre(bf), dtype=dtype, trace=trace)
     return n_p, torch.cat([A, 32.0 * Bc, 32.0 * G], dim=-1)
+
+
+def centre(w):
+    """C w over dim 0 (the output channels) in float64: weights [n, K] or a bias [n] of a layer in front of a LayerNorm."""
+    w = w.double()
+    return w - w.mean(dim=0, keepdim=True)
 
 
 def torsion_head(sd, s1, gt=None, fixed=None, eps=1e-8, dtype=torch.float64, L=layer, trace=None):

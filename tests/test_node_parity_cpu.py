@@ -108,7 +108,7 @@ def walk_trunk(sd32, batch, visit=None, check=True):
         if b < nb - 1:
             n_p, ab = stage("edge_node_parts", b, RN.edge_node_parts, sd, b, s1)
             p = f"{TR}edge_transition_{b}"
-            if check:      # the oracle's first layer and final layer on [0 | n'_i | n'_j] and [0 | 0 | n'_j]: A_i + B_j, G_j
+            if check:      # the oracle's first layer and final layer on [0 | n'_i | n'_j] and [0 | 0 | n'_j]: A_i + B_j, G_j (centred)
                 o_np = ON._lin(node, sd, p + ".initial_embed")
                 _close(n_p, rows(o_np), ("initial_embed", b))
                 i, j = 3 % N, 7 % N
@@ -116,7 +116,8 @@ def walk_trunk(sd32, batch, visit=None, check=True):
                 pre = ON._lin(torch.cat([z128, o_np[:, i], o_np[:, j]], -1), sd, p + ".trunk.0")
                 A, Bc, G = ab.view(B, N, -1)[..., :384], ab.view(B, N, -1)[..., 384:768] / 32, ab.view(B, N, -1)[..., 768:] / 32
                 _close(A[:, i] + Bc[:, j], pre, ("edge A_i + B_j", b))
-                _close(G[:, j], ON._lin(torch.cat([z128, z128, o_np[:, j]], -1), sd, p + ".final_layer"), ("edge G_j", b))
+                o_g = ON._lin(torch.cat([z128, z128, o_np[:, j]], -1), sd, p + ".final_layer")
+                _close(G[:, j], o_g - o_g.mean(-1, keepdim=True), ("edge G_j, centred over the channels", b))
             edge = ON.edge_transition(sd, p, node, edge) * edge_mask[..., None]
     gt = batch["torsion_angles_sin_cos"][..., 2, :].double()
     u, psi = stage("torsion_head", nb, RN.torsion_head, sd, rows(node), rows(gt), fixed.reshape(M))
