@@ -20,7 +20,10 @@
 // not (f << sum|terms|, or the O(omega^3) difference lo*dhi - hi*dlo at small omega) the reference's own float32 value is
 // rounding noise around this one.  Parity is judged against float64 anchors generated from the reference's own functions
 // (tests/golden/make_golden_score64.py): |ours - ref64| <= |ref32 - ref64| + 4e-5 |s| per residue.  Terms whose float32
-// weight exp(-l(l+1)sigma^2/2) underflowed to 0 contribute exactly 0 and are skipped.
+// weight exp(-l(l+1)sigma^2/2) underflowed to 0 contribute exactly 0 and are skipped.  Two departures from the chain: the
+// product quaternion q0^-1 qt is taken with w >= 0 before it becomes a rotation vector, and q0 = +-qt gives v = 0 (see there);
+// against float64 the score then sits within 3 x the chain's own principal-branch distance on every orientation and is exactly
+// 0 for one rotation on both sides (tests/score_cases.py).
 #include <hip/hip_runtime.h>
 
 #include "geom.h"
@@ -104,7 +107,20 @@ __global__ void __launch_bounds__(kThreads) se3_step_kernel(
         const float n2 = q0.w * q0.w + q0.x * q0.x + q0.y * q0.y + q0.z * q0.z;
         const Quat<float> q0inv{q0.w / n2, (q0.x * -1.0f) / n2, (q0.y * -1.0f) / n2, (q0.z * -1.0f) / n2};
         const Quat<float> q0i = matrix_to_quaternion<float>(quat_to_rot<float>(q0inv));
-        const Vec3<float> v = quaternion_to_axis_angle<float>(quat_multiply<float>(q0i, qtm));
+        // Both factors leave matrix_to_quaternion with their largest component positive, so whenever that component is not w
+        // the inverse and the frame take opposite signs and the product has w = -cos(theta / 2): the same rotation as angle
+        // 2 pi - theta, rebuilt as |xyz| * angle / sin(angle / 2) one rounding of atan2f from sin's zero (3e-6 / theta rad of
+        // noise in omega).  The representative with w >= 0 gives the same score vector (f is symmetric about pi, df
+        // antisymmetric, v flips) from the principal angle, where the conversion is well conditioned.
+        Quat<float> p = quat_multiply<float>(q0i, qtm);
+        if (p.w < 0.0f) { p.w = -p.w; p.x = -p.x; p.y = -p.y; p.z = -p.z; }
+        Vec3<float> v = quaternion_to_axis_angle<float>(p);
+        // One rotation on both sides (q0 = qt or q0 = -qt, component for component): R0^T Rt is the identity and the score is
+        // exactly 0.  The chain does not return that: invert_quat divides by |q|^2, which is 1 to float32 rounding only, so
+        // R(q0^-1) is not the exact transpose of R(qt) and v comes out as a few 1e-8 (a score of up to 1e-5 at sigma = 0.1).
+        const bool same = (q0.w == qt.w && q0.x == qt.x && q0.y == qt.y && q0.z == qt.z) ||
+                          (q0.w == -qt.w && q0.x == -qt.x && q0.y == -qt.y && q0.z == -qt.z);
+        if (same) v.x = v.y = v.z = 0.0f;
         const float omega = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z) + 1e-6f;
 
         const double omd = (double)omega;

@@ -82,6 +82,105 @@ def reverse_step64(xt7, rot_score, trans_score, t, dt, diffuse_mask, mask, cente
     return R_next, x_next
 
 
+# ----------------------------------------------------------------------------------------------- SE(3) score
+def quat_mul64(p, q):
+    """Hamilton product (w, x, y, z), float64.  The vector part adds its terms in the pairs that cancel in conj(q) (x) q, so that
+    product is exactly (|q|^2, 0, 0, 0)."""
+    a1, b1, c1, d1 = _f64(p).unbind(-1)
+    a2, b2, c2, d2 = _f64(q).unbind(-1)
+    return torch.stack([(a1 * a2 - b1 * b2) - (c1 * c2 + d1 * d2), (a1 * b2 + b1 * a2) + (c1 * d2 - d1 * c2),
+                        (a1 * c2 + c1 * a2) + (d1 * b2 - b1 * d2), (a1 * d2 + d1 * a2) + (b1 * c2 - c1 * b2)], -1)
+
+
+def relative_rotvec64(q0, qt):
+    """The principal rotation vector of R(q0)^T R(qt), angle in [0, pi]: the product of the normalised float64 quaternions with
+    its sign standardised (w >= 0), angle = 2 atan2(|xyz|, w).  Bit-equal quaternions give exactly 0."""
+    q0, qt = _f64(q0), _f64(qt)
+    q0 = q0 / q0.norm(dim=-1, keepdim=True) * torch.tensor([1.0, -1.0, -1.0, -1.0], dtype=F64)
+    p = quat_mul64(q0, qt / qt.norm(dim=-1, keepdim=True))
+    p = torch.where(p[..., :1] < 0, -p, p)
+    s = p[..., 1:].norm(dim=-1, keepdim=True)
+    theta = 2 * torch.atan2(s, p[..., :1])
+    return torch.where(s > 0, p[..., 1:] / s.clamp(min=1e-300) * theta, torch.zeros_like(p[..., 1:]))
+
+
+def igso3_series64(omega, sigma, L=1000):
+    """(f, df / d omega) of the IGSO(3) expansion, oracle/diffuser.py:36-63 term for term, in float64.  ``omega`` and ``sigma``
+    broadcast against each other; numpy, a thousand angles at a time."""
+    omega, sigma = np.broadcast_arrays(np.asarray(omega, dtype=np.float64), np.asarray(sigma, dtype=np.float64))
+    shape = omega.shape
+    om, sg = omega.reshape(-1), sigma.reshape(-1)
+    ls = np.arange(L, dtype=np.float64)[None]
+    f, df = np.empty_like(om), np.empty_like(om)
+    for a in range(0, om.size, 1024):
+        o, e = om[a:a + 1024, None], sg[a:a + 1024, None]
+        w = (2 * ls + 1) * np.exp(-ls * (ls + 1) * e ** 2 / 2)
+        hi, dhi = np.sin(o * (ls + 0.5)), (ls + 0.5) * np.cos(o * (ls + 0.5))
+        lo, dlo = np.sin(o / 2), 0.5 * np.cos(o / 2)
+        f[a:a + 1024] = (w * hi / lo).sum(-1)
+        df[a:a + 1024] = (w * (lo * dhi - hi * dlo) / lo ** 2).sum(-1)
+    return f.reshape(shape), df.reshape(shape)
+
+
+def rot_score_of_rotvec64(v, sigma):
+    """df / (f + 1e-4) * v / (omega + 1e-6) with omega = |v| + 1e-6 (so3.py:274-309 of the reference), float64.
+    ``v`` [B, N, 3], ``sigma`` [B]."""
+    v = _f64(v)
+    omega = v.norm(dim=-1) + 1e-6
+    f, df = igso3_series64(omega.numpy(), np.asarray(_f64(sigma)).reshape(-1, 1))
+    return (torch.as_tensor(df) / (torch.as_tensor(f) + 1e-4))[..., None] * v / (omega[..., None] + 1e-6)
+
+
+def trans_score64(x0, xt, p8, cs):
+    """-(cs x_t - e_half cs x_0) / cond_var with the schedule scalars of step_params, float64 (unmasked)."""
+    p8 = _f64(p8)
+    eh, cv = p8[:, 2].reshape(-1, 1, 1), p8[:, 3].reshape(-1, 1, 1)
+    return -(cs * _f64(xt) - eh * (cs * _f64(x0))) / cv
+
+
+def score64(x0_7, xt_7, t, mask, diffuser):
+    """The conditional score of the IGSO(3) x VP-SDE frame diffusion in float64 -> (rot [B,N,3], trans [B,N,3]), a pure function
+    of the float32 inputs.  Rotation: v = the principal rotation vector of R(q_0)^T R(q_t) (relative_rotvec64; the rotations are
+    quat_rot64 of each quaternion), omega = |v| + 1e-6, score = df / (f + 1e-4) * v / (omega + 1e-6) * mask with the 1000-term
+    series at sigma = the float32 bin value ``diffuser.step_params(t)[:, 0]``.  Translation, in coordinates scaled by 0.1:
+    -(0.1 x_t - e_half 0.1 x_0) / cond_var * mask."""
+    x0, xt, m = _f64(x0_7), _f64(xt_7), _f64(mask)[..., None]
+    p8 = diffuser.step_params(torch.as_tensor(t, dtype=torch.float32)).to(F64)
+    rot = rot_score_of_rotvec64(relative_rotvec64(x0[..., :4], xt[..., :4]), p8[:, 0])
+    trans = trans_score64(x0[..., 4:], xt[..., 4:], p8, float(diffuser.trans_diffuser.coordinate_scaling))
+    return rot * m, trans * m
+
+
+def score_chain32(x0_7, xt_7, p8, mask, standardise=False, cs=0.1):
+    """The reference's float32 conversion chain for v (oracle.geometry, as oracle.diffuser.FrameDiffuser.score strings it
+    together: inverse quaternion -> matrix -> quaternion, frame -> matrix -> quaternion, product, axis-angle), then the series
+    in float64, and the translation score in float32 -> (rot [B,N,3] float64, trans [B,N,3] float64, w [B,N] float32).
+    ``w`` is the real part of the float32 product: >= 0 on the principal branch (angle in [0, pi]), < 0 on the wrapped one
+    (angle 2 pi - delta, rebuilt as |xyz| angle / sin(angle / 2) next to sin's zero).  ``standardise``: the kernel's contract,
+    which negates the product where w < 0 before the axis-angle conversion and takes v = 0 where q_0 = +-q_t component for
+    component (one rotation on both sides; the chain's |q|^2 division leaves a few 1e-8 there)."""
+    from oracle import geometry as G
+
+    x0, xt = torch.as_tensor(x0_7).float(), torch.as_tensor(xt_7).float()
+    q0_inv = G.matrix_to_quaternion(G.quat_to_rot(G.invert_quat(x0[..., :4])))
+    qt = G.matrix_to_quaternion(G.quat_to_rot(xt[..., :4]))
+    p = G.quat_multiply(q0_inv, qt)
+    w = p[..., 0].clone()
+    if standardise:
+        p = torch.where(p[..., :1] < 0, -p, p)
+    v = G.quaternion_to_axis_angle(p)
+    if standardise:
+        a, b = x0[..., :4], xt[..., :4]
+        v = torch.where(((a == b).all(-1) | (a == -b).all(-1))[..., None], torch.zeros_like(v), v)
+    m = _f64(mask)[..., None]
+    p8 = torch.as_tensor(p8).float()
+    rot = rot_score_of_rotvec64(v, p8[:, 0]) * m
+    eh, cv = p8[:, 2].reshape(-1, 1, 1), p8[:, 3].reshape(-1, 1, 1)
+    csf = torch.tensor(cs, dtype=torch.float32)
+    trans = (-(xt[..., 4:] * csf - eh * (x0[..., 4:] * csf)) / cv).double() * m
+    return rot, trans, w
+
+
 # ----------------------------------------------------------------------------------------------- per-residue frame kernels
 def compose_update64(rigids7, update6, mask):
     """normalize(q + m q (x) (0, v)) and t + m R(q) u with R the un-normalised quadratic form -> [M, 7] float64."""
@@ -131,6 +230,54 @@ def prior_rotation64(z_axis, u, cdf_rows, row_of_sample, omega_grid):
     cdf, om = np.asarray(_f64(cdf_rows)), np.asarray(_f64(omega_grid))
     ang = np.stack([np.interp(u[b], cdf[int(r)], om) for b, r in enumerate(np.asarray(row_of_sample))])
     return rotvec_exp64(z / z.norm(dim=-1, keepdim=True) * torch.as_tensor(ang)[..., None])
+
+
+def matrix_rot64(m):
+    """The rotation a 3 x 3 block that is orthonormal to float32 rounding stands for: matrix -> quaternion (the four-candidate
+    formula, in float64) -> quat_rot64, which normalises."""
+    from oracle import geometry as G
+
+    return quat_rot64(G.matrix_to_quaternion(_f64(m)))
+
+
+def forward_marginal64(rig0_4x4, z_axis, u, z_trans, cdf_rows, row_of_sample, omega_grid, params2, diffuse_mask=None, cs=0.1):
+    """The noising branch of the forward marginal in float64 -> (R [B,N,3,3], x [B,N,3]), a pure function of the float32 frames
+    and noise.  Rotation: R_0 (matrix_rot64 of the 3 x 3 block) times the IGSO(3) draw prior_rotation64; translation, in
+    coordinates scaled by 0.1: (e_half 0.1 x_0 + std z) / 0.1 with (e_half, std) = params2 of the sample.  Residues with
+    ``diffuse_mask`` 0 keep R_0 and x_0."""
+    g = _f64(rig0_4x4)
+    R0, x0 = matrix_rot64(g[..., :3, :3]), g[..., :3, 3]
+    p2 = _f64(params2)
+    eh, std = p2[:, 0].reshape(-1, 1, 1), p2[:, 1].reshape(-1, 1, 1)
+    R = R0 @ prior_rotation64(z_axis, u, cdf_rows, row_of_sample, omega_grid)
+    x = (eh * (cs * x0) + std * _f64(z_trans)) / cs
+    if diffuse_mask is not None:
+        dm = _f64(diffuse_mask)[..., None]
+        R, x = torch.where(dm[..., None] > 0, R, R0), torch.where(dm > 0, x, x0)
+    return R, x
+
+
+def forward_marginal_chain32(rig0_4x4, z_axis, u, z_trans, cdf_rows, row_of_sample, omega_grid, params2, diffuse_mask=None, cs=0.1):
+    """oracle.diffuser.FrameDiffuser.forward_marginal on given noise, float32 with its float64 island (np.interp and
+    compose_rotvec), statement for statement -> frames [B, N, 7] float32.  tests/test_ref64_cpu.py holds it bit for bit to the
+    oracle's own call under the oracle's draws."""
+    from oracle import diffuser as OD
+    from oracle import geometry as G
+
+    g = torch.as_tensor(rig0_4x4).float()
+    rot_0, trans_0 = G.matrix_to_axis_angle(g[..., :3, :3]), g[..., :3, 3]
+    z = torch.as_tensor(z_axis).float()
+    x = z / torch.linalg.norm(z, dim=-1, keepdims=True)
+    cdf, om, uu = np.asarray(cdf_rows, dtype=np.float64), np.asarray(omega_grid), np.asarray(torch.as_tensor(u).float())
+    scal = torch.as_tensor(np.asarray([np.interp(uu[b], cdf[int(r)], om) for b, r in enumerate(np.asarray(row_of_sample))]), dtype=x.dtype)
+    rot_t = OD.compose_rotvec(rot_0, x * scal[..., None])
+    p2 = torch.as_tensor(params2).float()
+    loc = p2[:, 0].reshape(-1, 1, 1) * (trans_0 * cs)
+    trans_t = (torch.as_tensor(z_trans).float() * p2[:, 1].reshape(-1, 1, 1) + loc) / cs
+    if diffuse_mask is not None:
+        m = torch.as_tensor(diffuse_mask, dtype=trans_t.dtype)[..., None]
+        rot_t, trans_t = m * rot_t + (1 - m) * rot_0, m * trans_t + (1 - m) * trans_0
+    return G.Frames(trans_t, rot_mats=G.axis_angle_to_matrix(rot_t)).to_tensor_7()
 
 
 # ----------------------------------------------------------------------------------------------- ensemble statistics
@@ -289,6 +436,26 @@ def se3_case(family, N, diffuser):
                 noise_scale=ns, dt=torch.as_tensor(dt), dt_kind=dt_kind, z_rot=z_rot, z_trans=z_trans)
 
 
+def se3_fused_case(family, N, diffuser):
+    """se3_case plus a clean structure ``x0`` [B, N, 7] and, in place of the case's given scores, score64's: the inputs and the
+    float64 statement of the fused call the sampler makes.  x_0 is x_t turned by 0.05 .. 2 sigma of its sample (3 rad at most)
+    about a random axis and moved by 3 A: where a trajectory is, and where the chain's float32 series is well conditioned.
+    ``wrapped`` [B, N]: the branch of the chain's float32 product quaternion (score_chain32)."""
+    case = se3_case(family, N, diffuser)
+    rng = _rng("se3-fused", family, N)
+    sigma = case["p8"][:, 0].double().numpy()[:, None]
+    theta = np.minimum(rng.uniform(0.05, 2.0, size=(SE3_B, N)) * sigma, 3.0)
+    axis = rng.normal(size=(SE3_B, N, 3))
+    axis /= np.linalg.norm(axis, axis=-1, keepdims=True)
+    r_conj = np.concatenate([np.cos(theta / 2)[..., None], -np.sin(theta / 2)[..., None] * axis], -1)
+    q0 = quat_mul64(case["xt7"][..., :4], r_conj).numpy()            # R_0^T R_t = rot(theta, axis)
+    x0 = np.concatenate([q0, case["xt7"][..., 4:].numpy() + rng.normal(scale=3.0, size=(SE3_B, N, 3))], -1).astype(np.float32)
+    case["x0"] = torch.as_tensor(x0)
+    case["rot_score"], case["trans_score"] = score64(case["x0"], case["xt7"], case["t"], case["mask"], diffuser)
+    case["wrapped"] = score_chain32(case["x0"], case["xt7"], case["p8"], case["mask"])[2] < 0
+    return case
+
+
 def se3_ref64(case, diffuser):
     return reverse_step64(case["xt7"], case["rot_score"], case["trans_score"], case["t"], case["dt"], case["diffuse_mask"], case["mask"],
                           case["center"], case["noise_scale"], case["probability_flow"], case["z_rot"], case["z_trans"], diffuser)
@@ -297,7 +464,10 @@ def se3_ref64(case, diffuser):
 def se3_oracle(case, lengths=None, centers=None):
     """The float32 chain (oracle.diffuser.FrameDiffuser.reverse) on the case, one sample at a time on that sample's leading
     ``lengths[b]`` residues with its own dt and the generator seeded as se3_noise seeds it -> per sample (R [n,3,3], x [n,3])
-    float64, R from the normalised quaternion of the returned frame."""
+    float64, R from the normalised quaternion of the returned frame.  A case with ``x0`` (se3_fused_case) takes the chain's
+    own scores (FrameDiffuser.score, float32 series and all) in place of the given ones: the whole step.  Where the chain's
+    product quaternion is on the wrapped branch its rotation score is the noise the float64 suite exposes and would only widen
+    the distance; those residues keep the given (score64's) rotation score and the chain does the rest of the step."""
     from oracle import diffuser as OD
     from oracle.geometry import Frames
 
@@ -307,9 +477,13 @@ def se3_oracle(case, lengths=None, centers=None):
     for b, n in enumerate(lengths):
         sl = (slice(b, b + 1), slice(0, n))
         center = (case["center"] != 0) if centers is None else centers[b]
+        rs, ts = case["rot_score"][sl], case["trans_score"][sl]
+        if "x0" in case:
+            rs, ts = od.score(Frames.from_tensor_7(case["x0"][sl]), Frames.from_tensor_7(case["xt7"][sl]), case["t"][b:b + 1], case["mask"][sl].double())
+            rs = torch.where(case["wrapped"][sl][..., None], case["rot_score"][sl], rs)
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(case["seed"] + b)
-            nxt = od.reverse(Frames.from_tensor_7(case["xt7"][sl]), case["rot_score"][sl], case["trans_score"][sl], case["t"][b:b + 1],
+            nxt = od.reverse(Frames.from_tensor_7(case["xt7"][sl]), rs, ts, case["t"][b:b + 1],
                              float(case["dt"][b]), case["diffuse_mask"][sl].double(), center, case["noise_scale"],
                              case["probability_flow"]).to_tensor_7()[0]
         out.append((quat_rot64(nxt[:, :4]), nxt[:, 4:].double()))

@@ -1,5 +1,5 @@
-"""The HIP kernels that carry no matrix product -- the SE(3) step, the per-residue frame kernels, the forward-marginal prior and
-the ensemble statistics -- against the float64 references of tests/ref64.py, through ``str2str_amd.ops``, at the shapes where
+"""The HIP kernels that carry no matrix product -- the SE(3) step (score and reverse halves), the per-residue frame kernels, the
+forward marginal (prior and noising branches) and the ensemble statistics -- against the float64 references of tests/ref64.py, through ``str2str_amd.ops``, at the shapes where
 each kernel changes path (more than one workgroup, the strided residue loop, partial last workgroups, grid-stride loops).
 
 Tolerances.  SE(3) step: three times the distance of the reference's own float32 chain (oracle/) from float64 on the same case
@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import ref64
+import score_cases as sc
 from conftest import record_margin
 
 pytestmark = pytest.mark.gpu
@@ -113,6 +114,100 @@ def test_se3_fused_call_equals_split_calls(diffuser, family, N):
     assert (rs.cpu()[case["mask"] == 0] == 0).all() and (ts.cpu()[case["mask"] == 0] == 0).all()
     assert torch.equal(nxt, _reverse(case, rs, ts))
     assert not torch.equal(nxt[..., :4].cpu(), case["xt7"][..., :4])
+
+
+def _scores(c):
+    """The score-only call on a case of score_cases.score_case -> (rot, trans) [B, N, 3] float64 on the CPU."""
+    from str2str_amd import ops
+
+    _, rs, ts = ops.se3_step(_dev(c["x0"]), _dev(c["xt"]), _dev(c["mask"]), _dev(torch.ones_like(c["mask"])), _dev(c["p8"]), 0.0,
+                             want_next=False, want_scores=True)
+    assert rs.dtype == torch.float64 and ts.dtype == torch.float64
+    return rs.cpu(), ts.cpu()
+
+
+@pytest.mark.parametrize("N", sc.SCORE_N)
+def test_se3_scores_vs_float64(diffuser, N):
+    """The score half of the step (log(R_0^T R_t), the 1000-term IGSO(3) series, the translation score) against score64 on the
+    table of tests/score_cases.py: B = 3 at t = (min_t, 0.37, 1), eleven relative angles from exactly 0 to pi - 1e-5 laid
+    along the residues, x_t of every orientation class, a full, a gapped and a prefix mask over finite garbage, translations
+    up to +-300 A.  Per (angle, sample), residues on the principal and on the wrapped branch of the reference's float32 chain
+    judged and recorded apart, both against 3 x the chain's distance from float64 on the principal residues; the translation
+    score per sample against 3 x the float32 formula's distance; masked residues exactly 0.  Every figure is recorded before
+    the first assertion.
+
+    Before the product quaternion's sign was standardised in the kernel, the wrapped residues missed the bound at every angle
+    (measured on an MI355X at t = min_t: |error| 38 at theta = 1e-6, 1.5 at 1e-4, 0.14 at 1e-3, 1.6e-2 at 1e-2, 1.6e-3 at 0.1
+    against bounds of 4e-5 .. 5.5e-5; 1.4 .. 2.8 x the bound from theta = 1 up at t = 0.37 and 1) while the principal residues
+    sat where they sit now; tests/test_ref64_cpu.py plants the same mistake in the float32 chain."""
+    c = sc.score_case(N, diffuser)
+    D, Dt = sc.score_d32(diffuser)
+    rs, ts = _scores(c)
+    assert torch.isfinite(rs).all() and torch.isfinite(ts).all()
+    late = []
+    for which in ("principal", "wrapped"):
+        e = sc.score_family_errors(rs, N, diffuser, which)
+        for k in range(len(sc.SCORE_THETA)):
+            for b in range(sc.SCORE_B):
+                if not torch.isnan(e[k, b]):
+                    name = f"se3 rotation score vs float64 [{sc.family_label(k, b)}], {which} residues (bound 3 x D32)"
+                    record_margin(name, float(e[k, b]), 3 * float(D[k, b]))
+                    late.append((name, float(e[k, b]), 3 * float(D[k, b])))
+        ok = ~torch.isnan(e)
+        print(f"N={N} {which}: largest error / bound {float((e / (3 * D))[ok].max()) if ok.any() else 0.0:.3f}")
+    e_t = sc.trans_sample_errors(ts, N, diffuser)
+    for b in range(sc.SCORE_B):
+        name = f"se3 translation score vs float64 [t[{b}]] (bound 3 x float32 formula)"
+        record_margin(name, float(e_t[b]), 3 * float(Dt[b]))
+        late.append((name, float(e_t[b]), 3 * float(Dt[b])))
+    failed = [x for x in late if not x[1] < x[2]]
+    assert not failed, failed
+    masked = c["mask"] == 0
+    assert torch.equal(rs[masked], torch.zeros_like(rs[masked])) and torch.equal(ts[masked], torch.zeros_like(ts[masked]))
+
+
+def test_se3_scores_of_bit_equal_rotations_are_exactly_zero(diffuser):
+    """theta = 0 (x_0's quaternion bit-equal to x_t's) under mask 1: the rotation score is exactly 0, as score64 has it, at
+    every N of the table -- and with x_0's quaternion negated, which is the same rotation.
+
+    The chain the kernel restates does not return 0 there: invert_quat divides by |q|^2, which is 1 to float32 rounding only,
+    so R(q_0^-1) is not the exact transpose of R(q_t) and the product quaternion's vector part is a few 1e-8.  Measured on an
+    MI355X before the kernel took v = 0 for q_0 = +-q_t: 475 of the table's 693 such residues not exactly 0, largest |score|
+    1.03e-5 at t = min_t (sigma 0.1), 1.8e-7 at t = 0.37, 3.9e-8 at t = 1 (with the product's sign not standardised either:
+    39.7, 2.7, 0.53)."""
+    flip = torch.tensor([-1.0, -1, -1, -1, 1, 1, 1])
+    for sign in ("+", "-"):
+        worst, nonzero, total = 0.0, 0, 0
+        for N in sc.SCORE_N:
+            c = sc.score_case(N, diffuser)
+            zero = (c["band"] == 0) & (c["mask"] > 0)
+            assert torch.equal(c["x0"][..., :4][zero], c["xt"][..., :4][zero])
+            got = _scores(c if sign == "+" else dict(c, x0=c["x0"] * flip))[0][zero]
+            worst, nonzero, total = max(worst, float(got.abs().max())), nonzero + int((got != 0).any(-1).sum()), total + int(zero.sum())
+        print(f"theta = 0, q_0 = {sign}q_t: largest |rotation score| {worst:.3e}, {nonzero} of {total} residues not exactly 0")
+        record_margin(f"se3 rotation score at theta = 0, q_0 = {sign}q_t: largest |score| (required: exactly 0)", worst, 0.0)
+        assert nonzero == 0, (sign, worst, nonzero, total)
+
+
+@pytest.mark.parametrize("family,N", [("ode-c2", 65), ("sde03-c2", 513)])
+def test_se3_fused_step_vs_float64(diffuser, family, N):
+    """The call the sampler makes -- scores from x_0 and the reverse step in one launch -- against reverse_step64 fed score64's
+    scores (ref64.se3_fused_case: x_0 within 2 sigma of x_t, prefix masks, masked centre).  Bound: 3 x the distance of the
+    reference's float32 chain (its own score, then its reverse step) from that on the same case."""
+    from str2str_amd import ops
+
+    case = ref64.se3_fused_case(family, N, diffuser)
+    e_rot, e_trans = ref64.se3_oracle_distance(case, diffuser)
+    R64, x64 = ref64.se3_ref64(case, diffuser)
+    z_rot, z_trans = _noise(case)
+    nxt, rs, ts = ops.se3_step(_dev(case["x0"]), _dev(case["xt7"]), _dev(case["mask"]), _dev(case["diffuse_mask"]), _dev(case["p8"]), _dt(case),
+                               probability_flow=case["probability_flow"], center=case["center"], noise_scale=case["noise_scale"],
+                               z_rot=z_rot, z_trans=z_trans, want_next=True, want_scores=True)
+    a_rot, a_trans = _errors(nxt, R64, x64)
+    print(f"{family} N={N}: rot {a_rot:.3e} (chain {e_rot:.3e}), trans {a_trans:.3e} (chain {e_trans:.3e})")
+    check(f"se3 fused step vs float64 [{family}, N={N}]: rotation matrix entries (bound 3 x float32 chain)", a_rot, 3 * e_rot)
+    check(f"se3 fused step vs float64 [{family}, N={N}]: translations / sample scale (bound 3 x float32 chain)", a_trans, 3 * e_trans)
+    assert (rs.cpu()[case["mask"] == 0] == 0).all() and (ts.cpu()[case["mask"] == 0] == 0).all()
 
 
 @pytest.mark.parametrize("family,N", [("ode-c2", 65), ("sde03-c2", 513)])
@@ -230,6 +325,61 @@ def test_forward_marginal_prior_vs_float64(diffuser, rows):
     # the rows differ where it matters: sample 1 on its own row is not sample 1 on the others' row
     R_other = ref64.prior_rotation64(z_axis, u, cdf, (1, 1, 1), omega)
     assert float((R_other[1] - R[1]).abs().max()) > 1e-2
+
+
+@pytest.mark.parametrize("N", sc.FM_N)
+def test_forward_marginal_noising_vs_float64(diffuser, N):
+    """The noising branch (given rigids0_4x4: matrix -> axis-angle, the composition in float64, the VP translation, the blend,
+    back to a quaternion) against forward_marginal64 on the table of tests/score_cases.py: row_of_sample = (1, 0, 1) on the
+    diffuser's rows of t = 0.05 and 1, params2 at t = (min_t, 0.37, 1), uniforms on np.interp's branches, the planted frames,
+    compositions that cross pi, 4 x 4 inputs orthonormal to float32 rounding only, a fifth of the residues frozen.  Bound: 3 x
+    the float32 chain's distance on the same draws, at most 5e-6.  Frozen residues: translations bit for bit, rotations inside
+    the same bound."""
+    from str2str_amd import ops
+
+    c = sc.fm_case(N, diffuser)
+    out = ops.forward_marginal(_dev(c["rig0"]), _dev(c["z_axis"]), _dev(c["u"]), _dev(c["z_trans"]), _dev(c["cdf"]),
+                               _dev(torch.tensor(c["rows"], dtype=torch.int32)), _dev(c["omega"]), _dev(c["params2"]), _dev(c["diffuse_mask"])).cpu()
+    assert torch.isfinite(out).all()
+    a_rot, a_trans = sc.fm_errors(out, N, diffuser)
+    b_rot, b_trans = sc.fm_bounds(N, diffuser)
+    print(f"N={N}: rot {a_rot:.3e} (bound {b_rot:.3e}), trans {a_trans:.3e} (bound {b_trans:.3e})")
+    check(f"forward marginal, noising, vs float64 [N={N}]: rotation matrix entries (bound 3 x float32 chain, <= 5e-6)", a_rot, b_rot)
+    check(f"forward marginal, noising, vs float64 [N={N}]: translations / sample scale (bound 3 x float32 chain, <= 5e-6)", a_trans, b_trans)
+    frozen = c["diffuse_mask"] == 0
+    if frozen.any():
+        assert torch.equal(out[..., 4:][frozen], c["rig0"][..., :3, 3][frozen])
+        R64, _ = sc.fm_ref64(N, diffuser)
+        assert float((ref64.quat_rot64(out[..., :4]) - R64)[frozen].abs().max()) < b_rot
+
+
+def test_forward_marginal_device_noising_vs_float64(diffuser):
+    """The same through FrameDiffuser.forward_marginal_device with the noise given (N = 257, t_delta = 0.37): the wrapper's
+    CDF-row lookup and params2 against the reference's own formulae (oracle.diffuser.SO3 / R3), which the wrapper does not
+    share."""
+    from oracle import diffuser as OD
+
+    N, t_delta = 257, 0.37
+    c = sc.fm_case(N, diffuser)
+    out = diffuser.forward_marginal_device(_dev(c["rig0"]), t_delta, diffuse_mask=_dev(c["diffuse_mask"]),
+                                           noise=(_dev(c["z_axis"]), _dev(c["u"]), _dev(c["z_trans"]))).cpu()
+    so3, r3 = OD.SO3(), OD.R3()
+    t = torch.full((sc.FM_B,), t_delta, dtype=torch.float32)
+    mb = r3.marginal_b_t(t)
+    args = sc.fm_args(c, cdf_rows=so3.cdf_row(int(so3.t_to_idx(t[0])))[None], row_of_sample=(0, 0, 0), omega_grid=so3.discrete_omega,
+                      params2=torch.stack([torch.exp(-0.5 * mb), torch.sqrt(1 - torch.exp(-mb))], -1))
+    R64, x64 = ref64.forward_marginal64(**args)
+    chain = ref64.forward_marginal_chain32(**args)
+
+    def errors(o):
+        e = [ref64.rot_trans_error(ref64.quat_rot64(o[b, :, :4]), o[b, :, 4:], R64[b], x64[b]) for b in range(sc.FM_B)]
+        return max(a for a, _ in e), max(b for _, b in e)
+
+    (e_rot, e_trans), (a_rot, a_trans) = errors(chain), errors(out)
+    print(f"rot {a_rot:.3e} (chain {e_rot:.3e}), trans {a_trans:.3e} (chain {e_trans:.3e})")
+    check("forward_marginal_device, noising, vs float64: rotation matrix entries (bound 3 x float32 chain, <= 5e-6)", a_rot, min(3 * e_rot, sc.FM_CAP))
+    check("forward_marginal_device, noising, vs float64: translations / sample scale (bound 3 x float32 chain, <= 5e-6)", a_trans,
+          min(3 * e_trans, sc.FM_CAP))
 
 
 # ----------------------------------------------------------------------------------------------- ensemble statistics
