@@ -19,7 +19,11 @@ mean absolute difference of their per-residue relative accessibilities) and the 
 scattering curve and the Kirkwood hydrodynamic radius of the CA beads; no hydration shell, no excluded volume, no form-factor table) and
 writes ``saxs_<tag>_<mmdd-HH-MM>.csv`` (the mean relative difference of the two curves, the mean hydrodynamic radius of both, the JS
 distance of their distributions) and the curves ``saxs/<target>.csv``; ``+saxs_data=DIR`` adds the reduced chi^2 of the sampled
-ensemble's curve against the measured ``DIR/<target>.dat`` (columns q in 1/Angstrom, I, sigma)."""
+ensemble's curve against the measured ``DIR/<target>.dat`` (columns q in 1/Angstrom, I, sigma).
+``+dynamics=true`` also computes how the sampled and the target ensembles move (on the device: covariance of the superposed CA coordinates;
+the eigenproblem on the host) and writes ``dynamics_<tag>_<mmdd-HH-MM>.csv`` (the JS distance of the projections on the target's first two
+principal components, the RMSIP of the top ten, the mean absolute difference of the cross-correlation maps, the total variance of both)
+and the cross-correlations ``dynamics/<target>.csv``."""
 import logging
 import os
 import sys
@@ -93,6 +97,7 @@ SS_CLASSES = ("helix", "strand", "other")
 CONTACT_COLUMNS = ("q_mean", "q_mean_target", "js_q", "contact_mae", "rco", "rco_target")
 SASA_COLUMNS = ("sasa_mean", "sasa_mean_target", "js_sasa", "sasa_mae")
 SAXS_COLUMNS = ("saxs_mae", "rh_mean", "rh_mean_target", "js_rh")
+DYNAMICS_COLUMNS = ("js_pca", "rmsip", "dccm_mae", "var_total", "var_total_target")
 
 
 def _switch(name, value) -> bool:
@@ -188,6 +193,22 @@ def saxs_row(t):
     return row, {"q": metrics.SAXS_Q_GRID, "i_pred": np.around(curve["pred"], decimals=4), "i_target": np.around(curve["target"], decimals=4)}
 
 
+def dynamics_row(t):
+    """One row of the dynamics csv and the cross-correlations (every pair i < j) of both CA ensembles of the target ``t``: the PCA of
+    js_pca is the target ensemble's, the other columns live in the frame of its mean structure (metrics.dynamics_frame)."""
+    try:
+        covs = metrics.dynamics_frame(t.ca)                                                                   # the one superposition and covariance per ensemble
+    except ValueError as e:                    # an ensemble of one structure does not move: the columns stay NaN, the table empty
+        log.warning(f"dynamics of {t.pred_file}: {e}")
+        return _row(DYNAMICS_COLUMNS, ()), dict.fromkeys(("i", "j", "c_pred", "c_target"), ())
+    c = {k: metrics._dccm(v).cpu().numpy() for k, v in covs.items()}
+    var = metrics.total_variance_of(covs)
+    row = (metrics.js_pca(t.ca, return_pc=False)["pred"], metrics.rmsip_of(covs, {k: len(v) for k, v in t.ca.items()})["pred"],
+           metrics.dccm_mae_of(c)["pred"], var["pred"], var["target"])
+    i, j = np.triu_indices(len(c["pred"]), k=1)
+    return dict(zip(DYNAMICS_COLUMNS, row)), {"i": i, "j": j, "c_pred": np.around(c["pred"][i, j], decimals=4), "c_target": np.around(c["target"][i, j], decimals=4)}
+
+
 class Report(NamedTuple):
     """An optional report of ``evaluate_prediction``: ``+<name>=true`` switches it on, ``<name>/<target>.csv`` receives the table of every
     target and ``<prefix>_<tag>_<mmdd-HH-MM>.csv`` one row per target, with the mean row where ``mean_row`` says so."""
@@ -199,8 +220,9 @@ class Report(NamedTuple):
 
 
 REPORTS = (Report("secondary_structure", "ss", SS_COLUMNS, secondary_structure_row, False), Report("contacts", "contacts", CONTACT_COLUMNS, contacts_row, True),
-           Report("sasa", "sasa", SASA_COLUMNS, sasa_row, True), Report("saxs", "saxs", SAXS_COLUMNS, saxs_row, True))
-secondary_structure_switch, contacts_switch, sasa_switch, saxs_switch = (partial(_switch, r.name) for r in REPORTS)
+           Report("sasa", "sasa", SASA_COLUMNS, sasa_row, True), Report("saxs", "saxs", SAXS_COLUMNS, saxs_row, True),
+           Report("dynamics", "dynamics", DYNAMICS_COLUMNS, dynamics_row, True))
+secondary_structure_switch, contacts_switch, sasa_switch, saxs_switch, dynamics_switch = (partial(_switch, r.name) for r in REPORTS)
 
 
 def _write_summary(output_dir, prefix, tag, rows, columns, mean_row):
@@ -215,21 +237,22 @@ def _write_summary(output_dir, prefix, tag, rows, columns, mean_row):
 
 
 def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None, cluster_cutoff=None,
-                        secondary_structure=None, contacts=None, sasa=None, saxs=None, saxs_data=None):
+                        secondary_structure=None, contacts=None, sasa=None, saxs=None, saxs_data=None, dynamics=None):
     """reference src/eval.py:47-99: one row per target, one column per metric, plus the mean row.  ``extra_metrics``: names out of
     EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's).
     ``cluster_cutoff`` (A; None: nothing of this happens): the ``pred`` ensemble of every target is clustered by ``metrics.cluster_rmsd``;
     ``clusters/<target>.pdb`` receives the centres' MODELs, most populated first, and ``clusters_<tag>_<mmdd-HH-MM>.csv`` one row per
-    target (CLUSTER_COLUMNS), both next to the metrics csv.  ``secondary_structure``, ``contacts``, ``sasa``, ``saxs`` (true; otherwise
+    target (CLUSTER_COLUMNS), both next to the metrics csv.  ``secondary_structure``, ``contacts``, ``sasa``, ``saxs``, ``dynamics`` (true; otherwise
     nothing of it happens): the REPORTS on the ``pred`` and the ``target`` ensemble of every target.  Next to the metrics csv,
     ``ss_<tag>_<mmdd-HH-MM>.csv`` (SS_COLUMNS) and ``secondary_structure/<target>.csv`` receive the states' content and the per-residue
     propensities; ``contacts_...csv`` (CONTACT_COLUMNS) and ``contacts/<target>.csv`` the native-contact and contact-order summaries and
     the contact probabilities; ``sasa_...csv`` (SASA_COLUMNS) and ``sasa/<target>.csv`` the surface summaries and the per-residue mean
     surface and mean relative accessibility; ``saxs_...csv`` (SAXS_COLUMNS, and ``saxs_chi2`` against ``<saxs_data>/<target>.dat`` when
-    the directory ``saxs_data`` is given) and ``saxs/<target>.csv`` the scattering summaries and the curves.  All but the ss csv end
+    the directory ``saxs_data`` is given) and ``saxs/<target>.csv`` the scattering summaries and the curves; ``dynamics_...csv``
+    (DYNAMICS_COLUMNS) and ``dynamics/<target>.csv`` the essential-dynamics summaries and the cross-correlations.  All but the ss csv end
     with the mean row."""
     columns = metric_columns(extra_metrics)
-    switches = dict(secondary_structure=secondary_structure, contacts=contacts, sasa=sasa, saxs=saxs)
+    switches = dict(secondary_structure=secondary_structure, contacts=contacts, sasa=sasa, saxs=saxs, dynamics=dynamics)
     reports = [r for r in REPORTS if _switch(r.name, switches[r.name])]
     if saxs_data is not None and not _switch("saxs", saxs):
         raise ValueError(f"saxs_data {saxs_data}: needs saxs=true")
@@ -304,7 +327,7 @@ def evaluate(cfg):
     pred_dir = cfg.get("pred_dir")
     scoring = dict(target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"), extra_metrics=cfg.get("extra_metrics"),
                    cluster_cutoff=cfg.get("cluster_cutoff"), secondary_structure=cfg.get("secondary_structure"),
-                   contacts=cfg.get("contacts"), sasa=cfg.get("sasa"), saxs=cfg.get("saxs"), saxs_data=cfg.get("saxs_data"))
+                   contacts=cfg.get("contacts"), sasa=cfg.get("sasa"), saxs=cfg.get("saxs"), saxs_data=cfg.get("saxs_data"), dynamics=cfg.get("dynamics"))
     if pred_dir and os.path.isdir(pred_dir):
         log.info(f"Found pre-computed prediction directory {pred_dir}.")
         return evaluate_prediction(pred_dir, **scoring)

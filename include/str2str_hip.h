@@ -708,6 +708,40 @@ int s2s_backbone_sasa(const float* atoms, int n, int n_res, const unsigned char*
 int s2s_ca_scattering(const float* ca, int n, int n_res, const double* q, int n_q, const int* types, const double* table, int n_types,
                       double* intensity, double* inv_r_mean, void* stream);
 
+/* ---- Essential dynamics: how does the ensemble move?  Mean structure, covariance and projections of the superposed CA coordinates
+ * (csrc/ensemble_pca.hip; what `gmx covar` / `gmx anaeig` compute; no counterpart in the reference) ----
+ * x [n, n_res, 3] float32 CA coordinates; xform [n, 12] float64 in s2s_ca_superpose's layout (NULL: the identity); p [n] float64 sample
+ * weights, >= 0 and summing to 1 (the caller normalises; NULL: 1 / n each).  With c = 3 i + a the coordinate a of residue i:
+ *  Aligned coordinate.  y_sc = ((R_a0 x_i0 + R_a1 x_i1) + R_a2 x_i2) + t_a in float64 on the widened coordinates (contraction allowed: an fma
+ *     only removes a rounding); with xform NULL y_sc is the widened x itself.  y is never rounded to float32.
+ *  Mean.  m_c = sum_s p_s y_sc.  Thread g of 16 adds the structures g, g + 16, ... in ascending order, the 16 partial sums are added in
+ *     ascending g: the order depends on n alone.
+ *  Covariance (population form, no Bessel factor; two-pass).  C[r, c] = sum_s p_s (y_sr - m_r)(y_sc - m_c) about the GIVEN mean.  A prepass
+ *     writes z_sc = sqrt(p_s) (y_sc - m_c) as float64 into the workspace in blocks of 48 coordinates x 4-padded structures,
+ *     ws[(blk * Sp + k) * 48 + r], padding rows and columns zero.  One wave forms a 48 x 48 block of C on v_mfma_f64_16x16x4_f64 in nine
+ *     accumulator tiles, the k loop over the structures in ascending order, four per instruction.  Only blocks on or above the diagonal are
+ *     computed; every entry with r <= c is stored and copied to (c, r), so C is exactly symmetric.  The structures go through the workspace
+ *     in chunks of a multiple of 4; the accumulators of a later chunk start from the running C, so every entry is the same chain of
+ *     instructions -- the same bits -- for any workspace size.
+ *  Projection.  proj[s, k] = sum_c (y_sc - m_c) v_kc for components v [n_components, 3 n_res] float64.  One wave per structure; lane l adds
+ *     the coordinates l, l + 64, ... in ascending order, the lanes meet in the xor tree: the order depends on n_res alone.
+ * What this is NOT: an eigensolver (the symmetric eigenproblem of C is the host's), anything beyond CA atoms.  No gradients. */
+#define S2S_PCA_MAX_RES 1024   /* 3 n_res = 3072 coordinates: a structure's centred coordinates stay in LDS as float64, 24 KiB */
+/* the workspace of s2s_ca_covariance that takes the structures in chunks of `chunk` (rounded up to a multiple of 4) */
+#define S2S_PCA_WORKSPACE_DOUBLES(n_res, chunk) ((3ll * (n_res) + 47) / 48 * 48 * (((long long)(chunk) + 3) / 4 * 4))
+
+/* No scratch.  n >= 1, 1 <= n_res <= S2S_PCA_MAX_RES; otherwise hipErrorInvalidValue before any launch.  mean [n_res, 3] float64. */
+int s2s_ca_aligned_mean(const float* x, int n, int n_res, const double* xform, const double* p, double* mean, void* stream);
+
+/* cov [3 n_res, 3 n_res] float64, every entry written.  workspace: caller-owned, workspace_doubles >= S2S_PCA_WORKSPACE_DOUBLES(n_res, 4);
+ * the chunk is the largest multiple of 4 structures it holds (at most n rounded up to 4).  The same checks. */
+int s2s_ca_covariance(const float* x, int n, int n_res, const double* xform, const double* p, const double* mean, double* cov,
+                      double* workspace, long long workspace_doubles, void* stream);
+
+/* proj [n, n_components] float64.  No scratch.  The same checks, and n_components >= 1. */
+int s2s_ca_project(const float* x, int n, int n_res, const double* xform, const double* mean, const double* components, int n_components,
+                   double* proj, void* stream);
+
 /* ---- PDB text at the exit of the path (HOST pointers, host code; byte-identical to the reference's writers) ---- */
 
 /* protein.to_pdb per model (src/common/protein.py:152-234) over atom37 [n_models, n_res, 37, 3] float32 HOST coordinates with

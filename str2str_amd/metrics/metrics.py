@@ -32,7 +32,10 @@ test on N, CA, C, O, CB -- no side chains, so absolute areas overstate the expos
 and ``js_sasa`` as the summaries.  What a solution measurement would see: ``saxs_profile``, ``ensemble_saxs`` and ``hydrodynamic_radius``
 (csrc/ensemble_saxs.hip: the Debye intensity and the Kirkwood radius of the CA beads -- no hydration shell, no excluded volume, no
 built-in form factors, no side chains), ``saxs_mae``, ``mean_rh`` and ``js_rh`` as the summaries, ``saxs_chi2`` and ``read_saxs_dat`` for
-the comparison with a measured curve.
+the comparison with a measured curve.  How the ensemble moves: ``ensemble_covariance``, ``cross_correlation``, ``pca`` and ``pca_project``
+(csrc/ensemble_pca.hip: mean structure, 3L x 3L covariance and projections of the superposed CA coordinates in float64; the symmetric
+eigenproblem stays on the host), with ``js_pca``, ``rmsip``, ``dccm_mae`` and ``total_variance`` as the summaries -- Cartesian PCA of one
+global superposition, CA only, no quasi-harmonic entropy.
 """
 from __future__ import annotations
 
@@ -819,6 +822,192 @@ def read_saxs_dat(path, q_unit="1/A"):
                 rows.append(row)
     data = np.asarray(rows, dtype=np.float64).reshape(-1, 3)
     return (data[:, 0] / 10.0 if q_unit == "1/nm" else data[:, 0].copy()), data[:, 1].copy(), data[:, 2].copy()
+
+
+# ---- essential dynamics: covariance, PCA, cross-correlation (csrc/ensemble_pca.hip; include/str2str_hip.h has the definition) ----
+class EnsemblePCA(NamedTuple):
+    """The principal components of the superposed CA coordinates of an ensemble [R, L, 3], float64: ``mean`` [L, 3] (the mean structure
+    the covariance is taken about), ``components`` [K, 3L] (orthonormal rows, coordinate 3 i + a, descending variance, every row's
+    largest-magnitude entry positive), ``variances`` [K] (A^2, clamped at 0), ``total_variance`` (tr C, the sum of the squared RMSF) and
+    ``projections`` [R, K] (the fitted structures themselves, under the transforms that made the covariance, on the components)."""
+    mean: np.ndarray
+    components: np.ndarray
+    variances: np.ndarray
+    total_variance: float
+    projections: np.ndarray
+
+
+def _aligned_moments(x, xform, sample_weights=None, max_structures=None):
+    """-> device float64 (mean [L, 3], covariance [3L, 3L]) of the ensemble x under ``xform`` (None: the identity): two-pass."""
+    mean = ops.ca_aligned_mean(x, xform, sample_weights)
+    return mean, ops.ca_covariance(x, mean, xform, sample_weights, max_structures)
+
+
+def _fit_and_moments(coords, target, sample_weights, residue_weights, n_fit_rounds, fit):
+    x = _dev(coords)
+    xform = ops.ca_fit_transforms(x, None if target is None else _dev(target)[0], sample_weights, residue_weights, n_fit_rounds, fit)
+    return (x, xform, *_aligned_moments(x, xform, sample_weights))
+
+
+def ensemble_covariance(coords, target=None, sample_weights=None, residue_weights=None, n_fit_rounds=5, fit=True):
+    """How does the ensemble move?  -> (mean [L, 3], covariance [3L, 3L]) float64 of the CA coordinates ``coords`` [R, L, 3] after
+    superposition: every structure is superposed (``superpose``'s optimal proper rotation + translation, per-residue ``residue_weights``
+    [L] if given) onto ``target`` [L, 3] (default: the first structure), ``n_fit_rounds`` times, the target of every further round being the
+    mean of the superposed structures rounded to float32 -- a fixed count, no data-dependent stop.  ``fit=False``: the input is already
+    aligned.  With y_s the transformed structure in float64 (never rounded to float32) and p = ``sample_weights`` [R] (>= 0, normalised
+    to sum 1; default 1 / R): mean = sum_s p_s y_s and C[3i+a, 3j+b] = sum_s p_s (y_sia - m_ia)(y_sjb - m_jb), the population covariance (no
+    Bessel factor), two-pass, exactly symmetric.  One structure gives all zeros.  CA atoms only, at most ops.PCA_MAX_RES residues."""
+    _, _, mean, cov = _fit_and_moments(coords, target, sample_weights, residue_weights, n_fit_rounds, fit)
+    return mean.cpu().numpy(), cov.cpu().numpy()
+
+
+def _dccm(cov: torch.Tensor) -> torch.Tensor:
+    """Covariance [3L, 3L] -> [L, L]: c_ij = tr C_ij / sqrt(tr C_ii tr C_jj) over the 3 x 3 blocks; the diagonal is exactly 1, c_ij = 0
+    wherever either trace is 0 (a residue that does not move)."""
+    L = cov.shape[0] // 3
+    blocks = cov.reshape(L, 3, L, 3)
+    tr = (blocks[:, 0, :, 0] + blocks[:, 1, :, 1]) + blocks[:, 2, :, 2]
+    d = tr.diagonal()
+    den = (d[:, None] * d[None, :]).sqrt()
+    c = torch.where(den > 0.0, tr / torch.where(den > 0.0, den, torch.ones_like(den)), torch.zeros_like(tr)).clamp(-1.0, 1.0)
+    c.fill_diagonal_(1.0)
+    return c
+
+
+def cross_correlation(coords, target=None, sample_weights=None, residue_weights=None, n_fit_rounds=5, fit=True) -> np.ndarray:
+    """Which residues move together?  The dynamical cross-correlation map of ``ensemble_covariance``'s C (same arguments) -> float64 [L, L]
+    in [-1, 1]: c_ij = <dr_i . dr_j> / sqrt(<|dr_i|^2> <|dr_j|^2>) = tr C_ij / sqrt(tr C_ii tr C_jj).  The diagonal is exactly 1; c_ij = 0
+    where residue i or j does not move at all."""
+    return _dccm(_fit_and_moments(coords, target, sample_weights, residue_weights, n_fit_rounds, fit)[3]).cpu().numpy()
+
+
+def _top_components(cov: np.ndarray, k: int):
+    """The ``k`` largest eigenpairs of the symmetric ``cov`` -> (variances [k] descending, clamped at 0; components [k, n], every row's
+    largest-magnitude entry positive: the rule of ``tica_fit``'s ``canonical``)."""
+    import scipy.linalg
+
+    n = cov.shape[0]
+    vals, vecs = scipy.linalg.eigh(cov, subset_by_index=[n - k, n - 1])
+    vals, vecs = vals[::-1], vecs[:, ::-1].T
+    top = np.argmax(np.abs(vecs), axis=1)
+    sign = np.sign(vecs[np.arange(k), top])
+    return np.maximum(vals, 0.0), np.ascontiguousarray(vecs * np.where(sign == 0.0, 1.0, sign)[:, None])
+
+
+def _at_least_two(fn, x):
+    if x.shape[0] < 2:
+        raise ValueError(f"{fn}: needs at least 2 structures, got {x.shape[0]}")
+    return x
+
+
+def pca(coords, n_components=10, target=None, sample_weights=None, residue_weights=None, n_fit_rounds=5, fit=True) -> EnsemblePCA:
+    """Which collective coordinates carry the variance?  Principal components of ``ensemble_covariance``'s C (same arguments; R >= 2):
+    the top ``n_components`` (1 .. 3L) eigenpairs in descending eigenvalue order with canonical signs, variances clamped at 0.  The mean,
+    the covariance and the projections run on the device; the symmetric 3L x 3L eigenproblem runs on the host (scipy.linalg.eigh, as
+    ``tica_fit``'s does), for the top components only: 0.23 s at 3L = 768 and 0.46 s at 3L = 3072 for ten of them (profiles/pca_timing.md;
+    a full decomposition at 3072 is on the order of 10 s, an unmeasured estimate), against milliseconds on the device.  It is well-posed for
+    the top components even with fewer structures than coordinates (at most R - 1 variances are non-zero).  Cartesian PCA of ONE global
+    superposition: a hinge smears across components (``lddt`` and ``contact_map`` are the superposition-free tools)."""
+    x = _at_least_two("pca", _dev(coords))
+    n3 = 3 * x.shape[1]
+    if isinstance(n_components, bool) or int(n_components) != n_components or not 1 <= n_components <= n3:
+        raise ValueError(f"pca: n_components must be an integer in 1 .. {n3}, got {n_components}")
+    x, xform, mean, cov = _fit_and_moments(x, target, sample_weights, residue_weights, n_fit_rounds, fit)
+    cov_h = cov.cpu().numpy()
+    variances, components = _top_components(cov_h, int(n_components))
+    proj = ops.ca_project(x, mean, torch.as_tensor(components, device=x.device), xform)
+    return EnsemblePCA(mean.cpu().numpy(), components, variances, float(np.trace(cov_h)), proj.cpu().numpy())
+
+
+def pca_project(coords, model: EnsemblePCA, residue_weights=None) -> np.ndarray:
+    """``coords`` [R, L, 3] on the components of ``model`` -> float64 [R, K]: every structure is superposed ONCE onto the model's mean
+    structure (rounded to float32), then proj[s, k] = sum_c (y_sc - mean_c) v_kc with y in float64."""
+    x = _dev(coords)
+    mean = torch.as_tensor(np.asarray(model.mean, dtype=np.float64), device=x.device).contiguous()
+    comps = torch.as_tensor(np.asarray(model.components, dtype=np.float64), device=x.device).contiguous()
+    xform = ops.ca_superpose(x, mean.to(torch.float32), residue_weights)[1]
+    return ops.ca_project(x, mean, comps, xform).cpu().numpy()
+
+
+def js_of_columns(values, ref_key="target", n_bins=50, weights=None):
+    """{k: float64 [R_k, K], K numbers per structure} -> {k: the mean over the K columns of the JS distance from the reference's}:
+    per column histograms of ``n_bins`` bins over the reference's range with per-structure ``weights`` by key and PSEUDO_C."""
+    w = _weights(weights, values)
+    lo, hi = values[ref_key].min(axis=0), values[ref_key].max(axis=0)
+    hist = {k: np.stack([np.histogram(v[:, c], bins=n_bins, weights=w[k], range=(lo[c], hi[c]))[0] + PSEUDO_C for c in range(v.shape[1])])
+            for k, v in values.items()}                      # [K, n_bins]
+    return against_reference(hist, ref_key, lambda h, ref: np.mean([_js(a, b) for a, b in zip(h, ref)]))
+
+
+def js_pca(ca_coords_dict, ref_key="target", n_bins=50, n_components=2, weights=None, return_pc=True):
+    """Does each ensemble populate the reference's essential subspace the way the reference does?  PCA (``n_components``, fitted on the
+    reference ensemble -- no time order needed, unlike ``js_tica``) -> every ensemble, the reference included, through ``pca_project`` ->
+    ``n_bins``-bin histograms over the reference's range per component -> mean Jensen-Shannon distance.  ``weights``: per-structure
+    weights by key, as in ``js_pwd``; the reference's also weight its PCA.  -> results (, projections {k: [R_k, n_components]})."""
+    w = _weights(weights, ca_coords_dict)
+    model = pca(ca_coords_dict[ref_key], n_components, sample_weights=w[ref_key] if weights else None)
+    pc = {k: pca_project(v, model) for k, v in ca_coords_dict.items()}
+    results = js_of_columns(pc, ref_key, n_bins, w)
+    return (results, pc) if return_pc else results
+
+
+def dynamics_frame(ca_coords_dict, ref_key="target"):
+    """The common frame of ``rmsip``, ``dccm_mae`` and ``total_variance``: every ensemble (R >= 2), the reference included, is superposed
+    once on the reference ensemble's mean structure (``ensemble_covariance``'s mean, rounded to float32) and its covariance is taken about
+    its own mean under those transforms -> {k: device float64 [3L, 3L]}."""
+    ref = _at_least_two("dynamics_frame", _dev(ca_coords_dict[ref_key]))
+    target = ops.ca_aligned_mean(ref, ops.ca_fit_transforms(ref)).to(torch.float32)
+    covs = {}
+    for k, v in ca_coords_dict.items():
+        x = _at_least_two("dynamics_frame", _dev(v))
+        if x.shape[1] != ref.shape[1]:
+            raise ValueError(f"dynamics_frame: {k!r} has {x.shape[1]} residues for the reference's {ref.shape[1]}")
+        covs[k] = _aligned_moments(x, ops.ca_superpose(x, target)[1])[1]
+    return covs
+
+
+def rmsip_of(covs, n_structures, ref_key="target", n_components=10):
+    """``rmsip`` of the covariances {k: [3L, 3L]} of ``dynamics_frame`` and the ensembles' sizes {k: R_k}."""
+    n3 = covs[ref_key].shape[0]
+    out = {}
+    for k, c in covs.items():
+        K = min(int(n_components), n3 - 6, n_structures[ref_key] - 1, n_structures[k] - 1)
+        if K < 1:
+            raise ValueError(f"rmsip: no component to compare for {k!r}: min(n_components, 3L - 6, R_ref - 1, R - 1) = {K}")
+        if k == ref_key:
+            out[k] = 1.0
+            continue
+        u, v = (_top_components(_host(m, np.float64), K)[1] for m in (covs[ref_key], c))
+        out[k] = np.around(float(np.sqrt(np.square(u @ v.T).sum() / K)), decimals=4)
+    return out
+
+
+def rmsip(ca_coords_dict, ref_key="target", n_components=10):
+    """Does each ensemble span the reference's essential subspace?  The root mean square inner product (Amadei et al. 1999) of the top K
+    components u_i of the reference ensemble and v_j of each ensemble in ``dynamics_frame``'s common frame: sqrt((1 / K) sum_{i,j <= K}
+    (u_i . v_j)^2), 1 for equal subspaces, K = min(n_components, 3L - 6, R_ref - 1, R_k - 1) (ValueError if K < 1).  The reference's is 1.0."""
+    return rmsip_of(dynamics_frame(ca_coords_dict, ref_key), {k: len(_dev(v)) for k, v in ca_coords_dict.items()}, ref_key, n_components)
+
+
+def dccm_mae_of(dccms, ref_key="target"):
+    """``dccm_mae`` of cross-correlation maps {k: [L, L]} one already has."""
+    return against_reference({k: m[np.triu_indices(len(m), k=1)] for k, m in dccms.items()}, ref_key)
+
+
+def dccm_mae(ca_coords_dict, ref_key="target"):
+    """Do the same residues move together?  The mean |c - c_ref| over the pairs i < j of each ensemble's cross-correlation map from the
+    reference ensemble's, both in ``dynamics_frame``'s common frame (0.0 for a single residue)."""
+    return dccm_mae_of({k: _dccm(c).cpu().numpy() for k, c in dynamics_frame(ca_coords_dict, ref_key).items()}, ref_key)
+
+
+def total_variance_of(covs):
+    """``total_variance`` of the covariances of ``dynamics_frame``."""
+    return {k: np.around(float(c.diagonal().sum()), decimals=4) for k, c in covs.items()}
+
+
+def total_variance(ca_coords_dict, ref_key="target"):
+    """How much does each ensemble move?  tr C in A^2 (the sum over the residues of the squared RMSF) in ``dynamics_frame``'s common frame."""
+    return total_variance_of(dynamics_frame(ca_coords_dict, ref_key))
 
 
 # ---- clustering at a cutoff (csrc/ensemble_cluster.hip) ----------------------------------------------------------------------------

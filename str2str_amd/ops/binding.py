@@ -60,6 +60,9 @@ _SIGNATURES = {
     "s2s_secondary_structure": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "s2s_backbone_sasa": [_vp, _i, _i, _vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _vp],
     "s2s_ca_scattering": [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp],
+    "s2s_ca_aligned_mean": [_vp, _i, _i, _vp, _vp, _vp, _vp],
+    "s2s_ca_covariance": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _ll, _vp],
+    "s2s_ca_project": [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp],
     "s2s_cluster_adjacency": [_vp, _i, _i, _i, _d, _i, _vp, _vp, _vp],
     "s2s_cluster_gromos": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "s2s_format_pdb_models": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _ll],

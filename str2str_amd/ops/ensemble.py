@@ -1,6 +1,7 @@
 """Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition, lDDT, clustering,
 backbone violations, secondary structure and torsions, contact maps and the fraction of native contacts, solvent accessibility, solution
-scattering (Debye intensity, Kirkwood hydrodynamic radius)."""
+scattering (Debye intensity, Kirkwood hydrodynamic radius), essential dynamics (mean structure, covariance and projections of the superposed
+CA coordinates)."""
 import math
 from typing import Optional
 
@@ -27,6 +28,8 @@ SAXS_MAX_TYPES = 64               # S2S_SAXS_MAX_TYPES: rows of the form-factor 
 SAXS_MAX_STRUCTURES = 1 << 20     # structures per s2s_ca_scattering launch, unless max_structures says less
 CONTACT_MAX_RES = 1024            # S2S_CONTACT_MAX_RES: the chain length whose tile of structures fits the LDS of s2s_ca_native_q
 CONTACT_LAUNCH_STRUCTURES = 65535  # S2S_CONTACT_MAX_STRUCTURES: structures per launch of the contact kernels
+PCA_MAX_RES = 1024                # S2S_PCA_MAX_RES: the chain length whose centred coordinates fit the LDS of s2s_ca_project as float64
+PCA_WORKSPACE_BYTES = 256 << 20   # budget of the centred coordinates of one chunk of s2s_ca_covariance, unless max_structures says less
 CLUSTER_MAX_N = 65536             # S2S_CLUSTER_MAX_N: structures per clustering (512 MB of neighbour bits)
 CLUSTER_ROUNDS_PER_SYNC = 32      # rounds of the greedy loop enqueued between two readbacks of its state
 
@@ -216,6 +219,98 @@ def apply_xform(points: torch.Tensor, xform: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(points)
     _check(lib.s2s_apply_xform(_p(points), _p(xform), points.shape[0], points.shape[1], _p(out), _stream()), "s2s_apply_xform")
     return out
+
+
+def _pca_inputs(fn: str, ca, xform, sample_weights):
+    """``ca`` [R, L, 3] with the optional ``xform`` [R, 12] and ``sample_weights`` [R] (a tensor on any device, array or list; >= 0 with a
+    positive finite sum) of ``fn``, checked but for the device -> (R, L, the weights as a host float64 tensor normalised to sum 1, or None)."""
+    R, L = _ca_ensemble(fn, ca, PCA_MAX_RES)
+    if xform is not None and (not isinstance(xform, torch.Tensor) or xform.shape != (R, 12)):
+        raise HipLibraryError(f"{fn}: xform {tuple(getattr(xform, 'shape', ()))} for {R} structures, expected [{R}, 12]")
+    if sample_weights is None:
+        return R, L, None
+    p = torch.as_tensor(sample_weights).detach().to("cpu", torch.float64).contiguous()
+    if p.shape != (R,):
+        raise HipLibraryError(f"{fn}: sample_weights {tuple(p.shape)} for {R} structures")
+    total = float(p.sum())
+    if not (bool((p >= 0.0).all()) and 0.0 < total < float("inf")):
+        raise HipLibraryError(f"{fn}: sample_weights must be >= 0 with a positive finite sum")
+    return R, L, p / total
+
+
+def _pca_on_device(ca, xform, p):
+    _req(ca, name="ca")
+    if xform is not None:
+        _req(xform, torch.float64, "xform")
+    return None if p is None else p.to(ca.device)
+
+
+def ca_aligned_mean(ca: torch.Tensor, xform: Optional[torch.Tensor] = None, sample_weights=None) -> torch.Tensor:
+    """The mean structure of ca [R, L, 3] (fp32 device tensor) after the transforms ``xform`` [R, 12] fp64 (``ca_superpose``'s; None: the
+    identity) -> [L, 3] fp64: sum_s p_s (R_s x_s + t_s) in float64, p = ``sample_weights`` [R] normalised to sum 1 (None: 1 / R).  The order
+    of the sum depends on R alone."""
+    R, L, p = _pca_inputs("ca_aligned_mean", ca, xform, sample_weights)
+    p = _pca_on_device(ca, xform, p)
+    mean = torch.empty(L, 3, dtype=torch.float64, device=ca.device)
+    _check(load_library().s2s_ca_aligned_mean(_p(ca), R, L, _p(xform), _p(p), _p(mean), _stream()), "s2s_ca_aligned_mean")
+    return mean
+
+
+def ca_covariance(ca: torch.Tensor, mean: torch.Tensor, xform: Optional[torch.Tensor] = None, sample_weights=None,
+                  max_structures: Optional[int] = None) -> torch.Tensor:
+    """The covariance of the transformed coordinates of ca [R, L, 3] about ``mean`` [L, 3] fp64 -> [3L, 3L] fp64, coordinate 3 i + a:
+    sum_s p_s (y_s - mean)(y_s - mean)^T (population form), exactly symmetric.  ``max_structures`` bounds the structures (rounded up to a
+    multiple of 4) whose centred coordinates the workspace holds at a time; the result is bit for bit the same for any value."""
+    fn = "ca_covariance"
+    R, L, p = _pca_inputs(fn, ca, xform, sample_weights)
+    chunk = -(-_launch_structures(fn, max_structures, max(4, PCA_WORKSPACE_BYTES // (8 * 48 * -(-3 * L // 48)))) // 4) * 4
+    if not isinstance(mean, torch.Tensor) or mean.shape != (L, 3):
+        raise HipLibraryError(f"{fn}: mean {tuple(getattr(mean, 'shape', ()))} for {L} residues, expected [{L}, 3]")
+    p = _pca_on_device(ca, xform, p)
+    _req(mean, torch.float64, "mean")
+    cov = torch.empty(3 * L, 3 * L, dtype=torch.float64, device=ca.device)
+    ws = torch.empty(-(-3 * L // 48) * 48 * min(chunk, -(-R // 4) * 4), dtype=torch.float64, device=ca.device)   # S2S_PCA_WORKSPACE_DOUBLES
+    _check(load_library().s2s_ca_covariance(_p(ca), R, L, _p(xform), _p(p), _p(mean), _p(cov), _p(ws), ws.numel(), _stream()), "s2s_ca_covariance")
+    return cov
+
+
+def ca_project(ca: torch.Tensor, mean: torch.Tensor, components: torch.Tensor, xform: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ca [R, L, 3] after ``xform`` onto ``components`` [K, 3L] fp64 about ``mean`` [L, 3] fp64 -> [R, K] fp64: sum_c (y_sc - mean_c) v_kc.
+    The order of a sum depends on L alone."""
+    fn = "ca_project"
+    R, L, _ = _pca_inputs(fn, ca, xform, None)
+    if not (isinstance(mean, torch.Tensor) and isinstance(components, torch.Tensor)) or mean.shape != (L, 3) or components.ndim != 2 \
+            or components.shape[0] < 1 or components.shape[1] != 3 * L:
+        raise HipLibraryError(f"{fn}: mean {tuple(getattr(mean, 'shape', ()))} and components {tuple(getattr(components, 'shape', ()))}, "
+                              f"expected [{L}, 3] and [K, {3 * L}]")
+    _pca_on_device(ca, xform, None)
+    _req(mean, torch.float64, "mean"); _req(components, torch.float64, "components")
+    K = components.shape[0]
+    proj = torch.empty(R, K, dtype=torch.float64, device=ca.device)
+    _check(load_library().s2s_ca_project(_p(ca), R, L, _p(xform), _p(mean), _p(components), K, _p(proj), _stream()), "s2s_ca_project")
+    return proj
+
+
+def ca_fit_transforms(ca: torch.Tensor, target: Optional[torch.Tensor] = None, sample_weights=None, residue_weights=None,
+                      n_fit_rounds: int = 5, fit: bool = True) -> Optional[torch.Tensor]:
+    """The transforms of an essential-dynamics fit of ca [R, L, 3] -> xform [R, 12] fp64 (None with ``fit=False``: the identity).
+    ``ca_superpose`` onto ``target`` [L, 3] fp32 (None: ``ca[0]``), ``n_fit_rounds`` times; after each round but the last the target becomes
+    the ``sample_weights``-weighted mean of the transformed structures, formed in float64 and rounded to float32 (the superposition takes a
+    float32 target).  A fixed count: no data-dependent stop.  ``residue_weights`` [L] go to the superposition only."""
+    fn = "ca_fit_transforms"
+    _pca_inputs(fn, ca, None, sample_weights)
+    if not fit:
+        return None
+    rounds = _integer(fn, "n_fit_rounds", n_fit_rounds)
+    if target is not None:
+        _mobile_target(fn, ca, target, "coordinates ca", on_device=False)
+    _req(ca, name="ca")
+    target = ca[0] if target is None else _req(target, name="target")
+    for k in range(rounds):
+        xform = ca_superpose(ca, target, residue_weights)[1]
+        if k + 1 < rounds:
+            target = ca_aligned_mean(ca, xform, sample_weights).to(torch.float32)
+    return xform
 
 
 def _tm_d0(d0) -> float:
