@@ -137,6 +137,35 @@ int s2s_edge_embed_f16x3(const float* node_a, const float* node_b, const float* 
                          int n_rel, int n_bins, float ln_eps, int out_tiled, const float* proj_bias_cat64,
                          float* proj_attn_bias, float* proj_pair_z, int* range_words, void* stream);
 
+/* The edge embedding by CLASS, for chunks that share one timestep (replicas of a target: every sampler call).  node_a[b,i] is then
+ * one row per value of fixed_mask[b,i] and node_b[b,j] likewise, so with a 0/1 fixed mask a pair's first-layer sum -- and z,
+ * attn_bias and pair_z before the edge mask -- depends only on its class (fa, fb, d, bin): fa / fb the class of the fixed mask at
+ * i / j, d the row of rel_table (idx_i - idx_j + rel_offset, clamped), bin the distogram bin or -1 for none.  Two launches:
+ *
+ * s2s_edge_embed_classes_f16x3 runs the kernel body of s2s_edge_embed_f16x3 (same slots, split, LayerNorm, projection) once per row
+ *   r = ((fa * 2 + fb) * n_rel + d) * (n_bins + 1) + (bin + 1)
+ * of the table: (n_fixed == 2 ? 4 : 1) * n_rel * (n_bins + 1) records, row-major, of 168 floats z[128] | attn_bias[8] | pair_z[32]
+ * with the fused projection (proj_bias_cat64 != NULL; weight_stream then has its 5th stage), else of 128 floats (z).
+ *   node_a2 [n_fixed,128], node_b2 column-blocked [32][n_fixed][4]: the operands s2s_embed_assemble gives for a pseudo-sample of
+ *   n_fixed residues whose fixed mask runs over the values present (the same expression as for the chunk: the same floats);
+ *   rel_table / bin_table column-blocked as above.  The first-layer sum keeps the association ((a + b) + r) + kb * k, the edge mask
+ *   is 1.  The range report covers every row of the table -- a superset of the rows in use, so the guard can only fire earlier.
+ *
+ * s2s_edge_embed_expand computes every pair's class with the edge embedding's own device functions (csrc/edge_embed_class.h) and
+ * writes out = z[row] * (m_i m_j) (row-major or tiled, as above), attn_bias [B,8,N,N] and pair_z [B,N,N,32] (both optional, together)
+ * = the row's, or proj_bias_cat64 where m_i m_j = 0.  fixed_cls [B,N] int32: index of fixed_mask[b,i] among the n_fixed values.
+ * Bit for bit s2s_edge_embed_f16x3's outputs where the edge mask is non-zero (and equal as numbers where it is zero) under the
+ * ELIGIBILITY rules, which are the caller's: one timestep row for the whole chunk, fixed mask exactly 0/1, node mask exactly 0/1
+ * (or NULL).  It pays when the table is small against B*N*N (EmbeddingModule.embed).  Launch split and S2S_EE_MAX_PAIRS as above. */
+int s2s_edge_embed_classes_f16x3(const float* node_a2, const float* node_b2, const float* rel_table, const float* bin_table,
+                                 const void* weight_stream, const float* b2, const float* b3, const float* ln_gamma,
+                                 const float* ln_beta, float* table, int n_fixed, int n_rel, int n_bins, float ln_eps,
+                                 const float* proj_bias_cat64, int* range_words, void* stream);
+int s2s_edge_embed_expand(const float* table, const int* fixed_cls, const float* bin_lower, const long long* residue_idx,
+                          const float* ca_xyz, const float* mask, const float* proj_bias_cat64, float* out, int out_tiled,
+                          float* proj_attn_bias, float* proj_pair_z, int n_samples, int n_res, int rel_offset, int n_rel,
+                          int n_bins, void* stream);
+
 /* linear_b and down_z of InvariantPointAttention (src/models/net/ipa.py:177, :253) in one pass over z.
  *   w_packed: [linear_b.weight (8 rows); down_z.weight (32 rows); 24 zero rows] (64x128) packed
  *   bias_cat64 [64]; attn_bias [B,8,N,N] (head-major: what s2s_ipa_attention streams per head); pair_z [B,N,N,32]. */

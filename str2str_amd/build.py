@@ -52,6 +52,8 @@ UNITS = {
     # (the same source as two more translation units, compiled side by side: short-chain edge transition; edge embedding)
     "pair_mlp_f16_b.hip": ["-mllvm", "-pragma-unroll-threshold=10000000", "-fno-slp-vectorize"],
     "pair_mlp_f16_c.hip": ["-mllvm", "-pragma-unroll-threshold=10000000", "-fno-slp-vectorize"],
+    "pair_mlp_f16_d.hip": ["-mllvm", "-pragma-unroll-threshold=10000000", "-fno-slp-vectorize"],   # (the edge embedding on its class table)
+    "pair_embed_expand.hip": [],   # class table -> pair tensors (copies; the class rule is edge_embed_class.h's, explicit in its roundings)
     "ipa_attention.hip": ["-mllvm", "-pragma-unroll-threshold=10000000"],
     "ipa_attention_f16w.hip": ["-mllvm", "-pragma-unroll-threshold=10000000", "-fno-slp-vectorize"],   # (as above; -0.5 .. -1.5 % per IPA block)
     "node_gemm.hip": ["-mllvm", "-pragma-unroll-threshold=10000000", "-fno-slp-vectorize"],   # (as above: node layers -2.4 %)

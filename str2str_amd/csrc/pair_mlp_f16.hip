@@ -50,13 +50,15 @@
 
 #include <cstdlib>
 
+#include "edge_embed_class.h"
 #include "f16x3.h"
 #include "range_flag.h"
 #include "str2str_hip.h"
 
 // Three translation units from this one source (the four edge-transition instantiations + the two of the edge embedding took 7.5 minutes
 // of a forced build as one unit): S2S_PM_PART 1 (this file compiled directly) = the edge transition for chains of 32+ residues and the
-// public entry point, 2 (pair_mlp_f16_b.hip) = its per-lane-seed form for shorter chains, 3 (pair_mlp_f16_c.hip) = the edge embedding.
+// public entry point, 2 (pair_mlp_f16_b.hip) = its per-lane-seed form for shorter chains, 3 (pair_mlp_f16_c.hip) = the edge embedding,
+// 4 (pair_mlp_f16_d.hip) = the edge embedding's class-table form.
 #ifndef S2S_PM_PART
 #define S2S_PM_PART 1
 #endif
@@ -670,7 +672,13 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
 // rows (+ ReLU); the two 128 x 128 layers, LayerNorm and (PROJ) the first IPA block's linear_b / down_z run as f16x3 slots
 // exactly like the edge transition above: 5 weight stages of 32 KiB (W2 | W3 | [linear_b; down_z]), 40 slots of 6 MFMAs per
 // 32-pair tile, persistent workgroups; the NEXT tile's rows are gathered and split under the current tile's MFMAs.
-template <bool PROJ>
+// TABLE (s2s_edge_embed_classes_f16x3): the same body on the rows of the CLASS TABLE instead of on pairs.  "Pair" r is the class
+//   r = ((fa 2 + fb) n_rel + d) (n_bins + 1) + (bin + 1)   (s2s::ee_class_row)
+// and gathers node_a[fa], node_b[fb] (N = the number of rows of these two operands), rel_tab[d], bin_tab[bin] (kb = 0 for bin = -1):
+// no CA, residue index or mask is read, the edge mask is 1, and a row's outputs go to one contiguous record of `out`
+// (z[128] | attn_bias[8] | pair_z[32] with PROJ, z alone without).  Only the per-pair setup and the output addresses differ: the
+// weight pipe, the slots, the split, LayerNorm, the projection and the range tracking are the statements below, shared.
+template <bool PROJ, bool TABLE = false>
 __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
     const float* __restrict__ node_a, const float* __restrict__ node_b, const float* __restrict__ rel_tab,
     const float* __restrict__ bin_tab, const float* __restrict__ bin_lower, const long long* __restrict__ residue_idx,
@@ -682,7 +690,7 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
     constexpr int kSlots = 8 * kStages;
     __shared__ __attribute__((aligned(16))) char s_w[2][kStageBytes];
     __shared__ __attribute__((aligned(16))) float s_vec[512 + 64];  // b2 | b3 | gamma | beta | projection bias
-    __shared__ __attribute__((aligned(16))) float s_bins[64 + 4];    // distogram bin lower edges (ascending), padded with 3e38
+    __shared__ __attribute__((aligned(16))) float s_bins[s2s::kEeBinSlots];    // distogram bin lower edges (ascending), padded with 3e38
     const int lane = threadIdx.x & 63, h = lane >> 5, wave = threadIdx.x >> 6;
 
     // ---- weight pipe (identical to the edge transition's)
@@ -729,7 +737,7 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
         bool valid;
     };
     const long long NN = (long long)N * N;
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)node_b, 0, (unsigned)(M / N * 512), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)node_b, 0, (unsigned)((TABLE ? (long long)N : M / N) * 512), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc((void*)rel_tab, 0, n_rel * 512, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc((void*)bin_tab, 0, n_bins * 512, 0x00020000);
     // setup in two halves so that the per-pair loads (CA coordinates, residue indices, masks) are in flight for a few slots
@@ -758,6 +766,14 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
         r.valid = p < M;
         p = r.valid ? p : M - 1;
         r.p = p;
+        if constexpr (TABLE) {   // class row p -> (fa, fb, d, bin + 1), carried in the fields of the row / column node, the two indices
+            const unsigned nb1 = (unsigned)n_bins + 1u, q = (unsigned)p / nb1, cls = q / (unsigned)n_rel;
+            r.bi = cls >> 1; r.bj = cls & 1u; r.bb = 0;
+            r.ii = q - cls * (unsigned)n_rel; r.ij = (unsigned)p - q * nb1;
+            r.ax = r.ay = r.az = r.bx = r.by = r.bz = 0.f;
+            r.mi = r.mj = 1.f;
+            return r;
+        }
         // p = (bb N + i) N + j:  global row bi = p / N,  j = p - bi N,  bb = bi / N
         unsigned bi, j, bb, i;
         div_n((unsigned)p, bi, j);
@@ -774,22 +790,9 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
     auto setup_b = [&](const Raw& r) -> Ctx {
         Ctx c;
         c.valid = r.valid;
-        // distogram bin of this pair (no FMA contraction: mirrors torch.linalg.norm of the difference; geo_utils.py:44-56)
-        const float dx = r.ax - r.bx, dy = r.ay - r.by, dz = r.az - r.bz;
-        const float dist = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-        // the reference's one-hot (dist > lower[k]) * (dist < upper[k]), upper = lower[k+1] (1e8 for the last): with ascending
-        // edges (torch.linspace) that is k = #{edges < dist} - 1 unless dist sits exactly on the next edge (then no bin at all)
-        int cnt = 0;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {  // s_bins: n_bins <= 32 edges | 1e8 (the last bin's upper edge) | 3e38 ...
-            const float4 e = *reinterpret_cast<const float4*>(&s_bins[4 * u]);
-            cnt += (e.x < dist) + (e.y < dist) + (e.z < dist) + (e.w < dist);
-        }
-        cnt = cnt > n_bins ? n_bins : cnt;                  // dist beyond 1e8 when n_bins < 32: no bin, as below
-        const float up = s_bins[cnt];                       // upper edge of bin cnt - 1
-        const int bin = (cnt >= 1 && dist < up) ? cnt - 1 : -1;
-        long long d = r.ii - r.ij + rel_off;
-        d = d < 0 ? 0 : (d >= n_rel ? n_rel - 1 : d);
+        // distogram bin and relative-position row of this pair (edge_embed_class.h); TABLE: the class row names them
+        const int bin = TABLE ? (int)r.ij - 1 : s2s::ee_pair_bin(s_bins, n_bins, r.ax, r.ay, r.az, r.bx, r.by, r.bz);
+        const long long d = TABLE ? r.ii : s2s::ee_rel_row(r.ii, r.ij, rel_off, n_rel);
         c.ra = node_a + r.bi * 128;
         const unsigned jj = (unsigned)(r.bj - r.bb * N);
         c.vb = ((unsigned)r.bb * 32u * (unsigned)N + (unsigned)h * (unsigned)N + jj) * 16u;
@@ -798,7 +801,7 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
         c.kb = bin < 0 ? 0.f : 1.f;
         c.p = r.p;
         c.boff = r.p + 7 * r.bb * NN;
-        c.em = mask ? r.mi * r.mj : 1.0f;
+        c.em = (!TABLE && mask) ? r.mi * r.mj : 1.0f;
         return c;
     };
     float amax = 0.f;   // range guard (range_flag.h)
@@ -841,7 +844,7 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
 
     const long long n_wt = (M + 127) / 128;
     long long wt = blockIdx.x;
-    if (threadIdx.x < 68) s_bins[threadIdx.x] = (int)threadIdx.x < n_bins ? bin_lower[threadIdx.x] : ((int)threadIdx.x == n_bins ? 1e8f : 3.0e38f);
+    if constexpr (!TABLE) s2s::ee_fill_bins(s_bins, bin_lower, n_bins);
     __syncthreads();
     Ctx cur = setup_b(setup_a(wt));
     f16x8 xp[8][2];  // planes of the current layer's input (8 k-steps of 16)
@@ -890,7 +893,9 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
     };
     float ln_mean = 0.f, ln_rstd = 0.f;
     // output block of the wave (16 KiB): row-major  n 512 + g 32 + h 16,  tiled  g 1024 + lane 16  (edge transition, "Pair-tensor layouts")
-    const unsigned out_lane = out_tiled ? lane * 16u : (unsigned)((lane & 31) * 512 + h * 16), out_step = out_tiled ? 1024u : 32u;
+    // (TABLE: row-major records of kRec floats)
+    constexpr unsigned kRec = TABLE ? (PROJ ? s2s::kEeRecProj : s2s::kEeRecPlain) : 128u;
+    const unsigned out_lane = out_tiled ? lane * 16u : (unsigned)((lane & 31) * (kRec * 4) + h * 16), out_step = out_tiled ? 1024u : 32u;
     f16x8 xq[2][2];  // LayerNorm output planes of the projection's current / next k-step
     // LayerNorm output of k-step k (16 channels): scale, shift, edge mask, store (+ planes for the projection)
     __amdgpu_buffer_rsrc_t rs_out;  // this tile's 32 output rows; rows past M are outside num_records: their stores are dropped
@@ -898,8 +903,8 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
         const long long p0 = (wg_tile * 4 + __builtin_amdgcn_readfirstlane(wave)) * 32;
         const long long left = M - p0;
         // (tiled layout: the pairs of a partial last tile are interleaved with its padding, which the buffer holds: whole block)
-        rs_out = __builtin_amdgcn_make_buffer_rsrc((void*)(out + (p0 < M ? p0 : 0) * 128), 0,
-                                                   (unsigned)(left <= 0 ? 0 : (left < 32 && !out_tiled ? left : 32)) * 512u, 0x00020000);
+        rs_out = __builtin_amdgcn_make_buffer_rsrc((void*)(out + (p0 < M ? p0 : 0) * kRec), 0,
+                                                   (unsigned)(left <= 0 ? 0 : (left < 32 && !out_tiled ? left : 32)) * (kRec * 4u), 0x00020000);
     };
     float4 lga[2], lbe[2];  // gamma / beta of the next LayerNorm piece, read at the top of its slot
     auto ln_load = [&](auto kc) {
@@ -1058,16 +1063,19 @@ __global__ void __launch_bounds__(256) edge_embed_f16_kernel(
     if constexpr (PROJ) {
         if (cur.valid) {
             const float4 b0 = ldg4(s_vec + 512, 0, h);
-            float* o = proj_bias_out + cur.boff + 4 * h * NN;
+            // (TABLE: both projections follow z in the class row's record)
+            float* o = TABLE ? out + cur.p * kRec + 128 + 4 * h : proj_bias_out + cur.boff + 4 * h * NN;
+            const long long hs = TABLE ? 1 : NN;
+            float* pz = TABLE ? out + cur.p * kRec + 136 : proj_pz_out + cur.p * 32;
             o[0] = __builtin_fmaf(pq[0][0], kInvWS, b0.x);
-            o[NN] = __builtin_fmaf(pq[0][1], kInvWS, b0.y);
-            o[2 * NN] = __builtin_fmaf(pq[0][2], kInvWS, b0.z);
-            o[3 * NN] = __builtin_fmaf(pq[0][3], kInvWS, b0.w);
+            o[hs] = __builtin_fmaf(pq[0][1], kInvWS, b0.y);
+            o[2 * hs] = __builtin_fmaf(pq[0][2], kInvWS, b0.z);
+            o[3 * hs] = __builtin_fmaf(pq[0][3], kInvWS, b0.w);
 #pragma unroll
             for (int g = 1; g <= 4; ++g) {
                 const int t = g >> 2, rq = g & 3;
                 const float4 bq = ldg4(s_vec + 512, g, h);
-                *reinterpret_cast<float4*>(proj_pz_out + cur.p * 32 + 8 * (g - 1) + 4 * h) =
+                *reinterpret_cast<float4*>(pz + 8 * (g - 1) + 4 * h) =
                     make_float4(__builtin_fmaf(pq[t][4 * rq + 0], kInvWS, bq.x), __builtin_fmaf(pq[t][4 * rq + 1], kInvWS, bq.y),
                                 __builtin_fmaf(pq[t][4 * rq + 2], kInvWS, bq.z), __builtin_fmaf(pq[t][4 * rq + 3], kInvWS, bq.w));
             }
@@ -1212,3 +1220,28 @@ extern "C" int s2s_edge_embed_f16x3(const float* node_a, const float* node_b, co
     return (int)hipGetLastError();
 }
 #endif   // S2S_PM_PART == 3
+
+#if S2S_PM_PART == 4
+extern "C" int s2s_edge_embed_classes_f16x3(const float* node_a2, const float* node_b2, const float* rel_table, const float* bin_table,
+                                             const void* weight_stream, const float* b2, const float* b3, const float* ln_gamma,
+                                             const float* ln_beta, float* table, int n_fixed, int n_rel, int n_bins, float ln_eps,
+                                             const float* proj_bias_cat64, int* range_words, void* stream) {
+    if (n_fixed < 1 || n_fixed > 2 || n_rel < 1 || n_bins < 1 || n_bins > 32) return (int)hipErrorInvalidValue;
+    const long long M = (long long)(n_fixed == 2 ? 4 : 1) * n_rel * (n_bins + 1);   // class rows: every (fa, fb) of the fixed classes present
+    if (M * s2s::kEeRecProj * 4 >= (1ll << 32) || (long long)n_rel * 512 >= (1ll << 32)) return (int)hipErrorInvalidValue;   // 32-bit offsets
+    const long long wg_tiles = (M + 127) / 128;
+    const int n_cu = cu_count();
+    const long long grid = wg_tiles < n_cu ? wg_tiles : n_cu;
+    if (proj_bias_cat64)
+        hipLaunchKernelGGL((edge_embed_f16_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, node_a2, node_b2,
+                           rel_table, bin_table, (const float*)nullptr, (const long long*)nullptr, (const float*)nullptr,
+                           (const char*)weight_stream, b2, b3, ln_gamma, ln_beta, (const float*)nullptr, table, M, n_fixed, 0, n_rel, n_bins,
+                           ln_eps, 0, proj_bias_cat64, (float*)nullptr, (float*)nullptr, range_words);
+    else
+        hipLaunchKernelGGL((edge_embed_f16_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, node_a2, node_b2,
+                           rel_table, bin_table, (const float*)nullptr, (const long long*)nullptr, (const float*)nullptr,
+                           (const char*)weight_stream, b2, b3, ln_gamma, ln_beta, (const float*)nullptr, table, M, n_fixed, 0, n_rel, n_bins,
+                           ln_eps, 0, (const float*)nullptr, (float*)nullptr, (float*)nullptr, range_words);
+    return (int)hipGetLastError();
+}
+#endif   // S2S_PM_PART == 4

@@ -10,6 +10,7 @@ distogram-bin table) gathered inside ``s2s_edge_embed`` (csrc/pair_mlp.hip), whi
 from __future__ import annotations
 
 import math
+import os
 from functools import partial
 from typing import Optional
 
@@ -45,6 +46,7 @@ def get_timestep_embedding(timesteps: torch.Tensor, embedding_dim: int, max_len:
 
 class EmbeddingModule(nn.Module):
     launch_switches = ("arith", "node_arith")   # attributes set below that select launches: part of sampler._graph_key
+    launch_modes = ("ee_classes",)              # ... and the string-valued ones (S2S_EE_CLASSES), part of the key in the same way
 
     def __init__(self, init_embed_size: int, node_embed_size: int, edge_embed_size: int, num_bins: int = 22,
                  min_bin: float = 1e-5, max_bin: float = 20.0, self_conditioning: bool = True):
@@ -69,6 +71,11 @@ class EmbeddingModule(nn.Module):
         self._wcache, self._w16cache, self._proj_cache, self._idx_cache, self._fixed_cache = (DerivedCache() for _ in range(5))
         self.arith = default_arith()   # edge embedding kernels: "f16x3" (split-f16 MFMA, default) | "f32" (exact fp32 MFMA), str2str_amd/arith.py
         self.node_arith = default_arith()   # the node MLP (node-stream family: follows the trunk)
+        # the edge embedding by class (ops.edge_embed_classes_f16x3): "auto" where it is legal and pays, "1" wherever it is legal, "0" never
+        self.ee_classes = os.environ.get("S2S_EE_CLASSES", "auto")
+        if self.ee_classes not in ("auto", "0", "1"):
+            raise ValueError(f"S2S_EE_CLASSES={self.ee_classes!r}: expected auto, 0 or 1")
+        self._mask01_cache = DerivedCache()
 
     # ---- derived tensors
     def _weights(self):
@@ -113,15 +120,34 @@ class EmbeddingModule(nn.Module):
 
     def _fixed_terms(self, fixed_mask: torch.Tensor, w: dict, dev, node_pos: torch.Tensor):
         """Per-target constants of the first layers that do not depend on t: (node MLP: fixed-mask column + positional image [B,L,256],
-        edge row term [B,L,128], (edge column term in the f16x3 kernel's gather layout [B,32,L,4], the same row-major)).  Cached on
-        the mask tensor, the positional image and the weights."""
+        edge row term [B,L,128], (edge column term in the f16x3 kernel's gather layout [B,32,L,4], the same row-major), class terms).
+        Cached on the mask tensor, the positional image and the weights.
+        Class terms (the edge embedding by class, ops.edge_embed_classes_f16x3): None unless the mask is exactly 0/1 -- one host read
+        per target, here -- else {n_fixed: how many of the two values occur, fixed_cls [B,L] int32: each residue's index among them,
+        fa2 / fb2 / nc2: the edge row / column terms and a zero node term of a pseudo-sample of n_fixed residues whose mask runs over
+        those values (the same products as above, so ``embed_assemble`` gives the same floats as for the chunk's residues)}."""
         def build():
             fixed = fixed_mask.to(dev)[..., None].float()
             B, L = fixed.shape[:2]
+            vals = torch.unique(fixed).cpu().tolist()
+            cls = None
+            if vals and all(v in (0.0, 1.0) for v in vals):
+                f2 = torch.tensor(vals, device=dev, dtype=torch.float32).view(1, -1, 1)
+                cls = {"n_fixed": len(vals),
+                       "fixed_cls": ((fixed[..., 0] > 0) if len(vals) == 2 else torch.zeros_like(fixed[..., 0])).to(torch.int32).contiguous(),
+                       "fa2": (f2 * w["w_row_f"]).contiguous(),
+                       "fb2": (f2[:, None] * w["w_col_f"].view(1, 32, 1, 4)).expand(1, 32, len(vals), 4).contiguous(),
+                       "nc2": torch.zeros(len(vals), w["wn_f"].shape[0], device=dev)}
             return ((fixed * w["wn_f"] + node_pos).contiguous(), (fixed * w["w_row_f"]).contiguous(),
-                    ((fixed[:, None] * w["w_col_f"].view(1, 32, 1, 4)).expand(B, 32, L, 4).contiguous(), (fixed * w["w_col_f"]).contiguous()))
+                    ((fixed[:, None] * w["w_col_f"].view(1, 32, 1, 4)).expand(B, 32, L, 4).contiguous(), (fixed * w["w_col_f"]).contiguous()), cls)
 
         return self._fixed_cache.get([fixed_mask, w["wn_f"], node_pos], build)
+
+    def _mask_is_01(self, node_mask: Optional[torch.Tensor]) -> bool:
+        """Whether the node mask is exactly 0/1 (or absent): one host read per mask tensor, cached like the per-target terms."""
+        if node_mask is None:
+            return True
+        return self._mask01_cache.get([node_mask], lambda: (bool(((node_mask == 0) | (node_mask == 1)).all()),))[0]
 
     def time_images(self, t_emb: torch.Tensor) -> torch.Tensor:
         """[n, 32] timestep embeddings -> [n, 512] first-layer images + biases [node MLP | edge row | edge column] (one row per
@@ -185,6 +211,7 @@ class EmbeddingModule(nn.Module):
         single_t = t_img is not None or t_emb.shape[0] == 1
         M = B * L
         f16 = self.arith == "f16x3"
+        cls = None
         if single_t:
             # one timestep for the whole chunk (every sampler call): the three [*, 32] first-layer images are one row each -- a 32-term dot
             # product per output channel, evaluated elementwise for all three blocks at once (or handed in as t_img); the fixed-mask and
@@ -195,7 +222,7 @@ class EmbeddingModule(nn.Module):
             #  the kernel adds row sample of it instead of the one shared row: the same sums per element)
             per_sample = t_img is not None and t_img.ndim == 2 and t_img.shape[0] == B and B > 1
             img = (t_img if per_sample else t_img.reshape(-1)) if t_img is not None else (w["w_t_cat"] * t_emb).sum(-1) + w["b_t_cat"]
-            Fn, Fa, Fb = self._fixed_terms(fixed_mask, w, dev, node_pos)
+            Fn, Fa, Fb, cls = self._fixed_terms(fixed_mask, w, dev, node_pos)
             h_act, node_a, node_b = torch.ops.str2str_amd.embed_assemble(img.contiguous(), Fn, Fa, Fb[0] if f16 else Fb[1], B, L,
                                                                          self.node_arith == "f16x3", f16)
         else:
@@ -224,9 +251,22 @@ class EmbeddingModule(nn.Module):
             if next_proj is not None:  # 5-stage stream: W2 | W3 | the first IPA block's projection stage
                 stream = self._proj_cache.get([ws, next_proj["wp_f16x2"]], lambda: torch.cat([ws, next_proj["wp_f16x2"]]))
                 proj = (stream, next_proj["b64"])
-            edge_embed = ops.edge_embed_f16x3(node_a, node_b, rel_cb, w["bin_tab_cb"], w["bin_lower"], idx_dev, ca, ws, e2.bias,
-                                              w["b3c"], ln.weight, ln.bias, mask, span, ln.eps, proj=proj, column_blocked_tables=True,
-                                              out_layout=edge_layout)
+            # one timestep for the chunk and 0/1 masks: a pair's MLP input depends only on its class (fixed_i, fixed_j, d, bin) -- the MLP
+            # once per class row, then a copy per pair, where the table is small against the pairs (ops.edge_embed_classes_eligible)
+            by_class = cls is not None and ops.edge_embed_classes_eligible(
+                self.ee_classes, self.arith, single_t and not per_sample, cls["n_fixed"], self._mask_is_01(node_mask), rel_cb.shape[1],
+                w["bin_tab_cb"].shape[1], B, L)
+            if by_class:
+                # the two operand rows per fixed-mask value, by the launch that made the chunk's: the same sums, the same floats
+                _, node_a2, node_b2 = torch.ops.str2str_amd.embed_assemble(img.contiguous(), cls["nc2"], cls["fa2"], cls["fb2"], 1,
+                                                                           cls["n_fixed"], False, True)
+                edge_embed = ops.edge_embed_classes_f16x3(node_a2, node_b2, cls["fixed_cls"], rel_cb, w["bin_tab_cb"], w["bin_lower"], idx_dev,
+                                                          ca, ws, e2.bias, w["b3c"], ln.weight, ln.bias, mask, span, ln.eps, proj=proj,
+                                                          out_layout=edge_layout)
+            else:
+                edge_embed = ops.edge_embed_f16x3(node_a, node_b, rel_cb, w["bin_tab_cb"], w["bin_lower"], idx_dev, ca, ws, e2.bias,
+                                                  w["b3c"], ln.weight, ln.bias, mask, span, ln.eps, proj=proj, column_blocked_tables=True,
+                                                  out_layout=edge_layout)
         else:
             if edge_layout != "rowmajor":
                 raise ops.HipLibraryError("EmbeddingModule: the tiled pair layout belongs to the f16x3 kernels")

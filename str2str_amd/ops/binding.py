@@ -19,6 +19,8 @@ _SIGNATURES = {
     "s2s_edge_transition_f16x3": [_vp] * 9 + [_i, _i, _f, _i, _vp, _vp, _vp, _i, _vp, _vp],
     "s2s_edge_embed": [_vp] * 15 + [_i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "s2s_edge_embed_f16x3": [_vp] * 14 + [_i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
+    "s2s_edge_embed_classes_f16x3": [_vp] * 10 + [_i, _i, _i, _f, _vp, _vp, _vp],
+    "s2s_edge_embed_expand": [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "s2s_pair_project": [_vp] * 5 + [_i, _i, _vp],
     "s2s_ipa_prep_points": [_vp] * 6 + [_ll, _i, _i, _i, _i, _vp],
     "s2s_ipa_attention": [_vp] * 12 + [_i, _i, _i, _i, _i, _i, _i, _f, _f, _vp],

@@ -147,6 +147,90 @@ def edge_embed_f16x3(node_a, node_b, rel_table, bin_table, bin_lower, residue_id
     return out if proj is None else (out, pbias, ppz)
 
 
+# ---- the edge embedding by class (s2s_edge_embed_classes_f16x3 + s2s_edge_embed_expand; include/str2str_hip.h)
+# R of the eligibility rule  class rows x R <= B N^2.  Per row the table kernel costs what the edge embedding costs per pair, and the
+# two launches cost a few microseconds more than one, so the path can only win where the table is a small fraction of the pairs.
+# Set from the measured crossover with a factor 2 on the old kernel's side: profiles/r07_ee_classes_threshold.md.
+EE_CLASS_R = 12
+
+
+def edge_embed_class_rows(n_fixed: int, n_rel: int, n_bins: int) -> int:
+    """Rows of the class table: every (fa, fb) of the fixed-mask values present x every relative-position row x (no bin | each bin)."""
+    if n_fixed not in (1, 2):
+        raise HipLibraryError(f"edge_embed classes: {n_fixed} fixed-mask values (a 0/1 mask has one or two)")
+    return (4 if n_fixed == 2 else 1) * n_rel * (n_bins + 1)
+
+
+def edge_embed_class_row(fa: int, fb: int, d: int, bin_: int, n_rel: int, n_bins: int) -> int:
+    """Row of class (fa, fb, d, bin), bin = -1 for "none" (csrc/edge_embed_class.h: ee_class_row)."""
+    return ((fa * 2 + fb) * n_rel + d) * (n_bins + 1) + (bin_ + 1)
+
+
+def edge_embed_class_of_row(r: int, n_rel: int, n_bins: int):
+    """Inverse of ``edge_embed_class_row`` (the table kernel's decode) -> (fa, fb, d, bin)."""
+    q, b1 = divmod(r, n_bins + 1)
+    c, d = divmod(q, n_rel)
+    return c >> 1, c & 1, d, b1 - 1
+
+
+def edge_embed_classes_eligible(mode: str, arith: str, one_timestep: bool, n_fixed, mask_is_01: bool, n_rel: int, n_bins: int,
+                                B: int, N: int, R: int = EE_CLASS_R) -> bool:
+    """Whether a call of the edge embedding takes the class path.  ``mode`` = S2S_EE_CLASSES: "0" never, "1" whenever it is legal,
+    "auto" when it is legal and the table is small against the work.  Legal: f16x3 arithmetic, one timestep for the chunk, a fixed
+    mask that is exactly 0/1 (``n_fixed`` = how many of the two values occur, None if it is not) and a node mask that is 0/1 or absent."""
+    if mode not in ("auto", "0", "1"):
+        raise ValueError(f"S2S_EE_CLASSES={mode!r}: expected auto, 0 or 1")
+    if mode == "0" or arith != "f16x3" or not one_timestep or n_fixed not in (1, 2) or not mask_is_01:
+        return False
+    rows = edge_embed_class_rows(n_fixed, n_rel, n_bins)
+    if rows * 168 * 4 >= 2 ** 32:    # the table kernel's 32-bit offsets
+        return False
+    return mode == "1" or rows * R <= B * N * N
+
+
+def edge_embed_classes_f16x3(node_a2, node_b2, fixed_cls, rel_table, bin_table, bin_lower, residue_idx, ca, wstream, b2, b3, gamma, beta,
+                             mask, rel_offset: int, ln_eps=1e-5, out=None, proj=None, out_layout: str = "rowmajor"):
+    """The edge embedding by class: ``edge_embed_f16x3``'s outputs (same return contract, bit for bit where the edge mask is non-zero)
+    for a chunk that shares one timestep and has a 0/1 fixed mask and node mask -- the MLP once per class row, then a copy per pair.
+    ``node_a2`` [n_fixed,128] / ``node_b2`` [32,n_fixed,4]: what ``embed_assemble`` gives for a pseudo-sample whose fixed mask runs over
+    the n_fixed values present; ``fixed_cls`` [B,N] int32: each residue's index among them; tables column-blocked."""
+    lib = load_library()
+    B, N = fixed_cls.shape
+    n_fixed, n_rel, n_bins = node_a2.numel() // 128, rel_table.shape[1], bin_table.shape[1]
+    if node_b2.numel() != n_fixed * 128 or rel_table.shape[0] != 32 or bin_table.shape[0] != 32:
+        raise HipLibraryError("edge_embed_classes_f16x3: operands are not [n_fixed,128] / column-blocked [32, rows, 4]")
+    rows = edge_embed_class_rows(n_fixed, n_rel, n_bins)
+    _req_all(node_a2=node_a2, node_b2=node_b2, rel_table=rel_table, bin_table=bin_table, bin_lower=bin_lower, ca=ca, b2=b2, b3=b3, gamma=gamma,
+             beta=beta)
+    _req(residue_idx, torch.int64, "residue_idx"); _req(fixed_cls, torch.int32, "fixed_cls")
+    if tuple(residue_idx.shape) != (B, N) or ca.numel() != B * N * 3:
+        raise HipLibraryError("edge_embed_classes_f16x3: residue_idx / ca do not match fixed_cls [B, N]")
+    dev = node_a2.device
+    pw, pb, pbias, ppz = _proj_outputs(proj, B, N, dev, torch.int16, "wstream")
+    wstream = _req(wstream, torch.int16, "wstream") if proj is None else pw
+    if wstream.numel() * 2 != (5 if proj is not None else 4) * 32 * 1024:
+        raise HipLibraryError("s2s_edge_embed_classes_f16x3: weight stream has the wrong number of stages")
+    _req_opt(mask=mask)
+    if out_layout not in ("rowmajor", "tiled"):
+        raise HipLibraryError(f"edge_embed_classes_f16x3: out_layout {out_layout!r}")
+    tiled = out_layout == "tiled"
+    if out is None:
+        out = PairTiled(B, N, dev) if tiled else torch.empty(B, N, N, 128, device=dev, dtype=torch.float32)
+    elif isinstance(out, PairTiled) != tiled:
+        raise HipLibraryError("edge_embed_classes_f16x3: out does not have the requested layout")
+    table = torch.empty(rows, 168 if proj is not None else 128, device=dev, dtype=torch.float32)
+
+    def launch():   # both launches under one timer: the family's time is the table plus the expansion
+        rc = lib.s2s_edge_embed_classes_f16x3(_p(node_a2), _p(node_b2), _p(rel_table), _p(bin_table), _p(wstream), _p(b2), _p(b3), _p(gamma),
+                                              _p(beta), _p(table), n_fixed, n_rel, n_bins, ln_eps, _p(pb), _p(range_flag()), _stream())
+        return rc or lib.s2s_edge_embed_expand(_p(table), _p(fixed_cls), _p(bin_lower), _p(residue_idx), _p(ca), _p(mask), _p(pb),
+                                               _p(out.buf if tiled else out), 1 if tiled else 0, _p(pbias), _p(ppz), B, N, int(rel_offset),
+                                               n_rel, n_bins, _stream())
+
+    _check(_timed("s2s_edge_embed", launch), "s2s_edge_embed_classes_f16x3 / s2s_edge_embed_expand")
+    return out if proj is None else (out, pbias, ppz)
+
+
 def pair_project(edge, wp, bias64, attn_bias=None, pair_z=None):
     lib = load_library()
     B, N = edge.shape[0], edge.shape[1]

@@ -7,7 +7,7 @@ from .geometry import forward_marginal, frames_to_backbone, rigid_compose_update
 from .node import (embed_assemble, ipa_projections, node_chain, node_linear, node_linear_f32, node_linear_multi, node_linear_vfrag, pack_planes,
                    row_layernorm)
 from .packing import PairTiled
-from .pair import edge_embed, edge_embed_f16x3, edge_transition, edge_transition_f16x3, pair_project
+from .pair import edge_embed, edge_embed_classes_f16x3, edge_embed_f16x3, edge_transition, edge_transition_f16x3, pair_project
 
 _registered = False   # rebound by register_torch_ops: read it there only
 
@@ -61,6 +61,9 @@ _TORCH_OPS = {
     "edge_embed_f16x3(Tensor node_a, Tensor node_b, Tensor rel_table, Tensor bin_table, Tensor bin_lower, Tensor residue_idx, Tensor ca, "
     "Tensor wstream, Tensor b2, Tensor b3, Tensor gamma, Tensor beta, Tensor? mask, int rel_offset, float ln_eps) -> Tensor":
         lambda *a: edge_embed_f16x3(*a),
+    "edge_embed_classes_f16x3(Tensor node_a2, Tensor node_b2, Tensor fixed_cls, Tensor rel_table, Tensor bin_table, Tensor bin_lower, "
+    "Tensor residue_idx, Tensor ca, Tensor wstream, Tensor b2, Tensor b3, Tensor gamma, Tensor beta, Tensor? mask, int rel_offset, "
+    "float ln_eps) -> Tensor": lambda *a: edge_embed_classes_f16x3(*a),
     "pair_project(Tensor edge, Tensor wp, Tensor bias64) -> (Tensor, Tensor)": lambda *a: pair_project(*a),
     # ---- attention
     "ipa_prep_points(Tensor rigids7, Tensor q_pts_lin, Tensor kv_pts_lin, int n_heads=8, int n_qk=8, int n_v=12) -> (Tensor, Tensor, Tensor)":

@@ -128,7 +128,8 @@ def _graph_key(net, feats, b, N):
         h.update(k.encode()); h.update(str(tuple(v.shape)).encode()); h.update(v.detach().cpu().numpy().tobytes())
     # which kernels were captured: every switch the module classes declare (``launch_switches``: arithmetic, block exponents, folded
     # attention operands, padding semantics, ...), per module in module order -- a mixed network has many forms
-    modes = tuple((type(m).__name__, a, getattr(m, a)) for m in net.modules() for a in getattr(type(m), "launch_switches", ()))
+    modes = tuple((type(m).__name__, a, getattr(m, a)) for m in net.modules()
+                  for a in getattr(type(m), "launch_switches", ()) + getattr(type(m), "launch_modes", ()))
     return (id(net), sum(p._version for p in net.parameters()), b, N, modes, h.hexdigest())
 
 
