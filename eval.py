@@ -23,7 +23,9 @@ ensemble's curve against the measured ``DIR/<target>.dat`` (columns q in 1/Angst
 ``+dynamics=true`` also computes how the sampled and the target ensembles move (on the device: covariance of the superposed CA coordinates;
 the eigenproblem on the host) and writes ``dynamics_<tag>_<mmdd-HH-MM>.csv`` (the JS distance of the projections on the target's first two
 principal components, the RMSIP of the top ten, the mean absolute difference of the cross-correlation maps, the total variance of both)
-and the cross-correlations ``dynamics/<target>.csv``."""
+and the cross-correlations ``dynamics/<target>.csv``.
+``+tica_backend=device`` computes the ``js_tica`` column with the time-lagged covariances and the projections on the device
+(metrics.js_tica(backend="device")); absent, the column is the reference's path.  Column name and file layout do not change."""
 import logging
 import os
 import sys
@@ -107,6 +109,15 @@ def _switch(name, value) -> bool:
     if isinstance(value, str) and value.strip().lower() in ("true", "false", "1", "0", "yes", "no"):
         return value.strip().lower() in ("true", "1", "yes")
     raise ValueError(f"{name} {value!r}: expected true or false")
+
+
+def tica_backend_switch(value) -> str:
+    """``+tica_backend=...`` as js_tica's backend: absent, null and "host" are the reference's path."""
+    if value is None:
+        return "host"
+    if isinstance(value, str) and value.strip().lower() in ("host", "device"):
+        return value.strip().lower()
+    raise ValueError(f"tica_backend {value!r}: expected host or device")
 
 
 def _backbones(what, pred_file, target_file):
@@ -237,7 +248,7 @@ def _write_summary(output_dir, prefix, tag, rows, columns, mean_row):
 
 
 def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None, cluster_cutoff=None,
-                        secondary_structure=None, contacts=None, sasa=None, saxs=None, saxs_data=None, dynamics=None):
+                        secondary_structure=None, contacts=None, sasa=None, saxs=None, saxs_data=None, dynamics=None, tica_backend=None):
     """reference src/eval.py:47-99: one row per target, one column per metric, plus the mean row.  ``extra_metrics``: names out of
     EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's).
     ``cluster_cutoff`` (A; None: nothing of this happens): the ``pred`` ensemble of every target is clustered by ``metrics.cluster_rmsd``;
@@ -250,8 +261,9 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     surface and mean relative accessibility; ``saxs_...csv`` (SAXS_COLUMNS, and ``saxs_chi2`` against ``<saxs_data>/<target>.dat`` when
     the directory ``saxs_data`` is given) and ``saxs/<target>.csv`` the scattering summaries and the curves; ``dynamics_...csv``
     (DYNAMICS_COLUMNS) and ``dynamics/<target>.csv`` the essential-dynamics summaries and the cross-correlations.  All but the ss csv end
-    with the mean row."""
+    with the mean row.  ``tica_backend`` ("device"; None or "host": the reference's path) selects how the ``js_tica`` column is computed."""
     columns = metric_columns(extra_metrics)
+    tica_backend = tica_backend_switch(tica_backend)
     switches = dict(secondary_structure=secondary_structure, contacts=contacts, sasa=sasa, saxs=saxs, dynamics=dynamics)
     reports = [r for r in REPORTS if _switch(r.name, switches[r.name])]
     if saxs_data is not None and not _switch("saxs", saxs):
@@ -273,7 +285,8 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     output_dir = os.path.dirname(os.path.dirname(os.path.abspath(pred_dir)))
     tag = tag if tag is not None else "dev"
     fns = {"val_clash": metrics.validity, "val_bond": metrics.bonding_validity, "js_pwd": metrics.js_pwd, "js_rg": metrics.js_rg,
-           "js_tica": metrics.js_tica,   # the reference's five columns, in its order (src/eval.py:64-70)
+           "js_tica": metrics.js_tica if tica_backend == "host" else partial(metrics.js_tica, backend=tica_backend),
+           # (the reference's five columns, in its order: src/eval.py:64-70)
            "div_rmsd": metrics.diversity_rmsd, "div_tm": metrics.diversity_tm, "div_lddt": metrics.diversity_lddt}
     coverage = {"rmsd": metrics.coverage_rmsd, "tm": metrics.coverage_tm, "lddt": metrics.coverage_lddt}
     eval_res = {k: {} for k in columns}
@@ -327,7 +340,8 @@ def evaluate(cfg):
     pred_dir = cfg.get("pred_dir")
     scoring = dict(target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"), extra_metrics=cfg.get("extra_metrics"),
                    cluster_cutoff=cfg.get("cluster_cutoff"), secondary_structure=cfg.get("secondary_structure"),
-                   contacts=cfg.get("contacts"), sasa=cfg.get("sasa"), saxs=cfg.get("saxs"), saxs_data=cfg.get("saxs_data"), dynamics=cfg.get("dynamics"))
+                   contacts=cfg.get("contacts"), sasa=cfg.get("sasa"), saxs=cfg.get("saxs"), saxs_data=cfg.get("saxs_data"), dynamics=cfg.get("dynamics"),
+                   tica_backend=cfg.get("tica_backend"))
     if pred_dir and os.path.isdir(pred_dir):
         log.info(f"Found pre-computed prediction directory {pred_dir}.")
         return evaluate_prediction(pred_dir, **scoring)

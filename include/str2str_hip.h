@@ -771,6 +771,76 @@ int s2s_ca_covariance(const float* x, int n, int n_res, const double* xform, con
 int s2s_ca_project(const float* x, int n, int n_res, const double* xform, const double* mean, const double* components, int n_components,
                    double* proj, void* stream);
 
+/* ---- Time-lagged covariances and TICA: which collective coordinates are SLOW?  Reversible mean, instantaneous and time-lagged covariance
+ * of a feature trajectory, and projections onto given components (csrc/ensemble_tica.hip; the heavy half of the estimator behind the
+ * reference's js_tica, deeptime's Covariance(lagtime, reversible=True, remove_data_mean=True, bessels_correction=False) as oracle/tica.py
+ * restates it) ----
+ * f [T, D] float32 features, row-major, a row per frame in time order -- ANY features (the CA distances of s2s_ca_pairwise_distances are
+ * one choice).  lag >= 1; n = T - lag >= 1 frame pairs (t, t + lag), t = 0 .. n - 1.  Everything is float64 on the widened float32 values;
+ * no float atomics.
+ *  Mean.  m_c = (1 / 2n) sum_{t<n} (f_tc + f_{t+lag,c}).  Thread g of 16 adds the pairs g, g + 16, ... in ascending order, each as
+ *     f_t + f_{t+lag}; the 16 partial sums are added in ascending g, the total is divided by 2n: the order depends on (T, lag) alone.
+ *  Covariances (population form, no Bessel factor; two-pass) about the GIVEN mean.  With z_t = (f_t - m) / sqrt(2n):
+ *       C00[r, c] = sum_{t<n} (z_tr z_tc + z_{t+lag,r} z_{t+lag,c})        C0t[r, c] = sum_{t<n} (z_tr z_{t+lag,c} + z_{t+lag,r} z_tc)
+ *     A prepass writes two operand streams indexed by PAIR, z_t and z_{t+lag} (no halo), as float64 into the workspace in blocks of 48
+ *     features x 4-padded pairs, ws[(((s * nblk + blk) * G + g) * step + k) * 48 + r] for stream s, group g, pair slot k; padding features
+ *     and padding pairs are zero.  One wave owns a 48 x 48 block with block-row <= block-column and forms BOTH matrices from the same four
+ *     operand loads per k-step on v_mfma_f64_16x16x4_f64 (18 accumulator tiles, 36 instructions per 12 loaded doubles per lane), the k
+ *     loop over the pairs in ascending order, four per instruction; per step an entry of C00 takes its z_t product, then its z_{t+lag}
+ *     product, an entry of C0t its (t, t+lag) product, then its (t+lag, t) product.  Only entries with r <= c are computed; each is stored
+ *     and copied to (c, r): both matrices are exactly symmetric.
+ *  k-split.  With B = ceil(D / 48) blocks, the triangle has B (B + 1) / 2 of them.  The n pairs, rounded up to a multiple of 4 (n4), are
+ *     divided into G contiguous groups of S2S_TICA_GROUP_PAIRS pairs (a multiple of 4; the last group takes what is left):
+ *       wanted = max(1, min(S2S_TICA_WAVE_SLOTS / triangle, ceil(n4 / S2S_TICA_MIN_GROUP_PAIRS)))
+ *       group  = 4 ceil(n4 / 4 / wanted),   G = ceil(n4 / group)
+ *     -- a function of (n, D) alone, never of the workspace.  G = 1 accumulates in C itself.  With G > 1 group g accumulates into partial
+ *     blocks of its own in the workspace (the accumulator tiles as the lanes hold them, S2S_TICA_PARTIAL_BLOCK_DOUBLES per block and
+ *     matrix); a last kernel adds the partials of an entry in ascending g and writes the entry and its mirror.
+ *  Chunking.  The pairs go through the workspace in passes; a pass advances EVERY group by the same number of pairs, a multiple of 4, and
+ *     the accumulators of a later pass start from the running values, so every entry is the same chain of instructions -- the same bits
+ *     -- for any workspace size.
+ *  Projection.  proj[s, k] = sum_c (f_sc - m_c) v_kc for components v [n_components, D] float64.  One wave per row, f read directly (no
+ *     staging of the row: D is not bounded by LDS); lane l adds the features l, l + 64, ... in ascending order, the lanes meet in the xor
+ *     tree: the order depends on D alone.
+ * What this is NOT: an eigensolver (the two symmetric eigenproblems of TICA are the host's), a weighted estimator, a VAMP score.  No
+ * gradients. */
+#define S2S_TICA_MAX_FEATURES 16384       /* two D x D float64 matrices of 2 GiB each */
+#ifndef S2S_TICA_WAVE_SLOTS
+#define S2S_TICA_WAVE_SLOTS 1024          /* 256 CUs x 4 SIMDs: one wave of the product kernel per SIMD */
+#endif
+#define S2S_TICA_MIN_GROUP_PAIRS 512      /* a group is worth a wave from 128 k-steps (4608 MFMAs) on */
+#define S2S_TICA_PARTIAL_BLOCK_DOUBLES 2304   /* a 48 x 48 block as 9 accumulator tiles of 64 lanes x 4 registers */
+#define S2S_TICA_BLOCKS(D) (((long long)(D) + 47) / 48)
+#define S2S_TICA_TRIANGLE(D) (S2S_TICA_BLOCKS(D) * (S2S_TICA_BLOCKS(D) + 1) / 2)
+#define S2S_TICA_PAIRS4(T, lag) (((long long)(T) - (long long)(lag) + 3) / 4 * 4)
+#define S2S_TICA_MIN_(a, b) ((a) < (b) ? (a) : (b))
+#define S2S_TICA_GROUPS_WANTED(D, T, lag)                                                                                        \
+    (S2S_TICA_MIN_(S2S_TICA_WAVE_SLOTS / S2S_TICA_TRIANGLE(D), (S2S_TICA_PAIRS4(T, lag) + S2S_TICA_MIN_GROUP_PAIRS - 1) / S2S_TICA_MIN_GROUP_PAIRS) < 1 \
+         ? 1                                                                                                                     \
+         : S2S_TICA_MIN_(S2S_TICA_WAVE_SLOTS / S2S_TICA_TRIANGLE(D), (S2S_TICA_PAIRS4(T, lag) + S2S_TICA_MIN_GROUP_PAIRS - 1) / S2S_TICA_MIN_GROUP_PAIRS))
+#define S2S_TICA_GROUP_PAIRS(D, T, lag) \
+    ((S2S_TICA_PAIRS4(T, lag) / 4 + S2S_TICA_GROUPS_WANTED(D, T, lag) - 1) / S2S_TICA_GROUPS_WANTED(D, T, lag) * 4)
+#define S2S_TICA_GROUPS(D, T, lag) ((S2S_TICA_PAIRS4(T, lag) + S2S_TICA_GROUP_PAIRS(D, T, lag) - 1) / S2S_TICA_GROUP_PAIRS(D, T, lag))
+/* the workspace of s2s_lagged_covariances whose passes advance every group by `chunk` pairs (rounded up to a multiple of 4): the two
+ * operand streams of every group, then the partial blocks (none with one group) */
+#define S2S_TICA_WORKSPACE_DOUBLES(D, T, lag, chunk)                                                         \
+    (2 * S2S_TICA_BLOCKS(D) * 48 * S2S_TICA_GROUPS(D, T, lag) * (((long long)(chunk) + 3) / 4 * 4) +         \
+     (S2S_TICA_GROUPS(D, T, lag) > 1 ? S2S_TICA_GROUPS(D, T, lag) * 2 * S2S_TICA_TRIANGLE(D) * S2S_TICA_PARTIAL_BLOCK_DOUBLES : 0))
+
+/* No scratch.  1 <= D <= S2S_TICA_MAX_FEATURES, lag >= 1, lag < T <= 2^31 - 1; otherwise hipErrorInvalidValue before any launch.
+ * mean [D] float64. */
+int s2s_lagged_mean(const float* f, int T, int D, int lag, double* mean, void* stream);
+
+/* c00, c0t [D, D] float64, every entry written.  workspace: caller-owned, workspace_doubles >= S2S_TICA_WORKSPACE_DOUBLES(D, T, lag, 4); a
+ * pass advances every group by the largest multiple of 4 pairs it holds (at most a group's pairs).  The same checks. */
+int s2s_lagged_covariances(const float* f, int T, int D, int lag, const double* mean, double* c00, double* c0t, double* workspace,
+                           long long workspace_doubles, void* stream);
+
+/* proj [T, n_components] float64.  No scratch.  T >= 1, 1 <= D <= S2S_TICA_MAX_FEATURES, n_components >= 1; otherwise
+ * hipErrorInvalidValue before any launch. */
+int s2s_feature_project(const float* f, int T, int D, const double* mean, const double* components, int n_components, double* proj,
+                        void* stream);
+
 /* ---- PDB text at the exit of the path (HOST pointers, host code; byte-identical to the reference's writers) ---- */
 
 /* protein.to_pdb per model (src/common/protein.py:152-234) over atom37 [n_models, n_res, 37, 3] float32 HOST coordinates with

@@ -34,6 +34,7 @@ UNITS = {
     "ensemble_rmsd.hip": [],   # float64 throughout; contraction stays on (an fma only removes a rounding)
     "ensemble_tm.hip": [],     # (as above)
     "ensemble_pca.hip": [],    # (as above)
+    "ensemble_tica.hip": [],   # (as above)
     "ensemble_cluster.hip": [],   # integer and float64 comparisons only
     "ensemble_lddt.hip": [],      # float64 distances against squared bounds, integer sums
     # contraction off: the argument of the soft Q's exponential is then bit for bit the numpy yardstick's, so the a-priori bound of its

@@ -35,7 +35,10 @@ built-in form factors, no side chains), ``saxs_mae``, ``mean_rh`` and ``js_rh`` 
 the comparison with a measured curve.  How the ensemble moves: ``ensemble_covariance``, ``cross_correlation``, ``pca`` and ``pca_project``
 (csrc/ensemble_pca.hip: mean structure, 3L x 3L covariance and projections of the superposed CA coordinates in float64; the symmetric
 eigenproblem stays on the host), with ``js_pca``, ``rmsip``, ``dccm_mae`` and ``total_variance`` as the summaries -- Cartesian PCA of one
-global superposition, CA only, no quasi-harmonic entropy.
+global superposition, CA only, no quasi-harmonic entropy.  Which coordinates are slow: ``tica`` and ``tica_project``
+(csrc/ensemble_tica.hip: the reversible mean and the time-lagged covariances of any feature trajectory and the projections in float64 on
+the device; the two eigenproblems stay on the host) give the components, eigenvalues and implied timescales behind ``js_tica``, whose
+``backend="device"`` runs on them -- no weights in the fit, no VAMP score.
 """
 from __future__ import annotations
 
@@ -159,11 +162,23 @@ def tica_fit(x: np.ndarray, lagtime: int, dim: int = 2, epsilon: float = 1e-6):
     eigenvalue can rank second), canonical signs (every vector's largest-magnitude entry positive), kinetic-map scaling (vector x
     eigenvalue).  -> (mean [D], projection [D, dim]); transform = (x - mean) @ proj.
     Pinned by an analytic two-state process and against the restatement in oracle/tica.py (tests/test_host_cpu.py)."""
-    import scipy.linalg
-
     x = np.asarray(x, dtype=np.float64)
     if x.shape[0] <= lagtime:
         raise ValueError(f"js_tica: {x.shape[0]} frames are not enough for lagtime {lagtime}")
+    x0, xt = x[:-lagtime], x[lagtime:]
+    mean = 0.5 * (x0.mean(0) + xt.mean(0))
+    a, b = x0 - mean, xt - mean
+    n = 2.0 * a.shape[0]
+    c00 = (a.T @ a + b.T @ b) / n
+    c0t = (a.T @ b + b.T @ a) / n
+    return mean, _tica_from_covariances(c00, c0t, dim, epsilon)[0]
+
+
+def _tica_from_covariances(c00: np.ndarray, c0t: np.ndarray, dim: int, epsilon: float):
+    """The tail of ``tica_fit`` on the reversible covariances [D, D], wherever they were formed: eigh of C00, the absolute cut-off,
+    whitening, the symmetric eigenproblem of the whitened C0t, magnitude order, canonical signs, kinetic map.
+    -> (projection [D, <= dim], eigenvalues [<= dim], the rank kept above the cut-off)."""
+    import scipy.linalg
 
     def by_magnitude(vals, vecs):
         order = np.argsort(np.abs(vals))[::-1]
@@ -173,12 +188,6 @@ def tica_fit(x: np.ndarray, lagtime: int, dim: int = 2, epsilon: float = 1e-6):
         top = np.argmax(np.abs(vecs), axis=0)
         return vecs * np.sign(vecs[top, np.arange(vecs.shape[1])])[None, :]
 
-    x0, xt = x[:-lagtime], x[lagtime:]
-    mean = 0.5 * (x0.mean(0) + xt.mean(0))
-    a, b = x0 - mean, xt - mean
-    n = 2.0 * a.shape[0]
-    c00 = (a.T @ a + b.T @ b) / n
-    c0t = (a.T @ b + b.T @ a) / n
     w, v = by_magnitude(*scipy.linalg.eigh(c00))
     cut = max(epsilon, -w.min() + 1e-16) if w.min() < 0 else epsilon
     m = len(w) - int(np.searchsorted(np.abs(w)[::-1], cut))
@@ -187,22 +196,92 @@ def tica_fit(x: np.ndarray, lagtime: int, dim: int = 2, epsilon: float = 1e-6):
     white = canonical(v[:, :m]) / np.sqrt(w[:m])[None, :]     # [D, m]: white.T C00 white = I
     lam, u = by_magnitude(*scipy.linalg.eigh(white.T @ c0t @ white))
     proj = canonical(white @ u) * lam[None, :]
-    return mean, proj[:, :dim]
+    return proj[:, :dim], lam[:dim], m
 
 
-def js_tica(ca_coords_dict, ref_key="target", n_bins=50, lagtime=20, return_tic=True, weights=None):
+class EnsembleTICA(NamedTuple):
+    """The slow components of a feature trajectory [T, D], float64: ``mean`` [D] (the reversible mean the covariances are taken about),
+    ``components`` [D, dim] (``tica_fit``'s projection: whitened, canonical signs, kinetic-map scale; fewer columns when the rank is
+    below ``dim``), ``eigenvalues`` [dim] (the autocorrelations at the lag, by descending magnitude), ``timescales`` [dim]
+    (-lagtime / ln |eigenvalue| in frames, inf for |eigenvalue| >= 1), ``lagtime`` and ``rank`` (the eigenvalues of C00 kept above
+    the cut-off)."""
+    mean: np.ndarray
+    components: np.ndarray
+    eigenvalues: np.ndarray
+    timescales: np.ndarray
+    lagtime: int
+    rank: int
+
+
+def _features(x, pwd_offset=1) -> torch.Tensor:
+    """[T, L, 3] coordinates -> their CA distances (``pairwise_distance_ca``'s, left on the device); [T, D] -> taken as features.
+    -> float32 device tensor [T, D]."""
+    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+    if t.ndim == 3:
+        return ops.ca_pairwise_distances(_dev(t), pwd_offset)
+    if t.ndim != 2:
+        raise ValueError(f"tica: expected coordinates [T, L, 3] or features [T, D], got {tuple(t.shape)}")
+    return t.to("cuda", torch.float32).contiguous()
+
+
+def tica(coords_or_features, lagtime=20, dim=2, epsilon=1e-6, pwd_offset=1, max_pairs=None) -> EnsembleTICA:
+    """Which collective coordinates are slow?  TICA of a trajectory in time order, ``tica_fit``'s estimator with its heavy half on the
+    device: coordinates [T, L, 3] are featurised with their CA distances (``pwd_offset`` as in ``pairwise_distance_ca``), an input
+    [T, D] is taken as features (any: distances, sines and cosines of torsions, ...; rounded to float32).  The reversible mean and the
+    two D x D covariances over the T - ``lagtime`` frame pairs run on the device in float64 (csrc/ensemble_tica.hip; ``max_pairs`` bounds
+    the pairs its workspace holds at a time and changes no bit); the two symmetric eigenproblems run on the host, as for ``pca``
+    (``_tica_from_covariances``: the tail ``tica_fit`` runs).  No weights in the fit, no VAMP score, at most ops.TICA_MAX_FEATURES
+    features."""
+    if isinstance(lagtime, bool) or int(lagtime) != lagtime or lagtime < 1:
+        raise ValueError(f"tica: lagtime must be an integer >= 1, got {lagtime}")
+    if isinstance(dim, bool) or int(dim) != dim or dim < 1:
+        raise ValueError(f"tica: dim must be an integer >= 1, got {dim}")
+    f = _features(coords_or_features, pwd_offset)
+    if f.shape[0] <= lagtime:
+        raise ValueError(f"js_tica: {f.shape[0]} frames are not enough for lagtime {lagtime}")
+    mean = ops.lagged_mean(f, int(lagtime))
+    c00, c0t = ops.lagged_covariances(f, mean, int(lagtime), max_pairs)
+    proj, lam, rank = _tica_from_covariances(c00.cpu().numpy(), c0t.cpu().numpy(), int(dim), epsilon)
+    with np.errstate(divide="ignore"):
+        timescales = np.where(np.abs(lam) >= 1.0, np.inf, -float(lagtime) / np.log(np.minimum(np.abs(lam), 1.0)))
+    return EnsembleTICA(mean.cpu().numpy(), np.ascontiguousarray(proj), lam, np.abs(timescales), int(lagtime), int(rank))
+
+
+def tica_project(coords_or_features, model: EnsembleTICA, pwd_offset=1) -> np.ndarray:
+    """``coords_or_features`` ([R, L, 3] or [R, D], as in ``tica``) on the components of ``model`` -> float64 [R, dim]:
+    proj[s, k] = sum_c (f_sc - mean_c) v_ck in float64, on the device."""
+    f = _features(coords_or_features, pwd_offset)
+    mean = torch.as_tensor(np.asarray(model.mean, dtype=np.float64), device=f.device).contiguous()
+    comps = torch.as_tensor(np.ascontiguousarray(np.asarray(model.components, dtype=np.float64).T), device=f.device)
+    return ops.feature_project(f, mean, comps).cpu().numpy()
+
+
+def js_tica(ca_coords_dict, ref_key="target", n_bins=50, lagtime=20, return_tic=True, weights=None, backend="host"):
     """reference :169-200: TICA (2 components, fitted on the reference ensemble's pairwise distances) -> 50-bin histograms over the
-    reference's range per component -> mean Jensen-Shannon distance.  -> results (, projections) like the reference."""
+    reference's range per component -> mean Jensen-Shannon distance.  -> results (, projections) like the reference.
+    ``backend="host"`` (the default) is the reference's path: the features go to the host and deeptime's estimator, or ``tica_fit``
+    without it, fits and projects them there.  ``backend="device"`` fits with ``tica`` and projects every ensemble with
+    ``tica_project`` -- mean, covariances and projections on the device, the same histogram tail; it never consults deeptime."""
+    if backend not in ("host", "device"):
+        raise ValueError(f"js_tica: backend must be 'host' or 'device', got {backend!r}")
     w = _weights(weights, ca_coords_dict)
+    if backend == "device":
+        model = tica(ca_coords_dict[ref_key], lagtime, dim=2)
+        return _js_tica_tail({k: tica_project(v, model) for k, v in ca_coords_dict.items()}, ref_key, n_bins, w, return_tic)
     ca_pwd = {k: pairwise_distance_ca(v) for k, v in ca_coords_dict.items()}
     try:
         from deeptime.decomposition import TICA
 
-        tica = TICA(dim=2, lagtime=lagtime).fit(ca_pwd[ref_key]).fetch_model()
-        ca_dr2d = {k: tica.transform(v) for k, v in ca_pwd.items()}
+        tica_model = TICA(dim=2, lagtime=lagtime).fit(ca_pwd[ref_key]).fetch_model()
+        ca_dr2d = {k: tica_model.transform(v) for k, v in ca_pwd.items()}
     except ImportError:
         mean, proj = tica_fit(ca_pwd[ref_key], lagtime, dim=2)
         ca_dr2d = {k: (v.astype(np.float64) - mean) @ proj for k, v in ca_pwd.items()}
+    return _js_tica_tail(ca_dr2d, ref_key, n_bins, w, return_tic)
+
+
+def _js_tica_tail(ca_dr2d, ref_key, n_bins, w, return_tic):
+    """The histogram tail of ``js_tica`` on the projections of either backend."""
     d_min, d_max = ca_dr2d[ref_key].min(axis=0), ca_dr2d[ref_key].max(axis=0)
     binned = {k: np.stack([np.histogram(v[:, c], bins=n_bins, weights=w[k], range=(d_min[c], d_max[c]))[0] + PSEUDO_C for c in range(v.shape[1])], 1)
               for k, v in ca_dr2d.items()}      # [n_bins, 2]

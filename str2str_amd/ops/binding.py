@@ -65,6 +65,9 @@ _SIGNATURES = {
     "s2s_ca_aligned_mean": [_vp, _i, _i, _vp, _vp, _vp, _vp],
     "s2s_ca_covariance": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _ll, _vp],
     "s2s_ca_project": [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp],
+    "s2s_lagged_mean": [_vp, _i, _i, _i, _vp, _vp],
+    "s2s_lagged_covariances": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp],
+    "s2s_feature_project": [_vp, _i, _i, _vp, _vp, _i, _vp, _vp],
     "s2s_cluster_adjacency": [_vp, _i, _i, _i, _d, _i, _vp, _vp, _vp],
     "s2s_cluster_gromos": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "s2s_format_pdb_models": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _ll],

@@ -1,7 +1,7 @@
 """Ensemble metrics on the device: CA statistics, distance histograms, Kabsch RMSD, TM-score and superposition, lDDT, clustering,
 backbone violations, secondary structure and torsions, contact maps and the fraction of native contacts, solvent accessibility, solution
 scattering (Debye intensity, Kirkwood hydrodynamic radius), essential dynamics (mean structure, covariance and projections of the superposed
-CA coordinates)."""
+CA coordinates), time-lagged covariances of a feature trajectory (the heavy half of TICA) and projections of feature rows."""
 import math
 from typing import Optional
 
@@ -30,6 +30,9 @@ CONTACT_MAX_RES = 1024            # S2S_CONTACT_MAX_RES: the chain length whose 
 CONTACT_LAUNCH_STRUCTURES = 65535  # S2S_CONTACT_MAX_STRUCTURES: structures per launch of the contact kernels
 PCA_MAX_RES = 1024                # S2S_PCA_MAX_RES: the chain length whose centred coordinates fit the LDS of s2s_ca_project as float64
 PCA_WORKSPACE_BYTES = 256 << 20   # budget of the centred coordinates of one chunk of s2s_ca_covariance, unless max_structures says less
+TICA_MAX_FEATURES = 16384         # S2S_TICA_MAX_FEATURES: two D x D float64 matrices of 2 GiB each
+TICA_WAVE_SLOTS = 1024            # S2S_TICA_WAVE_SLOTS: the waves of s2s_lagged_covariances' product kernel that run at once
+TICA_MIN_GROUP_PAIRS = 512        # S2S_TICA_MIN_GROUP_PAIRS: the frame pairs from which a group of its k-split is worth a wave
 CLUSTER_MAX_N = 65536             # S2S_CLUSTER_MAX_N: structures per clustering (512 MB of neighbour bits)
 CLUSTER_ROUNDS_PER_SYNC = 32      # rounds of the greedy loop enqueued between two readbacks of its state
 
@@ -311,6 +314,86 @@ def ca_fit_transforms(ca: torch.Tensor, target: Optional[torch.Tensor] = None, s
         if k + 1 < rounds:
             target = ca_aligned_mean(ca, xform, sample_weights).to(torch.float32)
     return xform
+
+
+def tica_groups(n_pairs: int, D: int):
+    """S2S_TICA_GROUPS / S2S_TICA_GROUP_PAIRS of include/str2str_hip.h: how s2s_lagged_covariances divides ``n_pairs`` frame pairs of ``D``
+    features -> (the number of groups G, the pairs of a group: a multiple of 4).  A function of (n_pairs, D) alone."""
+    blocks = -(-D // 48)
+    n4 = -(-n_pairs // 4) * 4
+    wanted = max(1, min(TICA_WAVE_SLOTS // (blocks * (blocks + 1) // 2), -(-n4 // TICA_MIN_GROUP_PAIRS)))
+    group = -(-(n4 // 4) // wanted) * 4
+    return -(-n4 // group), group
+
+
+def _features(fn: str, f, lag=None):
+    """``f`` [T, D], the feature rows of ``fn`` in time order, and its ``lag`` (None: ``fn`` has none), checked but for the device
+    -> (T, D, lag)."""
+    if not isinstance(f, torch.Tensor):
+        raise HipLibraryError(f"{fn}: expected tensors, got {type(f).__name__} for features")
+    if f.ndim != 2 or f.shape[0] < 1 or f.shape[1] < 1:
+        raise HipLibraryError(f"{fn}: features {tuple(f.shape)}, expected [T, D]")
+    T, D = f.shape
+    if D > TICA_MAX_FEATURES or T > 2 ** 31 - 1:
+        raise HipLibraryError(f"{fn}: at most {TICA_MAX_FEATURES} features and {2 ** 31 - 1} frames, got {D} and {T}")
+    if lag is not None:
+        lag = _integer(fn, "lag", lag)
+        if T <= lag:
+            raise HipLibraryError(f"{fn}: {T} frames are not enough for lagtime {lag}")
+    return T, D, lag
+
+
+def _feature_vector(fn: str, what: str, v, shape: tuple):
+    if not isinstance(v, torch.Tensor) or v.shape != shape:
+        raise HipLibraryError(f"{fn}: {what} {tuple(getattr(v, 'shape', ()))}, expected {list(shape)}")
+
+
+def lagged_mean(features: torch.Tensor, lag: int) -> torch.Tensor:
+    """The reversible mean of the feature trajectory features [T, D] (fp32 device tensor, a row per frame in time order) over its
+    n = T - ``lag`` frame pairs (t, t + lag) -> [D] fp64: (1 / 2n) sum_t (f_t + f_{t+lag}) in float64.  The order of the sum depends on
+    (T, lag) alone."""
+    T, D, lag = _features("lagged_mean", features, lag)
+    _req(features, name="features")
+    mean = torch.empty(D, dtype=torch.float64, device=features.device)
+    _check(load_library().s2s_lagged_mean(_p(features), T, D, lag, _p(mean), _stream()), "s2s_lagged_mean")
+    return mean
+
+
+def lagged_covariances(features: torch.Tensor, mean: torch.Tensor, lag: int, max_pairs: Optional[int] = None):
+    """The instantaneous and the time-lagged covariance of features [T, D] about ``mean`` [D] fp64 over the n = T - ``lag`` frame pairs
+    -> (c00, c0t), each [D, D] fp64: with a = f_t - mean and b = f_{t+lag} - mean, sum_t (a a^T + b b^T) / 2n and sum_t (a b^T + b a^T) / 2n
+    (the reversible estimate, population form), both exactly symmetric.  ``max_pairs`` bounds the frame pairs (each group of
+    ``tica_groups`` takes a multiple of 4, at least 4) whose centred features the workspace holds at a time; the default is what
+    PCA_WORKSPACE_BYTES holds.  The result is bit for bit the same for any value."""
+    fn = "lagged_covariances"
+    T, D, lag = _features(fn, features, lag)
+    _feature_vector(fn, "mean", mean, (D,))
+    blocks = -(-D // 48)
+    G, group = tica_groups(T - lag, D)
+    pairs = PCA_WORKSPACE_BYTES // (8 * 2 * 48 * blocks) if max_pairs is None else _integer(fn, "max_pairs", max_pairs)
+    step = min(group, max(4, -(-(pairs // G) // 4) * 4))
+    _req(features, name="features"); _req(mean, torch.float64, "mean")
+    c00, c0t = (torch.empty(D, D, dtype=torch.float64, device=features.device) for _ in range(2))
+    partials = G * 2 * (blocks * (blocks + 1) // 2) * 2304 if G > 1 else 0
+    ws = torch.empty(2 * blocks * 48 * G * step + partials, dtype=torch.float64, device=features.device)   # S2S_TICA_WORKSPACE_DOUBLES
+    _check(load_library().s2s_lagged_covariances(_p(features), T, D, lag, _p(mean), _p(c00), _p(c0t), _p(ws), ws.numel(), _stream()),
+           "s2s_lagged_covariances")
+    return c00, c0t
+
+
+def feature_project(features: torch.Tensor, mean: torch.Tensor, components: torch.Tensor) -> torch.Tensor:
+    """features [T, D] (fp32 device tensor) onto ``components`` [K, D] fp64 about ``mean`` [D] fp64 -> [T, K] fp64:
+    sum_c (f_sc - mean_c) v_kc.  The order of a sum depends on D alone."""
+    fn = "feature_project"
+    T, D, _ = _features(fn, features)
+    _feature_vector(fn, "mean", mean, (D,))
+    if not isinstance(components, torch.Tensor) or components.ndim != 2 or components.shape[0] < 1 or components.shape[1] != D:
+        raise HipLibraryError(f"{fn}: components {tuple(getattr(components, 'shape', ()))}, expected [K, {D}]")
+    _req(features, name="features"); _req(mean, torch.float64, "mean"); _req(components, torch.float64, "components")
+    K = components.shape[0]
+    proj = torch.empty(T, K, dtype=torch.float64, device=features.device)
+    _check(load_library().s2s_feature_project(_p(features), T, D, _p(mean), _p(components), K, _p(proj), _stream()), "s2s_feature_project")
+    return proj
 
 
 def _tm_d0(d0) -> float:

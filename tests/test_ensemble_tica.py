@@ -1,0 +1,170 @@
+"""Time-lagged covariances and TICA on the device (csrc/ensemble_tica.hip) against the float64 yardstick in tests/ref_tica.py.
+
+The two sides hold the same float64 values (the widened float32 features) and differ in the order of their sums alone; the device is held
+to route B (np.longdouble, ascending frames) under the bounds of tests/tica_cases.py.  The device centres about its own mean, which
+differs from the yardstick's by some delta <= the first bound; the covariances change by -delta_r sum (a_c + b_c) - delta_c sum (a_r + b_r)
++ 2n delta_r delta_c, and sum (a + b) is itself a rounding residue about the reversible mean: second order.
+
+End to end the tolerance of every quantity is measured on the reference (tica_cases.sensitivity: how far the a-priori rounding of the
+covariances moves the oracle's own results), never on the code under test; the preconditions of those cases are asserted on the CPU
+(tests/test_ensemble_tica_cpu.py)."""
+import glob
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ref_tica as ref
+import tica_cases as cases
+from conftest import GOLDEN, record_margin
+from ensemble_cases import load_eval_entry, to_device as _dev, write_models
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize("offset", (False, True), ids=("origin", "offset100"))
+@pytest.mark.parametrize("T,D,lag", cases.CASES)
+def test_mean_covariances_and_projection(T, D, lag, offset):
+    """(6, 3, 1): a partial tile, n = 5 no multiple of 4; (37, 45, 3): one partial block; (130, 49, 20): one feature into a second block, so
+    mirrors and an off-diagonal block; (257, 120, 7): 2.5 blocks; (21, 45, 20): n = 1; the last: the smallest T whose pairs are split into
+    two groups at D = 45."""
+    from str2str_amd import ops
+
+    f = cases.features(T, D, lag, offset)
+    want_mean, want_c00, want_c0t, a00, a0t = cases.reference(T, D, lag, offset)
+    n = T - lag
+    G = ops.tica_groups(n, D)[0]
+    assert G == (2 if T == cases.SPLIT_T else 1)
+    fd = _dev(f)
+    mean = ops.lagged_mean(fd, lag)
+    c00, c0t = ops.lagged_covariances(fd, mean, lag)
+    assert all(t.is_cuda and t.dtype == torch.float64 for t in (mean, c00, c0t)) and mean.shape == (D,) and c00.shape == c0t.shape == (D, D)
+    mean_h, c00_h, c0t_h = mean.cpu().numpy(), c00.cpu().numpy(), c0t.cpu().numpy()
+    share_m = float((np.abs(mean_h - want_mean) / cases.mean_bound(f, lag)).max())
+    share_00 = float((np.abs(c00_h - want_c00) / cases.cov_bound(a00, n)).max())
+    share_0t = float((np.abs(c0t_h - want_c0t) / cases.cov_bound(a0t, n)).max())
+    print(f"T={T} D={D} lag={lag} offset={offset} G={G}: mean at {share_m:.3e} of its bound, C00 at {share_00:.3e}, C0t at {share_0t:.3e}")
+    record_margin("ensemble_tica_mean_of_apriori_bound", share_m, 1.0)
+    record_margin("ensemble_tica_c00_of_apriori_bound", share_00, 1.0)
+    record_margin("ensemble_tica_c0t_of_apriori_bound", share_0t, 1.0)
+    assert share_m <= 1.0 and share_00 <= 1.0 and share_0t <= 1.0
+    for c in (c00_h, c0t_h):                                                                # exactly symmetric, as bytes
+        assert c.tobytes() == np.ascontiguousarray(c.T).tobytes()
+    for max_pairs in (4, 8, n):                                                             # any chunking: identical bytes
+        got = ops.lagged_covariances(fd, mean, lag, max_pairs=max_pairs)
+        assert torch.equal(got[0], c00) and torch.equal(got[1], c0t), max_pairs
+    # projection onto random unit vectors about the yardstick's mean: the same z on both sides
+    K = min(5, D)
+    v = np.linalg.qr(np.random.default_rng(T).normal(size=(D, K)))[0].T.copy()
+    want_proj, magnitudes = ref.project(f, want_mean, v)
+    proj = ops.feature_project(fd, _dev(want_mean.copy()), _dev(v))
+    share_p = float((np.abs(proj.cpu().numpy() - want_proj) / cases.proj_bound(magnitudes, D)).max())
+    record_margin("ensemble_tica_projection_of_apriori_bound", share_p, 1.0)
+    assert proj.shape == (T, K) and proj.dtype == torch.float64 and share_p <= 1.0, share_p
+    # a row slice of f as its own call: the sub-trajectory's result, whatever lies around it in memory
+    a, b = 1, T - 1
+    if b - a > lag:
+        sub_mean, sub_c00, sub_c0t, sub_a00, sub_a0t = ref.explicit(f[a:b], lag)
+        got_mean = ops.lagged_mean(fd[a:b], lag)
+        got_c00, got_c0t = ops.lagged_covariances(fd[a:b], got_mean, lag)
+        assert (np.abs(got_mean.cpu().numpy() - sub_mean) <= cases.mean_bound(f[a:b], lag)).all()
+        assert (np.abs(got_c00.cpu().numpy() - sub_c00) <= cases.cov_bound(sub_a00, n - 2)).all()
+        assert (np.abs(got_c0t.cpu().numpy() - sub_c0t) <= cases.cov_bound(sub_a0t, n - 2)).all()
+        alone = fd[a:b].clone()
+        again = ops.lagged_covariances(alone, got_mean, lag)
+        assert torch.equal(ops.lagged_mean(alone, lag), got_mean) and torch.equal(again[0], got_c00) and torch.equal(again[1], got_c0t)
+    assert torch.equal(ops.feature_project(fd[a:b], mean, _dev(v)), ops.feature_project(fd, mean, _dev(v))[a:b])
+
+
+@pytest.mark.parametrize("tag", cases.TAGS)
+def test_tica_end_to_end_against_the_oracle(tag):
+    """``tica`` on tests/golden/tica.npz (a: D = 66, lag 20; b: D = 45, lag 5) against oracle.tica.TICA: the rank is the oracle's;
+    eigenvalues, components and the projections of target and pred sit within 4 s, s the largest change the a-priori rounding of the
+    covariances causes in the oracle's own results over 8 seeded perturbations (4: random draws understate the worst alignment)."""
+    from str2str_amd import ops
+    from str2str_amd.metrics import metrics
+
+    ca, feats, lag, *_ = cases.fixture(tag)
+    est, s = cases.oracle_fit(tag), cases.sensitivity(tag)
+    model = metrics.tica(ca["target"], lagtime=lag)
+    D = feats["target"].shape[1]
+    assert isinstance(model, metrics.EnsembleTICA) and model.lagtime == lag and model.rank == len(ref.OT.spd_eig(ref.route_a(feats["target"], lag)[1], 1e-6)[0])
+    assert model.mean.shape == (D,) and model.components.shape == (D, 2) and model.eigenvalues.shape == model.timescales.shape == (2,)
+    tics = {k: metrics.tica_project(v, model) for k, v in ca.items()}
+    got = {"eigenvalues": np.abs(model.eigenvalues - est.eigenvalues[:2]).max(), "components": np.abs(model.components - est.coefficients).max(),
+           **{f"tic_{k}": np.abs(tics[k] - est.transform(feats[k])).max() for k in ca}}
+    for name, d in got.items():
+        print(f"tag {tag}: {name} off by {d:.3e}, s = {s[name]:.3e}, share of 4 s {d / (4 * s[name]):.3e}")
+        record_margin(f"ensemble_tica_end_to_end_{name} tag={tag} (bound: 4 s)", d, 4 * s[name])
+        record_margin("ensemble_tica_end_to_end_of_4s", d / (4 * s[name]), 1.0)
+    assert all(d <= 4 * s[name] for name, d in got.items()), (got, s)
+    want_ts = np.where(np.abs(est.eigenvalues[:2]) >= 1.0, np.inf, -lag / np.log(np.abs(est.eigenvalues[:2])))
+    assert np.abs(model.timescales - want_ts).max() <= 1e-6 * want_ts.max() and (model.timescales > 0).all()
+    # features in, features out: the same model bit for bit, and tica_project of coordinates is feature_project of their features
+    fd = ops.ca_pairwise_distances(_dev(ca["target"].astype(np.float32)), 1)
+    assert np.array_equal(fd.cpu().numpy(), feats["target"])
+    same = metrics.tica(feats["target"], lagtime=lag, max_pairs=8)
+    assert all(np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(same, model))
+    direct = ops.feature_project(fd, _dev(model.mean), _dev(np.ascontiguousarray(model.components.T)))
+    assert direct.cpu().numpy().tobytes() == tics["target"].tobytes() == metrics.tica_project(feats["target"], model).tobytes()
+    with pytest.raises(ValueError, match="frames are not enough for lagtime"):
+        metrics.tica(ca["target"][:lag], lagtime=lag)
+
+
+@pytest.mark.parametrize("tag", cases.TAGS)
+def test_js_tica_device_backend_equals_the_fixture(tag):
+    """``js_tica(backend="device")`` with and without ``weights=`` equals the fixture's rounded values (the CPU file asserts that no
+    projection sits on a histogram edge and no score on a rounding boundary); the default backend is untouched."""
+    from str2str_amd.metrics import metrics
+
+    ca, _, lag, w, want, want_w = cases.fixture(tag)
+    res, tics = metrics.js_tica(ca, ref_key="target", lagtime=lag, backend="device")
+    assert res["target"] == 0.0 and res["pred"] == want, (res, want)
+    assert tics["pred"].shape == (len(ca["pred"]), 2) and tics["target"].dtype == np.float64
+    res_w = metrics.js_tica(ca, ref_key="target", lagtime=lag, weights={"pred": w}, return_tic=False, backend="device")
+    assert res_w["pred"] == want_w and res_w["pred"] != res["pred"], (res_w, want_w)
+    host = metrics.js_tica(ca, ref_key="target", lagtime=lag, return_tic=False)
+    assert abs(host["pred"] - want) < 1.5e-4                     # (the bound of test_hip_parity.py for the host path)
+
+
+def test_eval_tica_backend_switch(tmp_path):
+    """The CLN025 fixture as a target trajectory of 400 frames (two autoregressive coordinates of different memory move the chain's second
+    half and its last three residues, plus noise: many more frames than the 45 features, two slow eigenvalues that stand apart, so the
+    components are well conditioned) and 60 samples.  With ``tica_backend="device"`` the metrics csv has the same columns and rows, the js_tica column is a number within one unit of the
+    fourth decimal of the default run's, and every other column is the default run's text."""
+    from str2str_amd.common.pdb_utils import extract_backbone_coords
+
+    entry = load_eval_entry("s2s_eval_entry_tica")
+    fixture = os.path.join(GOLDEN, "pdb", "CLN025.pdb")
+    tgt = extract_backbone_coords(fixture)
+    L = tgt.shape[1]
+    rng = np.random.default_rng(33)
+    target_dir = tmp_path / "targets"
+    target_dir.mkdir()
+
+    def trajectory(R, c1, c2):
+        s = np.zeros((R, 2))
+        for t in range(1, R):                                   # two autoregressive coordinates of unit variance
+            s[t] = (c1, c2) * s[t - 1] + rng.normal(size=2) * np.sqrt(1.0 - np.square((c1, c2)))
+        x = tgt[0][None] + rng.normal(size=(R, L, 3)) * 0.3
+        x[:, L // 2:, 0] += 2.0 * s[:, :1]
+        x[:, -3:, 1] += 2.0 * s[:, 1:]
+        return x
+
+    write_models(str(target_dir / "CLN025.pdb"), fixture, trajectory(400, 0.995, 0.97))
+    samples = trajectory(60, 0.9, 0.8)
+    rows = {}
+    for sub, backend in (("host", None), ("device", "device")):
+        pred_dir = tmp_path / sub / "samples" / "all"
+        pred_dir.mkdir(parents=True)
+        write_models(str(pred_dir / "CLN025.pdb"), fixture, samples)
+        entry.evaluate_prediction(str(pred_dir), str(target_dir), tag="t", tica_backend=backend)
+        files = glob.glob(str(tmp_path / sub / "metrics_t_*.csv"))
+        assert len(files) == 1 and sorted(f.split("_")[0] for f in os.listdir(tmp_path / sub)) == ["metrics", "samples"]
+        rows[sub] = [ln.rstrip("\n").split("\t") for ln in open(files[0])]
+    assert rows["host"][0] == rows["device"][0] == ["", "val_clash", "val_bond", "js_pwd", "js_rg", "js_tica"]
+    assert [r[0] for r in rows["device"][1:]] == ["CLN025", "mean"]
+    for host, device in zip(rows["host"][1:], rows["device"][1:]):
+        assert host[:5] == device[:5]
+        assert 0.0 < float(device[5]) <= 1.0 and abs(float(device[5]) - float(host[5])) <= 1e-4 + 1e-12, (host, device)
