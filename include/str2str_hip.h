@@ -763,7 +763,9 @@ int s2s_ca_scattering(const float* ca, int n, int n_res, const double* q, int n_
 int s2s_ca_aligned_mean(const float* x, int n, int n_res, const double* xform, const double* p, double* mean, void* stream);
 
 /* cov [3 n_res, 3 n_res] float64, every entry written.  workspace: caller-owned, workspace_doubles >= S2S_PCA_WORKSPACE_DOUBLES(n_res, 4);
- * the chunk is the largest multiple of 4 structures it holds (at most n rounded up to 4).  The same checks. */
+ * the chunk is the largest multiple of 4 structures it holds (at most n rounded up to 4).  The same checks.  Per chunk: the prepass, then
+ * cov_product_kernel of csrc/ensemble_pca.hip, one wave per 48 x 48 block on or above the diagonal, on the tile set and operands of
+ * csrc/sym48_f64.h. */
 int s2s_ca_covariance(const float* x, int n, int n_res, const double* xform, const double* p, const double* mean, double* cov,
                       double* workspace, long long workspace_doubles, void* stream);
 

@@ -4,29 +4,23 @@
 //
 //   s2s_ca_aligned_mean   m = sum_s p_s y_s,  y_s = R_s x_s + t_s in float64 (the float32 coordinates widened; never rounded back).
 //   s2s_ca_covariance     C = sum_s p_s (y_s - m)(y_s - m)^T, two-pass.  A prepass writes sqrt(p_s) (y_s - m) in blocks of 48 coordinates x
-//                         structures; every 48 x 48 block of C on or above the diagonal is one [48, R] x [R, 48] float64 matrix product
-//                         on v_mfma_f64_16x16x4_f64 (nine accumulator tiles per wave, the idiom of ensemble_rmsd.hip), the k loop running
-//                         over the structures in ascending order.  The SAME scaled coordinates serve as either operand, products commute
-//                         and the sums run in one order; the lower triangle is written from its mirror, so C is exactly symmetric.
-//                         The structures pass through the workspace in chunks of a multiple of 4 (one MFMA's k); the accumulators of a
-//                         later chunk start from the running C, so the chain of MFMAs of an entry -- and with it every bit of C -- is the
-//                         same for any chunk size.
+//                         structures; every 48 x 48 block of C on or above the diagonal is one wave on the tile set and operands
+//                         of sym48_f64.h, the k loop running over the structures in ascending order: C is exactly
+//                         symmetric.  The structures pass through the workspace in chunks of a multiple of 4 (one MFMA's k); the
+//                         accumulators of a later chunk start from the running C, so the chain of MFMAs of an entry -- and with it every
+//                         bit of C -- is the same for any chunk size.
 //   s2s_ca_project        proj[s, k] = sum_c (y_sc - m_c) v_kc, one wave per structure.
 //
 // Everything is float64; contraction stays on (an fma only removes a rounding).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "ensemble_common.h"
 #include "str2str_hip.h"
+#include "sym48_f64.h"
 
 namespace {
 
-using ensemble::wave_sum;
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-constexpr int MEAN_GROUPS = 16;   // structure groups of a workgroup of the mean kernel (64 coordinates x 16 groups = 1024 threads)
+using sym48::MEAN_GROUPS;
 
 // Coordinate c = 3 i + a of structure s after its transform (xform NULL: the identity, the widened float32 value itself).
 __device__ __forceinline__ double aligned_coord(const float* __restrict__ x, const double* __restrict__ xform, long long s, int n3, int c) {
@@ -37,29 +31,18 @@ __device__ __forceinline__ double aligned_coord(const float* __restrict__ x, con
     return t[3 * a] * (double)p[i3] + t[3 * a + 1] * (double)p[i3 + 1] + t[3 * a + 2] * (double)p[i3 + 2] + t[9 + a];
 }
 
-// Thread (group g, coordinate c) adds the structures g, g + 16, ... in ascending order; the 16 partial sums of a coordinate are then added in
-// ascending g: the order is a function of the number of structures alone.
+// sym48::grouped_column_sum over the structures, the term of structure s being p_s y_s: the order is a function of their number alone.
 __global__ void __launch_bounds__(64 * MEAN_GROUPS) aligned_mean_kernel(const float* __restrict__ x, int n, int n3,
                                                                         const double* __restrict__ xform, const double* __restrict__ p,
                                                                         double* __restrict__ mean) {
-    __shared__ double part[MEAN_GROUPS][64];
-    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + lane;
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63);
     const double uniform = 1.0 / (double)n;
-    double acc = 0.0;
-    if (c < n3)
-        for (int s = g; s < n; s += MEAN_GROUPS) acc += (p ? p[s] : uniform) * aligned_coord(x, xform, s, n3, c);
-    part[g][lane] = acc;
-    __syncthreads();
-    if (g == 0 && c < n3) {
-        double m = part[0][lane];
-        for (int k = 1; k < MEAN_GROUPS; ++k) m += part[k][lane];
-        mean[c] = m;
-    }
+    double m;
+    if (sym48::grouped_column_sum(n, c < n3, [=](long long s) { return (p ? p[s] : uniform) * aligned_coord(x, xform, s, n3, c); }, m)) mean[c] = m;
 }
 
 // Prepass of one chunk (structures s0 .. s0 + n_chunk - 1 of n; Sp = n_chunk rounded up to 4): out[(blk * Sp + k) * 48 + r] =
-// sqrt(p_s) (y_s[48 blk + r] - mean[48 blk + r]), zero for a coordinate >= n3 and for a padding structure k >= n_chunk.
+// sqrt(p_s) (y_s[48 blk + r] - mean[48 blk + r]), zero for a coordinate >= n3 and for a padding structure k >= n_chunk (sym48_f64.h's layout).
 __global__ void __launch_bounds__(256) cov_prep_kernel(const float* __restrict__ x, int n, int n3, int nblk, const double* __restrict__ xform,
                                                        const double* __restrict__ p, const double* __restrict__ mean, int s0, int n_chunk, int Sp,
                                                        double* __restrict__ out) {
@@ -74,21 +57,21 @@ __global__ void __launch_bounds__(256) cov_prep_kernel(const float* __restrict__
     out[((size_t)(cp / 48) * Sp + k) * 48 + cp % 48] = v;
 }
 
-// One wave per 48 x 48 block (bi = blockIdx.y, bj = blockIdx.x) of C with bi <= bj.  MFMA operands (lane maps of the f64 16x16x4 form): lane l
-// feeds A[row = l & 15][k = l >> 4] and B[k = l >> 4][col = l & 15], and receives D[row = (l >> 4) + 4 r][col = l & 15] in register r.
-// first: the accumulators start from zero, otherwise from the running C.  Entries with row <= col are stored and copied to their mirror.
+// One wave per 48 x 48 block (bi = blockIdx.y, bj = blockIdx.x) of C with bi <= bj, on the tiles and operands of sym48_f64.h, one operand
+// set per k-step: three waves per SIMD, so the 2080 blocks of the cap are resident at once.  The running-value load and the mirrored store
+// are its own loops (measured faster than the header's helpers: DESIGN.md).  first: start from zero, otherwise from the running C.
 __global__ void __launch_bounds__(64) cov_product_kernel(const double* __restrict__ buf, int Sp, int n3, int first, double* __restrict__ cov) {
     const int bi = blockIdx.y, bj = blockIdx.x, lane = threadIdx.x;
     if (bi > bj) return;
     const int q = lane >> 4, col = lane & 15;
     const double* pa = buf + (size_t)bi * Sp * 48 + q * 48 + col;
     const double* pb = buf + (size_t)bj * Sp * 48 + q * 48 + col;
-    d4 acc[3][3];
+    sym48::Block acc;
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+            acc[i][j] = sym48::d4{0.0, 0.0, 0.0, 0.0};
             if (!first) {
                 const int gc = bj * 48 + 16 * j + col;
 #pragma unroll
@@ -99,14 +82,10 @@ __global__ void __launch_bounds__(64) cov_product_kernel(const double* __restric
             }
         }
     for (int k0 = 0; k0 < Sp; k0 += 4) {
-        double av[3], bv[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { av[c] = pa[16 * c]; bv[c] = pb[16 * c]; }
+        sym48::Operands<1> x;
+        x.load(pa, pb);
         pa += 192; pb += 192;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i], bv[j], acc[i][j], 0, 0, 0);
+        x.accumulate(acc);
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -123,8 +102,7 @@ __global__ void __launch_bounds__(64) cov_product_kernel(const double* __restric
         }
 }
 
-// One wave per structure: z = y - mean goes to LDS once, then lane l adds the coordinates l, l + 64, ... of every component in ascending
-// order and the lanes meet in the xor tree: the order is a function of the chain length alone.
+// One wave per structure: z = y - mean goes to LDS once, then sym48::project_row: the order is a function of the chain length alone.
 __global__ void __launch_bounds__(64) project_kernel(const float* __restrict__ x, int n3, const double* __restrict__ xform,
                                                      const double* __restrict__ mean, const double* __restrict__ comp, int K,
                                                      double* __restrict__ proj) {
@@ -133,13 +111,7 @@ __global__ void __launch_bounds__(64) project_kernel(const float* __restrict__ x
     const long long s = blockIdx.x;
     for (int c = lane; c < n3; c += 64) z[c] = aligned_coord(x, xform, s, n3, c) - mean[c];
     __syncthreads();
-    for (int k = 0; k < K; ++k) {
-        const double* v = comp + (size_t)k * n3;
-        double acc = 0.0;
-        for (int c = lane; c < n3; c += 64) acc += z[c] * v[c];
-        acc = wave_sum(acc);
-        if (lane == 0) proj[s * K + k] = acc;
-    }
+    sym48::project_row(n3, [&](int c) { return z[c]; }, comp, K, proj + s * K);
 }
 
 }  // namespace

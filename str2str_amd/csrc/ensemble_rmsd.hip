@@ -21,13 +21,12 @@
 #include "ensemble_common.h"
 #include "kabsch_f64.h"
 #include "str2str_hip.h"
+#include "sym48_f64.h"
 
 namespace {
 
 using namespace kabsch;
 using ensemble::wave_sum;
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 // Prepass, one wave per structure slot (slots n .. 16 ceil(n/16) - 1 and residues L .. Lp - 1 are zero padding): weighted centroid, G, and
 // sqrt(w_i) (x_i - x-bar) as float64 in blocks of 16 structures, out[(blk * Lp + i) * 48 + 16 c + s].  The SAME scaled coordinates serve
@@ -67,10 +66,10 @@ __global__ void __launch_bounds__(64) rmsd_prep_kernel(const float* __restrict__
     }
 }
 
-// One wave per 16 x 16 block of pairs (A block = blockIdx.y, B block = 4 blockIdx.x + wave).  MFMA operands (lane maps of the f64
-// 16x16x4 form): lane l feeds A[row = l & 15][k = l >> 4] and B[k = l >> 4][col = l & 15], and receives D[row = (l >> 4) + 4 r][col = l & 15]
-// in register r.  row0 >= 0: the A ensemble is rows row0 .. of the B ensemble (a row chunk of a self matrix); a pair below the diagonal is
-// then evaluated as its mirror pair (H transposed in registers), so the matrix is exactly symmetric and independent of the chunking.
+// One wave per 16 x 16 block of pairs (A block = blockIdx.y, B block = 4 blockIdx.x + wave), on the tiles, operands and lane maps of
+// sym48_f64.h: register r of lane l holds the pair (row (l >> 4) + 4 r, column l & 15) of the block in every tile.  row0 >= 0: the A
+// ensemble is rows row0 .. of the B ensemble (a row chunk of a self matrix); a pair below the diagonal is then evaluated as its mirror
+// pair (H transposed in registers), so the matrix is exactly symmetric and independent of the chunking.
 // mirror: the whole self matrix in one launch -- blocks below the diagonal are skipped and written by their mirror block.
 __global__ void __launch_bounds__(256) rmsd_pairs_kernel(const double* __restrict__ a_buf, const double* __restrict__ g_a, int n_a,
                                                          const double* __restrict__ b_buf, const double* __restrict__ g_b, int n_b, int L,
@@ -83,20 +82,13 @@ __global__ void __launch_bounds__(256) rmsd_pairs_kernel(const double* __restric
     const int q = lane >> 4, col = lane & 15;
     const double* pa = a_buf + (size_t)bi * Lp * 48 + q * 48 + col;
     const double* pb = b_buf + (size_t)bj * Lp * 48 + q * 48 + col;
-    d4 acc[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+    sym48::Block acc;
+    sym48::zero(acc);
     for (int k0 = 0; k0 < Lp; k0 += 4) {
-        double av[3], bv[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { av[c] = pa[16 * c]; bv[c] = pb[16 * c]; }
+        sym48::Operands<1> x;
+        x.load(pa, pb);
         pa += 192; pb += 192;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i], bv[j], acc[i][j], 0, 0, 0);
+        x.accumulate(acc);
     }
     const double W = *w_sum;
     const int gj = bj * 16 + col;

@@ -6,32 +6,25 @@
 //   s2s_lagged_mean         m = (1 / 2n) sum_{t<n} (f_t + f_{t+lag}), n = T - lag, in float64 on the widened float32 features.
 //   s2s_lagged_covariances  with z_t = (f_t - m) / sqrt(2n):  C00 = sum_t (z_t z_t^T + z_{t+lag} z_{t+lag}^T),
 //                           C0t = sum_t (z_t z_{t+lag}^T + z_{t+lag} z_t^T).  A prepass writes the two operand streams z_t and z_{t+lag},
-//                           indexed by PAIR (no halo), in blocks of 48 features x 4-padded pairs; one wave owns a 48 x 48 block on or above
-//                           the diagonal and forms BOTH matrices from the same four operand loads per k-step: 18 accumulator tiles, 36
-//                           v_mfma_f64_16x16x4_f64 per 12 loaded doubles per lane.  Entries with row <= column are stored and copied to
-//                           their mirror: both matrices are exactly symmetric.  When the triangle has fewer blocks than the device has
-//                           wave slots the pairs are divided into G contiguous groups (G a function of (n, D) alone), each with partial
-//                           matrices of its own in the workspace; a last kernel adds them in ascending group order.  The pairs pass
-//                           through the workspace in chunks of a multiple of 4 per group; a later chunk's accumulators start from the
-//                           running values, so the chain of MFMAs of an entry -- every bit -- is the same for any workspace size.
+//                           indexed by PAIR (no halo), in blocks of 48 features x 4-padded pairs; the symmetric block product of
+//                           sym48_f64.h with two streams forms BOTH matrices, exactly symmetric, from the same four operand loads per
+//                           k-step.  When the triangle has fewer blocks than the device has wave slots the pairs are divided into G
+//                           contiguous groups (G a function of (n, D) alone), each with partial matrices of its own in the workspace; a
+//                           last kernel adds them in ascending group order.  The pairs pass through the workspace in passes of a multiple
+//                           of 4 per group: every bit is the same for any workspace size.
 //   s2s_feature_project     proj[s, k] = sum_c (f_sc - m_c) v_kc, one wave per row, f read directly (no staging: D is not bounded by LDS).
 //
 // Everything is float64, no float atomics; contraction stays on (an fma only removes a rounding).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "ensemble_common.h"
 #include "str2str_hip.h"
+#include "sym48_f64.h"
 
 namespace {
 
-using ensemble::wave_sum;
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-constexpr int MEAN_GROUPS = 16;    // pair groups of a workgroup of the mean kernel (64 features x 16 groups = 1024 threads)
-constexpr int TILE_DOUBLES = 256;  // one 16 x 16 accumulator tile in the lane layout: register r of lane l at r * 64 + l
-constexpr int BLOCK_DOUBLES = 9 * TILE_DOUBLES;   // S2S_TICA_PARTIAL_BLOCK_DOUBLES
+using sym48::BLOCK_DOUBLES;   // S2S_TICA_PARTIAL_BLOCK_DOUBLES
+using sym48::MEAN_GROUPS;
 
 // How the pairs are divided (the rule of include/str2str_hip.h, S2S_TICA_GROUPS): a function of (n, D) alone.
 struct Split {
@@ -52,23 +45,13 @@ inline Split split_of(int T, int D, int lag) {
     return s;
 }
 
-// Thread (group g, feature c) adds the pairs g, g + 16, ... in ascending order, each as f_t + f_{t+lag}; the 16 partial sums of a feature
-// are then added in ascending g and divided by 2n: the order is a function of (T, lag) alone.
+// sym48::grouped_column_sum over the pairs, the term of pair t being f_t + f_{t+lag}, divided by 2n: the order is a function of (T, lag) alone.
 __global__ void __launch_bounds__(64 * MEAN_GROUPS) lagged_mean_kernel(const float* __restrict__ f, int n, int D, int lag,
                                                                        double* __restrict__ mean) {
-    __shared__ double part[MEAN_GROUPS][64];
-    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + lane;
-    double acc = 0.0;
-    if (c < D)
-        for (long long t = g; t < n; t += MEAN_GROUPS) acc += (double)f[t * D + c] + (double)f[(t + lag) * D + c];
-    part[g][lane] = acc;
-    __syncthreads();
-    if (g == 0 && c < D) {
-        double m = part[0][lane];
-        for (int k = 1; k < MEAN_GROUPS; ++k) m += part[k][lane];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+    double m;
+    if (sym48::grouped_column_sum(n, c < D, [=](long long t) { return (double)f[t * D + c] + (double)f[(t + lag) * D + c]; }, m))
         mean[c] = m / (2.0 * (double)n);
-    }
 }
 
 // Prepass of one pass (every group advanced to the pair offset `off` of its own, `step` pairs each).  Slot (g, k) holds the pair
@@ -96,60 +79,10 @@ __global__ void __launch_bounds__(256) lagged_prep_kernel(const float* __restric
     out[stream + at] = z1;
 }
 
-// Block (bi, bj), bi <= bj, number `tri` of the upper triangle in row-major order.
-__device__ __forceinline__ void block_of(long long tri, int nblk, int& bi, int& bj) {
-    int i = 0;
-    while (tri >= nblk - i) { tri -= nblk - i; ++i; }
-    bi = i; bj = i + (int)tri;
-}
-
-// Entries with row <= col of an accumulated block go to C and to their mirror.  (gr > gc occurs only inside a diagonal block: that entry
-// comes from its mirror.)
-__device__ __forceinline__ void store_block(const d4 (&acc)[3][3], int bi, int bj, int q, int col, int D, double* __restrict__ c) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int gc = bj * 48 + 16 * j + col;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int gr = bi * 48 + 16 * i + q + 4 * r;
-                if (gr >= D || gc >= D || gr > gc) continue;
-                c[(size_t)gr * D + gc] = acc[i][j][r];
-                if (gr < gc) c[(size_t)gc * D + gr] = acc[i][j][r];
-            }
-        }
-}
-
-// The operands of one k-step (4 pairs) of a lane: z_t (a0) and z_{t+lag} (a1) of the row block, z_t (b0) and z_{t+lag} (b1) of the column
-// block, three doubles each (the three 16-row tiles of a 48-block).
-struct Operands {
-    double a0[3], a1[3], b0[3], b1[3];
-
-    __device__ __forceinline__ void load(const double* __restrict__ pa, const double* __restrict__ pb, size_t stream) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { a0[c] = pa[16 * c]; a1[c] = pa[stream + 16 * c]; b0[c] = pb[16 * c]; b1[c] = pb[stream + 16 * c]; }
-    }
-
-    __device__ __forceinline__ void accumulate(d4 (&s00)[3][3], d4 (&s0t)[3][3]) const {
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                s00[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[i], b0[j], s00[i][j], 0, 0, 0);
-                s00[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[i], b1[j], s00[i][j], 0, 0, 0);
-                s0t[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[i], b1[j], s0t[i][j], 0, 0, 0);
-                s0t[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[i], b0[j], s0t[i][j], 0, 0, 0);
-            }
-    }
-};
-
-// One wave per (block of the upper triangle = blockIdx.x, group = blockIdx.y).  MFMA operands (lane maps of the f64 16x16x4 form): lane l
-// feeds A[row = l & 15][k = l >> 4] and B[k = l >> 4][col = l & 15], and receives D[row = (l >> 4) + 4 r][col = l & 15] in register r.
-// Per k-step (4 pairs) the lane loads z_t and z_{t+lag} of block bi (a0, a1) and of block bj (b0, b1), three doubles each, and every tile
-// (i, j) takes   C00 += a0_i b0_j, C00 += a1_i b1_j, C0t += a0_i b1_j, C0t += a1_i b0_j   in that order.
-// first: the accumulators start from zero, otherwise from the running values -- of C itself (part == NULL: one group), or of the group's
-// partial block in the lane layout, part[(((g * 2 + m) * ntri + tri) * 9 + 3 i + j) * 256 + r * 64 + lane].
+// One wave per (block of the upper triangle = blockIdx.x, group = blockIdx.y) of one pass, on the pieces of sym48_f64.h; buf is the
+// prepass's output.
+// first: the accumulators start from zero, otherwise from the running values -- of c00 and c0t themselves (part == NULL: one group), or of
+// the group's partial blocks in the lane layout, part[((g * 2 + m) * ntri + tri) * BLOCK_DOUBLES ...], m = 0 for c00, 1 for c0t.
 __global__ void __launch_bounds__(64) lagged_product_kernel(const double* __restrict__ buf, int nblk, long long ntri, int G, long long group,
                                                             long long n4, long long off, int step, int D, int first,
                                                             double* __restrict__ c00, double* __restrict__ c0t, double* __restrict__ part) {
@@ -160,39 +93,26 @@ __global__ void __launch_bounds__(64) lagged_product_kernel(const double* __rest
     if (kn <= 0) return;                                     // this group is already through
     if (kn > step) kn = step;
     int bi, bj;
-    block_of(tri, nblk, bi, bj);
+    sym48::block_of(tri, nblk, bi, bj);
     const int q = lane >> 4, col = lane & 15;
     const size_t stream = (size_t)nblk * G * step * 48;
     const double* pa = buf + (((size_t)bi * G + g) * step + q) * 48 + col;
     const double* pb = buf + (((size_t)bj * G + g) * step + q) * 48 + col;
     double* p00 = part ? part + ((((size_t)g * 2 + 0) * ntri + tri) * BLOCK_DOUBLES) + lane : nullptr;
     double* p0t = part ? part + ((((size_t)g * 2 + 1) * ntri + tri) * BLOCK_DOUBLES) + lane : nullptr;
-    d4 s00[3][3], s0t[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            s00[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-            s0t[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-            if (first) continue;
-            const int gc = bj * 48 + 16 * j + col;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (part) {
-                    s00[i][j][r] = p00[(3 * i + j) * TILE_DOUBLES + r * 64];
-                    s0t[i][j][r] = p0t[(3 * i + j) * TILE_DOUBLES + r * 64];
-                } else {
-                    const int gr = bi * 48 + 16 * i + q + 4 * r;
-                    if (gr < D && gc < D) {
-                        s00[i][j][r] = c00[(size_t)gr * D + gc];
-                        s0t[i][j][r] = c0t[(size_t)gr * D + gc];
-                    }
-                }
-            }
-        }
-    // Two operand sets in turn (no register copies between steps): while one set's 36 MFMAs run, the other set's loads are in flight.  The
+    sym48::Block s00, s0t;
+    sym48::zero(s00);
+    sym48::zero(s0t);
+    if (!first && part) {
+        sym48::load_partial(s00, p00);
+        sym48::load_partial(s0t, p0t);
+    } else if (!first) {
+        sym48::load_running(s00, bi, bj, q, col, D, c00);
+        sym48::load_running(s0t, bi, bj, q, col, D, c0t);
+    }
+    // Two operand sets in turn (no register copies between steps): while one set's MFMAs run, the other set's loads are in flight.  The
     // step after the last one reloads the last step's operands (an address that is valid anyway) and never uses them.
-    Operands x, y;
+    sym48::Operands<2> x, y;
     const long long steps = kn / 4;
     x.load(pa, pb, stream);
     for (long long s = 0; s < steps; s += 2) {
@@ -208,64 +128,39 @@ __global__ void __launch_bounds__(64) lagged_product_kernel(const double* __rest
         pa += hop2; pb += hop2;
     }
     if (part) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    p00[(3 * i + j) * TILE_DOUBLES + r * 64] = s00[i][j][r];
-                    p0t[(3 * i + j) * TILE_DOUBLES + r * 64] = s0t[i][j][r];
-                }
+        sym48::store_partial(s00, p00);
+        sym48::store_partial(s0t, p0t);
     } else {
-        store_block(s00, bi, bj, q, col, D, c00);
-        store_block(s0t, bi, bj, q, col, D, c0t);
+        sym48::store_mirrored(s00, bi, bj, q, col, D, c00);
+        sym48::store_mirrored(s0t, bi, bj, q, col, D, c0t);
     }
 }
 
 // One wave per (block of the upper triangle = blockIdx.x, matrix = blockIdx.y): the G partial blocks are added in ascending g, in the lane
-// layout the product kernel left them in, and the sums go to C and to the mirrors.
+// layout the product kernel left them in, and the sums go to the matrix and to the mirrors.
 __global__ void __launch_bounds__(64) lagged_reduce_kernel(const double* __restrict__ part, int nblk, long long ntri, int G, int D,
                                                            double* __restrict__ c00, double* __restrict__ c0t) {
     const long long tri = blockIdx.x;
     const int m = blockIdx.y, lane = threadIdx.x;
     int bi, bj;
-    block_of(tri, nblk, bi, bj);
+    sym48::block_of(tri, nblk, bi, bj);
     const size_t per_group = (size_t)2 * ntri * BLOCK_DOUBLES;
     const double* p = part + ((size_t)m * ntri + tri) * BLOCK_DOUBLES + lane;
-    d4 acc[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = p[(3 * i + j) * TILE_DOUBLES + r * 64];
+    sym48::Block acc;
+    sym48::load_partial(acc, p);
     for (int g = 1; g < G; ++g) {
         p += per_group;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[i][j][r] += p[(3 * i + j) * TILE_DOUBLES + r * 64];
+        sym48::add_partial(acc, p);
     }
-    store_block(acc, bi, bj, lane >> 4, lane & 15, D, m ? c0t : c00);
+    sym48::store_mirrored(acc, bi, bj, lane >> 4, lane & 15, D, m ? c0t : c00);
 }
 
-// One wave per row: lane l adds the features l, l + 64, ... of every component in ascending order, read from f itself, and the lanes meet
-// in the xor tree: the order is a function of D alone.
+// One wave per row, sym48::project_row on f_s - mean read from f itself: the order is a function of D alone.
 __global__ void __launch_bounds__(64) feature_project_kernel(const float* __restrict__ f, int D, const double* __restrict__ mean,
                                                              const double* __restrict__ comp, int K, double* __restrict__ proj) {
-    const int lane = threadIdx.x;
     const long long s = blockIdx.x;
     const float* row = f + s * D;
-    for (int k = 0; k < K; ++k) {
-        const double* v = comp + (size_t)k * D;
-        double acc = 0.0;
-        for (int c = lane; c < D; c += 64) acc += ((double)row[c] - mean[c]) * v[c];
-        acc = wave_sum(acc);
-        if (lane == 0) proj[s * K + k] = acc;
-    }
+    sym48::project_row(D, [=](int c) { return ((double)row[c] - mean[c]); }, comp, K, proj + s * K);
 }
 
 inline bool bad_shape(int T, int D, int lag) { return D < 1 || D > S2S_TICA_MAX_FEATURES || lag < 1 || T <= lag; }
@@ -298,8 +193,7 @@ extern "C" int s2s_lagged_covariances(const float* f, int T, int D, int lag, con
         hipLaunchKernelGGL(lagged_product_kernel, dim3((unsigned)sp.ntri, (unsigned)G), dim3(64), 0, st, workspace, sp.nblk, sp.ntri, G, sp.group,
                            sp.n4, off, (int)step, D, off == 0 ? 1 : 0, c00, c0t, part);
     }
-    if (G > 1)
-        hipLaunchKernelGGL(lagged_reduce_kernel, dim3((unsigned)sp.ntri, 2u), dim3(64), 0, st, part, sp.nblk, sp.ntri, G, D, c00, c0t);
+    if (G > 1) hipLaunchKernelGGL(lagged_reduce_kernel, dim3((unsigned)sp.ntri, 2u), dim3(64), 0, st, part, sp.nblk, sp.ntri, G, D, c00, c0t);
     return (int)hipGetLastError();
 }
 

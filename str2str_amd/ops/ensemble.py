@@ -248,6 +248,20 @@ def _pca_on_device(ca, xform, p):
     return None if p is None else p.to(ca.device)
 
 
+def _mean_of(fn: str, mean, shape: tuple, of: str = ""):
+    """The ``mean`` argument of ``fn`` is a tensor of ``shape`` (checked but for the device); ``of``: what the message says the shape is for."""
+    if not isinstance(mean, torch.Tensor) or mean.shape != shape:
+        raise HipLibraryError(f"{fn}: mean {tuple(getattr(mean, 'shape', ()))}{of}, expected {list(shape)}")
+
+
+def _projection(x, x_name: str, mean, components):
+    """What ``ca_project`` and ``feature_project`` share once their shapes are checked: the rows ``x`` fp32, ``mean`` and ``components``
+    [K, width] fp64, all on the device -> (K, proj [rows, K] fp64 on that device, uninitialised)."""
+    _req(x, name=x_name); _req(mean, torch.float64, "mean"); _req(components, torch.float64, "components")
+    K = components.shape[0]
+    return K, torch.empty(x.shape[0], K, dtype=torch.float64, device=x.device)
+
+
 def ca_aligned_mean(ca: torch.Tensor, xform: Optional[torch.Tensor] = None, sample_weights=None) -> torch.Tensor:
     """The mean structure of ca [R, L, 3] (fp32 device tensor) after the transforms ``xform`` [R, 12] fp64 (``ca_superpose``'s; None: the
     identity) -> [L, 3] fp64: sum_s p_s (R_s x_s + t_s) in float64, p = ``sample_weights`` [R] normalised to sum 1 (None: 1 / R).  The order
@@ -267,8 +281,7 @@ def ca_covariance(ca: torch.Tensor, mean: torch.Tensor, xform: Optional[torch.Te
     fn = "ca_covariance"
     R, L, p = _pca_inputs(fn, ca, xform, sample_weights)
     chunk = -(-_launch_structures(fn, max_structures, max(4, PCA_WORKSPACE_BYTES // (8 * 48 * -(-3 * L // 48)))) // 4) * 4
-    if not isinstance(mean, torch.Tensor) or mean.shape != (L, 3):
-        raise HipLibraryError(f"{fn}: mean {tuple(getattr(mean, 'shape', ()))} for {L} residues, expected [{L}, 3]")
+    _mean_of(fn, mean, (L, 3), f" for {L} residues")
     p = _pca_on_device(ca, xform, p)
     _req(mean, torch.float64, "mean")
     cov = torch.empty(3 * L, 3 * L, dtype=torch.float64, device=ca.device)
@@ -287,9 +300,7 @@ def ca_project(ca: torch.Tensor, mean: torch.Tensor, components: torch.Tensor, x
         raise HipLibraryError(f"{fn}: mean {tuple(getattr(mean, 'shape', ()))} and components {tuple(getattr(components, 'shape', ()))}, "
                               f"expected [{L}, 3] and [K, {3 * L}]")
     _pca_on_device(ca, xform, None)
-    _req(mean, torch.float64, "mean"); _req(components, torch.float64, "components")
-    K = components.shape[0]
-    proj = torch.empty(R, K, dtype=torch.float64, device=ca.device)
+    K, proj = _projection(ca, "ca", mean, components)
     _check(load_library().s2s_ca_project(_p(ca), R, L, _p(xform), _p(mean), _p(components), K, _p(proj), _stream()), "s2s_ca_project")
     return proj
 
@@ -343,11 +354,6 @@ def _features(fn: str, f, lag=None):
     return T, D, lag
 
 
-def _feature_vector(fn: str, what: str, v, shape: tuple):
-    if not isinstance(v, torch.Tensor) or v.shape != shape:
-        raise HipLibraryError(f"{fn}: {what} {tuple(getattr(v, 'shape', ()))}, expected {list(shape)}")
-
-
 def lagged_mean(features: torch.Tensor, lag: int) -> torch.Tensor:
     """The reversible mean of the feature trajectory features [T, D] (fp32 device tensor, a row per frame in time order) over its
     n = T - ``lag`` frame pairs (t, t + lag) -> [D] fp64: (1 / 2n) sum_t (f_t + f_{t+lag}) in float64.  The order of the sum depends on
@@ -367,7 +373,7 @@ def lagged_covariances(features: torch.Tensor, mean: torch.Tensor, lag: int, max
     PCA_WORKSPACE_BYTES holds.  The result is bit for bit the same for any value."""
     fn = "lagged_covariances"
     T, D, lag = _features(fn, features, lag)
-    _feature_vector(fn, "mean", mean, (D,))
+    _mean_of(fn, mean, (D,))
     blocks = -(-D // 48)
     G, group = tica_groups(T - lag, D)
     pairs = PCA_WORKSPACE_BYTES // (8 * 2 * 48 * blocks) if max_pairs is None else _integer(fn, "max_pairs", max_pairs)
@@ -386,12 +392,10 @@ def feature_project(features: torch.Tensor, mean: torch.Tensor, components: torc
     sum_c (f_sc - mean_c) v_kc.  The order of a sum depends on D alone."""
     fn = "feature_project"
     T, D, _ = _features(fn, features)
-    _feature_vector(fn, "mean", mean, (D,))
+    _mean_of(fn, mean, (D,))
     if not isinstance(components, torch.Tensor) or components.ndim != 2 or components.shape[0] < 1 or components.shape[1] != D:
         raise HipLibraryError(f"{fn}: components {tuple(getattr(components, 'shape', ()))}, expected [K, {D}]")
-    _req(features, name="features"); _req(mean, torch.float64, "mean"); _req(components, torch.float64, "components")
-    K = components.shape[0]
-    proj = torch.empty(T, K, dtype=torch.float64, device=features.device)
+    K, proj = _projection(features, "features", mean, components)
     _check(load_library().s2s_feature_project(_p(features), T, D, _p(mean), _p(components), K, _p(proj), _stream()), "s2s_feature_project")
     return proj
 

@@ -13,7 +13,7 @@ import numpy as np
 
 import ref_pca as ref
 
-PLAIN_SHAPES = ((5, 3), (33, 16), (40, 17), (130, 40))      # (R, L): see tests/test_ensemble_pca.py for why these
+PLAIN_SHAPES = ((5, 3), (33, 16), (40, 17), (130, 40), (6, 33))      # (R, L): see tests/test_ensemble_pca.py for why these
 FITTED_SHAPES = ((40, 20), (33, 48), (100, 7))
 MODE_SD = (3.0, 1.5, 0.7)                                   # x sqrt(L) / 3 Angstrom: the planted amplitudes' standard deviations
 NOISE = 0.05

@@ -43,7 +43,8 @@ def _apriori_cov_bound(z, p):
 @pytest.mark.parametrize("R,L", cases.PLAIN_SHAPES)
 def test_moments_and_projection_without_fit(R, L, weighted, offset):
     """(5, 3): 9 coordinates, a partial tile, R no multiple of 4; (33, 16): exactly one 48-block; (40, 17): a second block with 3 live
-    rows; (130, 40): 2.5 blocks, so off-diagonal and mirrored blocks."""
+    rows; (130, 40): 2.5 blocks, so off-diagonal and mirrored blocks;
+    (6, 33): 99 coordinates, three blocks with a 3-wide last one at odd row and column blocks, and only two k-steps."""
     from str2str_amd import ops
 
     x, p = cases.plain(R, L, weighted, offset)

@@ -27,8 +27,8 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("T,D,lag", cases.CASES)
 def test_mean_covariances_and_projection(T, D, lag, offset):
     """(6, 3, 1): a partial tile, n = 5 no multiple of 4; (37, 45, 3): one partial block; (130, 49, 20): one feature into a second block, so
-    mirrors and an off-diagonal block; (257, 120, 7): 2.5 blocks; (21, 45, 20): n = 1; the last: the smallest T whose pairs are split into
-    two groups at D = 45."""
+    mirrors and an off-diagonal block; (257, 120, 7): 2.5 blocks; (21, 45, 20): n = 1; (10, 97, 2): three blocks with one live feature
+    in the last, two k-steps; the last: the smallest T whose pairs are split into two groups at D = 45."""
     from str2str_amd import ops
 
     f = cases.features(T, D, lag, offset)

@@ -36,8 +36,9 @@ def groups(n, D):
 SPLIT_D, SPLIT_LAG = 45, 20
 SPLIT_T = next(T for T in range(SPLIT_LAG + 1, 1 << 16) if groups(T - SPLIT_LAG, SPLIT_D)[0] > 1)   # the smallest T with G > 1 at D = 45
 # (T, D, lag): a partial tile with n = 5 no multiple of 4; one partial block; one feature into a second block (mirrors, an off-diagonal
-# block); 2.5 blocks; n = 1; the smallest T at which the pairs of D = 45 are split into groups
-CASES = ((6, 3, 1), (37, 45, 3), (130, 49, 20), (257, 120, 7), (21, 45, 20), (SPLIT_T, SPLIT_D, SPLIT_LAG))
+# block); 2.5 blocks; n = 1; three blocks with one live feature in the last and two k-steps; the smallest T at which the pairs of D = 45
+# are split into groups (it stays the last case)
+CASES = ((6, 3, 1), (37, 45, 3), (130, 49, 20), (257, 120, 7), (21, 45, 20), (10, 97, 2), (SPLIT_T, SPLIT_D, SPLIT_LAG))
 
 
 def _frozen(*arrays):
