@@ -779,7 +779,7 @@ def cluster_gromos(adj: torch.Tensor, deg: torch.Tensor, rounds_per_sync: int = 
     if int(rounds_per_sync) < 1:
         raise HipLibraryError(f"cluster_gromos: rounds_per_sync {rounds_per_sync}")
     dev = adj.device
-    live_deg = deg.clone()                                   # the loop counts its live neighbours down in place
+    live_deg = torch.empty_like(deg).copy_(deg)              # the loop counts its live neighbours down in place
     labels, centres, sizes = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
     state = torch.empty(3, dtype=torch.int32, device=dev)
     live, members = (torch.empty(adj.shape[1], dtype=torch.int64, device=dev) for _ in range(2))
