@@ -76,6 +76,19 @@ int s2s_edge_transition(const float* edge, const float* node_ab, const float* no
  *   (B N N rounded up to 32 pairs; the padding is never read as data).
  *     io_layout bit 0: edge is tiled;  bit 1: out is written tiled;  bit 2: out is not written at all (out may be NULL; needs the
  *     fused projection -- the last EdgeTransition of the trunk, whose pair vectors only feed the next block's projections).
+ *   BY CLASS (the first EdgeTransition behind the edge embedding's class path, below).  The embedding's pair tensor need not exist: every
+ *   row of it is a copy of a record of the class table.  edge is then ONE buffer of 4-byte words,
+ *     [ M32 int32: the class row of every pair in flat pair order, -1 where m_i m_j = 0 | a record of zeros | the class table's records ],
+ *   M32 = n_samples n_res^2 rounded up to 32 (the records start 16-byte aligned; both offsets follow from n_samples and n_res), as
+ *   s2s_edge_embed_classes_f16x3 (table = edge + M32 + one record) and s2s_edge_embed_expand (out = edge, out_tiled = 2) fill it; the
+ *   zero record is the caller's (ops.edge_embed_classes_f16x3 zeroes it).  Rows are addressed by 32-bit BYTE offsets: the records
+ *   (zero record + table) must stay below 4 GB -- the row count is not an argument here, so the caller answers for it (the class
+ *   path's eligibility rule, ops.edge_embed_classes_eligible, refuses larger tables).  A
+ *   lane reads the z[128] of record index + 1 -- 16-byte groups at a stride of 8 floats, as of a row-major row -- so a masked pair
+ *   reads zeros: z x (m_i m_j) for a 0/1 mask.  The index words past the last pair are never read.
+ *     io_layout bit 3: edge is such a buffer (not with bit 0; needs the fused projection, else hipErrorInvalidValue);
+ *     bit 4 (with bit 3 only): its records are 168 floats (the table was built with the fused projection), else 128.
+ *   A split launch (S2S_ET_MAX_PAIRS) moves the index pointer by whole samples; the records stay where they are.
  *   node_ab HERE is [B,N,896] = [ 2^-e (W1[:,128:256].n' + b1) | 2^5 W1[:,256:384].n' | 2^(5-e) (Wf[:,256:384].n' + bf) ]  (e = prescale_exp
  *   below; W1 = the first hidden layer, Wf / bf = final_layer): everything the pair (i, j) takes from its two NODES through a linear
  *   layer, computed once per node.  The column half B_j (384) is the START VALUE of the layer-1 accumulators, which carry 2^5 x the
@@ -156,7 +169,12 @@ int s2s_edge_embed_f16x3(const float* node_a, const float* node_b, const float* 
  * = the row's, or proj_bias_cat64 where m_i m_j = 0.  fixed_cls [B,N] int32: index of fixed_mask[b,i] among the n_fixed values.
  * Bit for bit s2s_edge_embed_f16x3's outputs where the edge mask is non-zero (and equal as numbers where it is zero) under the
  * ELIGIBILITY rules, which are the caller's: one timestep row for the whole chunk, fixed mask exactly 0/1, node mask exactly 0/1
- * (or NULL).  It pays when the table is small against B*N*N (EmbeddingModule.embed).  Launch split and S2S_EE_MAX_PAIRS as above. */
+ * (or NULL).  It pays when the table is small against B*N*N (EmbeddingModule.embed).  Launch split and S2S_EE_MAX_PAIRS as above.
+ *   out_tiled = 2 (INDEX MODE): z is not written.  out receives one int32 per pair in flat pair order -- the pair's class row, or -1
+ *   where m_i m_j = 0: the index words of the by-class buffer of s2s_edge_transition_f16x3 (io_layout bit 3), whose zero record is the
+ *   caller's to provide.  attn_bias and pair_z as in the other modes.
+ *   Records are 168 floats whenever proj_bias_cat64 != NULL -- also with proj_attn_bias = proj_pair_z = NULL, which expands z alone out
+ *   of a table that was built with the fused projection -- else 128. */
 int s2s_edge_embed_classes_f16x3(const float* node_a2, const float* node_b2, const float* rel_table, const float* bin_table,
                                  const void* weight_stream, const float* b2, const float* b3, const float* ln_gamma,
                                  const float* ln_beta, float* table, int n_fixed, int n_rel, int n_bins, float ln_eps,

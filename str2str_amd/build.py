@@ -54,6 +54,7 @@ UNITS = {
     "pair_mlp_f16_b.hip": ["-mllvm", "-pragma-unroll-threshold=10000000", "-fno-slp-vectorize"],
     "pair_mlp_f16_c.hip": ["-mllvm", "-pragma-unroll-threshold=10000000", "-fno-slp-vectorize"],
     "pair_mlp_f16_d.hip": ["-mllvm", "-pragma-unroll-threshold=10000000", "-fno-slp-vectorize"],   # (the edge embedding on its class table)
+    "pair_mlp_f16_e.hip": ["-mllvm", "-pragma-unroll-threshold=10000000", "-fno-slp-vectorize"],   # (the edge transition reading its edge rows by class)
     "pair_embed_expand.hip": [],   # class table -> pair tensors (copies; the class rule is edge_embed_class.h's, explicit in its roundings)
     "ipa_attention.hip": ["-mllvm", "-pragma-unroll-threshold=10000000"],
     "ipa_attention_f16w.hip": ["-mllvm", "-pragma-unroll-threshold=10000000", "-fno-slp-vectorize"],   # (as above; -0.5 .. -1.5 % per IPA block)

@@ -11,6 +11,12 @@
 // Layouts as s2s_edge_embed_f16x3: z row-major [B,N,N,128] or tiled (a 32-pair block is [32 chunks of 4 channels][32 pairs][4]),
 // attn_bias head-major [B,8,N,N], pair_z [B,N,N,32].  Every access is a whole-line 16 B-per-lane access except attn_bias (4 B per
 // lane, 128 B runs, as in the edge embedding).  32-bit pair indices inside a launch; the entry point splits like s2s_edge_embed_f16x3.
+// INDEX MODE (out_tiled = 2): z is not written at all.  `out` receives one int32 per pair in flat pair order, the pair's class row, or
+// -1 where m_i m_j = 0, so that a consumer that reads record index + 1 of [a record of zeros | table] gets z x (m_i m_j) for a 0/1
+// mask (s2s_edge_transition_f16x3, io_layout bit 3; the caller provides the zero record).  attn_bias and pair_z are written as in
+// the other modes.
+// RECORD SIZE: 168 floats whenever proj_bias_cat64 is given, also where the two projection outputs are not asked for (z alone out of a
+// table that was built with the fused projection), else 128.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -22,13 +28,13 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <bool PROJ>
+template <bool PROJ, bool REC168 = PROJ>
 __global__ void __launch_bounds__(256) edge_embed_expand_kernel(
     const float* __restrict__ table, const int* __restrict__ fixed_cls, const float* __restrict__ bin_lower,
     const long long* __restrict__ residue_idx, const float* __restrict__ ca, const float* __restrict__ mask,
     const float* __restrict__ proj_b, float* __restrict__ out, float* __restrict__ attn_bias, float* __restrict__ pair_z,
     long long M, int N, int rel_off, int n_rel, int n_bins, int out_tiled) {
-    constexpr unsigned kRec = PROJ ? s2s::kEeRecProj : s2s::kEeRecPlain;
+    constexpr unsigned kRec = REC168 ? s2s::kEeRecProj : s2s::kEeRecPlain;
     __shared__ __attribute__((aligned(16))) float s_bins[s2s::kEeBinSlots];
     const unsigned lane = threadIdx.x & 63, h = lane >> 5, wave = threadIdx.x >> 6;
     s2s::ee_fill_bins(s_bins, bin_lower, n_bins);
@@ -47,7 +53,9 @@ __global__ void __launch_bounds__(256) edge_embed_expand_kernel(
     const float em = mask ? __fmul_rn(mask[bi], mask[bj]) : 1.0f;
     const float* rec = table + (unsigned long long)row * kRec;
 
-    if (out_tiled) {   // lane (pair n, half h) owns chunks 2g + h of its pair: the store of group g covers 1 KiB of the block
+    if (out_tiled == 2) {   // index mode: 4 B per pair, 128 B per wave
+        if (valid && h == 0) reinterpret_cast<int*>(out)[p] = em == 0.f ? -1 : (int)row;
+    } else if (out_tiled) {   // lane (pair n, half h) owns chunks 2g + h of its pair: the store of group g covers 1 KiB of the block
         float* o = out + (unsigned long long)(p0 >> 5) * 4096u + lane * 4u;
         f32x4 v[16];
 #pragma unroll
@@ -115,7 +123,7 @@ extern "C" int s2s_edge_embed_expand(const float* table, const int* fixed_cls, c
                                      float* proj_attn_bias, float* proj_pair_z, int n_samples, int n_res, int rel_offset, int n_rel,
                                      int n_bins, void* stream) {
     if (n_samples <= 0 || n_res <= 0) return 0;
-    if (n_bins < 1 || n_bins > 32 || (out_tiled & ~1) || n_rel < 1) return (int)hipErrorInvalidValue;
+    if (n_bins < 1 || n_bins > 32 || out_tiled < 0 || out_tiled > 2 || n_rel < 1) return (int)hipErrorInvalidValue;
     if ((proj_attn_bias != nullptr) != (proj_pair_z != nullptr) || (proj_attn_bias && !proj_bias_cat64)) return (int)hipErrorInvalidValue;
     // 32-bit pair indices inside a launch: the split of s2s_edge_embed_f16x3 (and its test hook)
     const long long NN = (long long)n_res * n_res;
@@ -124,20 +132,25 @@ extern "C" int s2s_edge_embed_expand(const float* table, const int* fixed_cls, c
     long long cap = cap_env ? atoll(cap_env) : 0;
     if (cap <= 0 || cap > (1ll << 31) - 1) cap = (1ll << 31) - 1;
     long long chunk = cap / NN;
-    if (out_tiled && chunk < n_samples) chunk -= chunk % tile_aligned_samples(NN);
+    if (out_tiled == 1 && chunk < n_samples) chunk -= chunk % tile_aligned_samples(NN);
     if (chunk < 1) return (int)hipErrorInvalidValue;
     for (long long b0 = 0; b0 < n_samples; b0 += chunk) {
         const long long nb = n_samples - b0 < chunk ? n_samples - b0 : chunk;
         const long long M = nb * NN, rows0 = b0 * n_res;
         const unsigned grid = (unsigned)((M + 127) / 128);
         const float* mk = mask ? mask + rows0 : nullptr;
+        float* o = out + (out_tiled == 2 ? b0 * NN : b0 * NN * 128);   // (index mode: one 4-byte word per pair)
         if (proj_attn_bias)
             hipLaunchKernelGGL(edge_embed_expand_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, table, fixed_cls + rows0,
-                               bin_lower, residue_idx + rows0, ca_xyz + rows0 * 3, mk, proj_bias_cat64, out + b0 * NN * 128, proj_attn_bias + b0 * 8 * NN,
+                               bin_lower, residue_idx + rows0, ca_xyz + rows0 * 3, mk, proj_bias_cat64, o, proj_attn_bias + b0 * 8 * NN,
                                proj_pair_z + b0 * NN * 32, M, n_res, rel_offset, n_rel, n_bins, out_tiled);
+        else if (proj_bias_cat64)   // z alone out of 168-float records
+            hipLaunchKernelGGL((edge_embed_expand_kernel<false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, table, fixed_cls + rows0,
+                               bin_lower, residue_idx + rows0, ca_xyz + rows0 * 3, mk, (const float*)nullptr, o, (float*)nullptr,
+                               (float*)nullptr, M, n_res, rel_offset, n_rel, n_bins, out_tiled);
         else
             hipLaunchKernelGGL(edge_embed_expand_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, table, fixed_cls + rows0,
-                               bin_lower, residue_idx + rows0, ca_xyz + rows0 * 3, mk, (const float*)nullptr, out + b0 * NN * 128, (float*)nullptr,
+                               bin_lower, residue_idx + rows0, ca_xyz + rows0 * 3, mk, (const float*)nullptr, o, (float*)nullptr,
                                (float*)nullptr, M, n_res, rel_offset, n_rel, n_bins, out_tiled);
     }
     return (int)hipGetLastError();

@@ -58,7 +58,7 @@
 // Three translation units from this one source (the four edge-transition instantiations + the two of the edge embedding took 7.5 minutes
 // of a forced build as one unit): S2S_PM_PART 1 (this file compiled directly) = the edge transition for chains of 32+ residues and the
 // public entry point, 2 (pair_mlp_f16_b.hip) = its per-lane-seed form for shorter chains, 3 (pair_mlp_f16_c.hip) = the edge embedding,
-// 4 (pair_mlp_f16_d.hip) = the edge embedding's class-table form.
+// 4 (pair_mlp_f16_d.hip) = the edge embedding's class-table form, 5 (pair_mlp_f16_e.hip) = the edge transition reading its edge rows BY CLASS.
 #ifndef S2S_PM_PART
 #define S2S_PM_PART 1
 #endif
@@ -107,13 +107,18 @@ __device__ float s2s_one[1] = {1.0f};   // stands in for an absent node mask (re
 // PROJ: also emit the NEXT IPA block's linear_b / down_z (ipa.py:177,253) of the pair vector just produced -- one more
 // weight stage (64 x 128 Wcat, chain-packed), 8 more slots on the LayerNorm output while it is still in registers,
 // attention bias written head-major [B,8,N,N], pair_z [B,N,N,32].  Saves the 512 B/pair re-read of z by s2s_pair_project.
-template <bool PROJ, bool STAGE>
+// BYCLS (io_layout bit 3; the first EdgeTransition behind the edge embedding's class path): `edge` is not a pair tensor but the records of
+// the class table, record 0 all zero and class r at record r + 1, and `cls_idx` holds one int32 per pair, its class or -1 where the edge
+// mask is zero (s2s_edge_embed_expand, index mode).  A lane reads its pair's z[128] straight out of its record: the same 16 B groups at
+// a stride of 8 floats as a row-major edge row, from a table that stays in the L2 instead of a pair tensor from HBM.
+template <bool PROJ, bool STAGE, bool BYCLS = false>
 __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
     const float* __restrict__ edge, const float* __restrict__ node_ab, const float* __restrict__ node_p,
     const char* __restrict__ wblob, const float* __restrict__ b2,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mask,
     float* __restrict__ out, long long M, int N, float ln_eps, int io_layout, unsigned mask_stride, const float* __restrict__ proj_b,
-    float* __restrict__ proj_bias_out, float* __restrict__ proj_pz_out, int* __restrict__ range_flag, float sk) {
+    float* __restrict__ proj_bias_out, float* __restrict__ proj_pz_out, int* __restrict__ range_flag, float sk,
+    const int* __restrict__ cls_idx) {
     constexpr int kStages = kStagesBase + (PROJ ? 1 : 0);
     constexpr int kSlots = 8 * kStages;
     // Weight stages in LDS.  PROJ (31 stages, every launch of the sampler): a RING of four 32 KiB buffers, stage x in buffer x & 3, the
@@ -247,6 +252,30 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
         const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(r + g * in_step));
         return make_float4(v.x, v.y, v.z, v.w);
     };
+    // BYCLS: a pair's row as ONE 32-bit byte offset into the records (below 4 GB by the CALLER's rule, see the header: the row count is
+    // not known here): record cls + 1, this lane's
+    // half.  The loads are base (scalar) + offset (one register) + immediate; the class index itself lives from its load to the offset.
+#ifndef S2S_ET_CLS_NT
+#define S2S_ET_CLS_NT 0      // table rows as plain loads (they are re-read from the L2 by every tile that meets the class; profiles/r08_et_by_class_stop_rule.md)
+#endif
+#ifndef S2S_ET_CLS_SLOT
+#define S2S_ET_CLS_SLOT 200  // the schedule slot that requests the next tile's class indices (one HBM round trip ahead of slot kXv0 + 1)
+#endif
+    const unsigned cls_rec = (io_layout & 16) ? s2s::kEeRecProj : s2s::kEeRecPlain;
+    auto cls_pair = [&](long long wg_tile) -> unsigned {   // flat pair of this lane in tile wg_tile, clamped like setup()
+        const unsigned p = ((unsigned)wg_tile * 4u + (unsigned)wave) * 32u + ((unsigned)lane & 31u);
+        return p < (unsigned)M ? p : (unsigned)M - 1u;
+    };
+    auto cls_off = [&](int cls) -> unsigned { return ((unsigned)(cls + 1) * cls_rec + 4u * (unsigned)h) * 4u; };
+    auto ldrow_cls = [&](unsigned off, int g) -> float4 {
+        const f32x4* q = reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(edge) + off + 32 * g);
+#if S2S_ET_CLS_NT
+        const f32x4 v = __builtin_nontemporal_load(q);
+#else
+        const f32x4 v = *q;
+#endif
+        return make_float4(v.x, v.y, v.z, v.w);
+    };
     const long long n_wt = (M + 127) / 128;
     long long wt = blockIdx.x;
     // (No phase stagger between workgroups: each requests its next edge row 16+ slots ahead of its use (kXv0 below), so running in
@@ -269,8 +298,14 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
     };
     {
         float4 xv[16];
+        if constexpr (BYCLS) {
+            const unsigned off = cls_off(cls_idx[cur.p]);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) xv[i] = ldrow(erow_of(cur), i);  // accumulator ("chain") channel order, see xpl
+            for (int i = 0; i < 16; ++i) xv[i] = ldrow_cls(off, i);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) xv[i] = ldrow(erow_of(cur), i);  // accumulator ("chain") channel order, see xpl
+        }
         for (int i = threadIdx.x; i < 768; i += 256)
             s_vec[i] = i < 384 ? sk * b2[i] : (i < 512 ? 0.f : (i < 640 ? gamma[i - 512] : beta[i - 640]));   // (384..511 unused: bf rides in the per-node start values G_j)
         if (PROJ && threadIdx.x < 64) s_vec[768 + threadIdx.x] = proj_b[threadIdx.x];
@@ -461,6 +496,7 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
     bool has_next = false;
     PairCtx nxt = cur;  // next tile's context, edge row and planes: produced under the last 16 slots of this tile
     float4 xv[16];
+    unsigned ncls = 0;   // BYCLS: the next tile's class index (from slot S2S_ET_CLS_SLOT), then its row offset (from slot kXv0 + 1)
     f16x8 xpn[8][2];
     f16x8 xq[8][2];   // final-layer input planes of k-steps 8..15 (block 1 of the layer-2 epilogue)
     auto slot = [&](auto sc) {
@@ -487,14 +523,21 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
         //  address unit -- and whatever waits next on the in-order counter waits for all of it.  Two loads per slot, in slots whose
         //  next counter wait (the weight store 4+ slots later) is at least 6 slots away: HBM latency fits in between.)
         constexpr int kXv0 = 208;
+        if constexpr (BYCLS && s == S2S_ET_CLS_SLOT) ncls = (unsigned)cls_idx[cls_pair(has_next ? wt_next : wt)];
+        if constexpr (BYCLS && s == kXv0 + 1) ncls = cls_off((int)ncls);
         if constexpr (s == kXv0) nxt = setup(has_next ? wt_next : wt);
         if constexpr (s == kXv0 + 3) stage_load(nxt);     // (slots ss = 3, 0 of the next stage: none of the edge row's loads)
         if constexpr (s == kXv0 + 8) stage_store();
         if constexpr (s > kXv0 && s <= kXv0 + 16 && ((s & 3) == 1 || (s & 3) == 2)) {
             constexpr int i = 4 * ((s - kXv0) / 4) + 2 * ((s & 3) - 1);   // 2 loads in each of the slots ss = 1, 2, 5, 6 of two stages
-            const float* er = erow_of(nxt);
-            xv[i] = ldrow(er, i);
-            xv[i + 1] = ldrow(er, i + 1);
+            if constexpr (BYCLS) {
+                xv[i] = ldrow_cls(ncls, i);
+                xv[i + 1] = ldrow_cls(ncls, i + 1);
+            } else {
+                const float* er = erow_of(nxt);
+                xv[i] = ldrow(er, i);
+                xv[i + 1] = ldrow(er, i + 1);
+            }
         }
         if constexpr (s == 236) seeds_load(nxt, 0);
         // ... and the start values of its first two layer-1 tiles (both accumulator tiles are dead from slot 179 on)
@@ -1110,13 +1153,15 @@ int cu_count() {
     return n_cu;
 }
 
-template <bool STAGE>
+template <bool STAGE, bool BYCLS = false>
 int et_launch(const float* edge, const float* node_ab, const float* node_p, const void* weight_stream, const float* b2,
               const float* ln_gamma, const float* ln_beta, const float* mask, float* out, int n_samples, int n_res, float ln_eps,
               int io_layout, const float* proj_bias_cat64, float* proj_attn_bias, float* proj_pair_z, int prescale_exp, int* range_words,
               void* stream) {
     if (n_samples <= 0 || n_res <= 0) return 0;
-    if ((io_layout & ~7) || ((io_layout & 4) && !proj_attn_bias) || (!(io_layout & 4) && !out)) return (int)hipErrorInvalidValue;
+    if ((io_layout & ~31) || ((io_layout & 4) && !proj_attn_bias) || (!(io_layout & 4) && !out)) return (int)hipErrorInvalidValue;
+    // by class (bit 3): not with a tiled input, only with the fused projection; bit 4 (the record size) only with bit 3
+    if (BYCLS != ((io_layout & 8) != 0) || (BYCLS ? ((io_layout & 1) || !proj_attn_bias) : (io_layout & 16) != 0)) return (int)hipErrorInvalidValue;
     if (prescale_exp < 0 || prescale_exp > 15) return (int)hipErrorInvalidValue;
     const float sk = ldexpf(1.0f, -prescale_exp);
     const long long NN = (long long)n_res * n_res;
@@ -1135,22 +1180,26 @@ int et_launch(const float* edge, const float* node_ab, const float* node_p, cons
         const long long M = nb * NN, rows0 = b0 * n_res;
         const long long wg_tiles = (M + 127) / 128;
         const long long grid = wg_tiles < n_cu ? wg_tiles : n_cu;
-        const float* e = edge + b0 * NN * 128;
+        // BYCLS: words [0, M32) of `edge` are the pairs' class indices, the records follow and do not move with the launch
+        const long long m32 = ((long long)n_samples * NN + 31) / 32 * 32;
+        const float* e = BYCLS ? edge + m32 : edge + b0 * NN * 128;
+        const int* ci = BYCLS ? reinterpret_cast<const int*>(edge) + b0 * NN : nullptr;
         const float* nab = node_ab + rows0 * 896;
         const float* np = node_p + rows0 * 128;
         const float* mk = mask ? mask + rows0 : one;
         const unsigned mks = mask ? 1u : 0u;
         float* o = out ? out + b0 * NN * 128 : nullptr;
-        auto k_proj = &edge_transition_f16_kernel<true, STAGE>;
-        auto k_plain = &edge_transition_f16_kernel<false, STAGE>;
-        if (proj_attn_bias)
+        auto k_proj = &edge_transition_f16_kernel<true, STAGE, BYCLS>;
+        if (proj_attn_bias) {
             hipLaunchKernelGGL(k_proj, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, e, nab, np,
                                (const char*)weight_stream, b2, ln_gamma, ln_beta, mk, o, M, n_res, ln_eps, io_layout, mks, proj_bias_cat64,
-                               proj_attn_bias + b0 * 8 * NN, proj_pair_z + b0 * NN * 32, range_words, sk);
-        else
+                               proj_attn_bias + b0 * 8 * NN, proj_pair_z + b0 * NN * 32, range_words, sk, ci);
+        } else if constexpr (!BYCLS) {
+            auto k_plain = &edge_transition_f16_kernel<false, STAGE>;
             hipLaunchKernelGGL(k_plain, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, e, nab, np,
                                (const char*)weight_stream, b2, ln_gamma, ln_beta, mk, o, M, n_res, ln_eps, io_layout, mks,
-                               (const float*)nullptr, (float*)nullptr, (float*)nullptr, range_words, sk);
+                               (const float*)nullptr, (float*)nullptr, (float*)nullptr, range_words, sk, (const int*)nullptr);
+        }
     }
     return (int)hipGetLastError();
 }
@@ -1168,8 +1217,18 @@ extern "C" __attribute__((visibility("hidden"))) int s2s_et_f16x3_short_chains(S
 #if S2S_PM_PART == 2
 extern "C" int s2s_et_f16x3_short_chains(S2S_ET_ARGS) { return et_launch<false>(S2S_ET_PASS); }
 #endif
+// the first EdgeTransition behind the class path of the edge embedding: edge rows read by class (io_layout bit 3; its own translation unit)
+extern "C" __attribute__((visibility("hidden"))) int s2s_et_f16x3_by_class(S2S_ET_ARGS);   // (inside the library only)
+#if S2S_PM_PART == 5
+extern "C" int s2s_et_f16x3_by_class(S2S_ET_ARGS) {
+    // the records (zero record + class rows) are addressed with 32-bit byte offsets: below 4 GB is the caller's contract (header), it
+    // cannot be checked here -- the row count is no argument of this entry point
+    return n_res >= 32 ? et_launch<true, true>(S2S_ET_PASS) : et_launch<false, true>(S2S_ET_PASS);
+}
+#endif
 #if S2S_PM_PART == 1
 extern "C" int s2s_edge_transition_f16x3(S2S_ET_ARGS) {
+    if (io_layout & 8) return s2s_et_f16x3_by_class(S2S_ET_PASS);
     return n_res >= 32 ? et_launch<true>(S2S_ET_PASS) : s2s_et_f16x3_short_chains(S2S_ET_PASS);
 }
 #endif

@@ -46,7 +46,7 @@ def get_timestep_embedding(timesteps: torch.Tensor, embedding_dim: int, max_len:
 
 class EmbeddingModule(nn.Module):
     launch_switches = ("arith", "node_arith")   # attributes set below that select launches: part of sampler._graph_key
-    launch_modes = ("ee_classes",)              # ... and the string-valued ones (S2S_EE_CLASSES), part of the key in the same way
+    launch_modes = ("ee_classes", "et_by_class")   # ... and the string-valued ones (S2S_EE_CLASSES, S2S_ET_BY_CLASS), part of the key in the same way
 
     def __init__(self, init_embed_size: int, node_embed_size: int, edge_embed_size: int, num_bins: int = 22,
                  min_bin: float = 1e-5, max_bin: float = 20.0, self_conditioning: bool = True):
@@ -75,6 +75,11 @@ class EmbeddingModule(nn.Module):
         self.ee_classes = os.environ.get("S2S_EE_CLASSES", "auto")
         if self.ee_classes not in ("auto", "0", "1"):
             raise ValueError(f"S2S_EE_CLASSES={self.ee_classes!r}: expected auto, 0 or 1")
+        # behind the class path, the pair tensor by class (ops.PairByClass: the first EdgeTransition reads the table, z is not materialised):
+        # "auto" / "1" wherever DenoisingNet.forward can take it, "0" never
+        self.et_by_class = os.environ.get("S2S_ET_BY_CLASS", "auto")
+        if self.et_by_class not in ("auto", "0", "1"):
+            raise ValueError(f"S2S_ET_BY_CLASS={self.et_by_class!r}: expected auto, 0 or 1")
         self._mask01_cache = DerivedCache()
 
     # ---- derived tensors
@@ -184,7 +189,8 @@ class EmbeddingModule(nn.Module):
               next_proj=None, t_emb: Optional[torch.Tensor] = None, edge_layout: str = "rowmajor", t_img: Optional[torch.Tensor] = None):
         """-> node_embed [B,N,D_node], the same in the node stream's activation format (what the trunk's first projections and every
         skip_embed read), edge_embed [B,N,N,D_edge], projections or None (reference :107-159; ``edge_layout`` "tiled": as an
-        ``ops.PairTiled`` for the trunk's f16x3 pair kernels, arithmetic "f16x3" only).  ``t`` may live on
+        ``ops.PairTiled`` for the trunk's f16x3 pair kernels, arithmetic "f16x3" only; "by_class": as an ``ops.PairByClass`` where the
+        call takes the class path and ``next_proj`` is given, "tiled" otherwise).  ``t`` may live on
         the host (the sampler knows it there): its embedding is then computed on the host and uploaded.
         ``node_mask`` optionally fuses DenoisingNet's mask multiplies (reference :186-187); ``next_proj`` (packed
         pair-projection weights of the first IPA block) makes the last value the block's (attn_bias, pair_z)."""
@@ -256,6 +262,8 @@ class EmbeddingModule(nn.Module):
             by_class = cls is not None and ops.edge_embed_classes_eligible(
                 self.ee_classes, self.arith, single_t and not per_sample, cls["n_fixed"], self._mask_is_01(node_mask), rel_cb.shape[1],
                 w["bin_tab_cb"].shape[1], B, L)
+            if edge_layout == "by_class" and not (by_class and next_proj is not None):
+                edge_layout = "tiled"
             if by_class:
                 # the two operand rows per fixed-mask value, by the launch that made the chunk's: the same sums, the same floats
                 _, node_a2, node_b2 = torch.ops.str2str_amd.embed_assemble(img.contiguous(), cls["nc2"], cls["fa2"], cls["fb2"], 1,
@@ -321,7 +329,7 @@ class DenoisingNet(nn.Module):
         node_embed, node_act, edge_embed, first_proj = self.embedder.embed(
             residue_idx=batch["residue_idx"], t=batch["t"], fixed_mask=fixed_mask, self_conditioning_ca=batch["sc_ca_t"], node_mask=node_mask,
             t_emb=batch.get("t_emb"), t_img=batch.get("t_img"), next_proj=self.translator.trunk["ipa_0"].pair_proj_weights() if fuse else None,
-            **({"edge_layout": "tiled"} if tiled else {}))
+            **({"edge_layout": "by_class" if getattr(self.embedder, "et_by_class", "0") != "0" else "tiled"} if tiled else {}))
         tb = dict(batch)
         tb["residue_mask"], tb["fixed_mask"] = node_mask, fixed_mask
         tb["rigids_t"] = batch["rigids_t"].to(dev)

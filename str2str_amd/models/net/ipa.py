@@ -320,6 +320,11 @@ class TranslationIPA(nn.Module):
         init7 = batch["rigids_t"].type(torch.float).contiguous()
         curr7 = torch.ops.str2str_amd.rigid_scale_trans(init7, self.coordinate_scaling, False)
         proj = _first_proj
+        # the embedding's pair tensor by class has ONE reader that takes it as it is: an f16x3 EdgeTransition 0 with the fused projection.
+        # Whatever else comes first -- the unfused pair_project, the exact kernel -- gets the materialised tensor, here and nowhere else
+        if isinstance(edge_embed, ops.PairByClass) and not (_first_proj is not None and self.fuse_pair_projection and self.num_blocks > 1
+                                                             and T["edge_transition_0"].arith == "f16x3"):
+            edge_embed = ops.pair_untiled(edge_embed)
 
         def lin(x, w, **kw):
             return ops.node_apply(x, w, M, **kw)

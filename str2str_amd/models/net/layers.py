@@ -229,10 +229,13 @@ class EdgeTransition(nn.Module):
     def pair_mlp(self, edge_embed, node_ab, n_p, edge_mask_1d=None, next_proj=None, out_layout: str = "rowmajor", ab_kernel_form: bool = False):
         """The N x N part given the per-node vectors n' = initial_embed(node) [B,N,128] and
         node_ab = [W1[:,128:256] n' + b1 | W1[:,256:] n' | Wf[:,256:] n' + bf] [B,N,896] (``node_parts``).  Arithmetic "f16x3" only: ``edge_embed`` may be
-        an ``ops.PairTiled`` and ``out_layout`` "tiled" / "none" (ops.edge_transition_f16x3) -- how the trunk chains its pair kernels."""
+        an ``ops.PairTiled`` and ``out_layout`` "tiled" / "none" (ops.edge_transition_f16x3) -- how the trunk chains its pair kernels -- or the
+        embedding's ``ops.PairByClass``, which the kernel reads by class when the projection is fused and which is materialised otherwise."""
         if self._shape != (128, 128, 384, 128, 2):
             raise ops.HipLibraryError(f"EdgeTransition kernel is built for c_z=128, c_s=256 (got {self._shape})")
         mask = None if edge_mask_1d is None else edge_mask_1d.type(torch.float32).contiguous()
+        if isinstance(edge_embed, ops.PairByClass) and not (self.arith == "f16x3" and next_proj is not None):
+            edge_embed = ops.pair_untiled(edge_embed)   # only the f16x3 kernel with the fused projection reads by class
         if self.arith == "f16x3":
             pk = self._packed()
             proj = None
@@ -240,13 +243,13 @@ class EdgeTransition(nn.Module):
                 stream = self._proj_cache.get([pk["wstream_f16"], next_proj["wp_f16x2"]],
                                               lambda: torch.cat([pk["wstream_f16"], next_proj["wp_f16x2"]]))
                 proj = (stream, next_proj["b64"])
-            tiled_in = isinstance(edge_embed, ops.PairTiled)
+            tiled_in, cls_in = isinstance(edge_embed, ops.PairTiled), isinstance(edge_embed, ops.PairByClass)
             B, N = edge_embed.shape[0], edge_embed.shape[1]
             z, bias, pz = torch.ops.str2str_amd.edge_transition_f16x3_chain(
-                edge_embed.buf if tiled_in else edge_embed.contiguous(), tiled_in, B, N, node_ab, n_p,
+                edge_embed.buf if tiled_in or cls_in else edge_embed.contiguous(), tiled_in, B, N, node_ab, n_p,
                 pk["wstream_f16"] if proj is None else proj[0], self.trunk[2].bias, self.layer_norm.weight,
                 self.layer_norm.bias, mask, self.layer_norm.eps, None if proj is None else proj[1], out_layout, int(self.prescale_exp),
-                bool(ab_kernel_form))
+                bool(ab_kernel_form), **({"in_rec": edge_embed.rec} if cls_in else {}))
             if out_layout == "tiled":
                 z = ops.PairTiled(B, N, buf=z)
             return z if proj is None else (z, bias, pz)

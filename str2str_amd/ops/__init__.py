@@ -18,7 +18,7 @@ from .hostio import (float64_normal_outputs, format_pdb_models, host_rng_can_dis
 from .node import (CHAIN_WIDTHS, NARROW_MAX_WORK, SMALL_ROWS, embed_assemble, ipa_projections, node_apply,
                    node_apply_chain, node_apply_multi, node_chain, node_linear, node_linear_f32, node_linear_multi, node_linear_vfrag,
                    pack_planes, row_layernorm, small_rows_variant, to_act)
-from .packing import (NODE_TG, LazyDict, PairTiled, act_alloc, column_blocked, fragment_order, node_tiles, pack_f16x2_layer, pack_f16x3_embed_stream,
+from .packing import (NODE_TG, LazyDict, PairByClass, PairTiled, act_alloc, column_blocked, fragment_order, node_tiles, pack_f16x2_layer, pack_f16x3_embed_stream,
                       pack_f16x3_stream, pack_node_layer, pack_node_weight, pack_node_weight_f32, pack_weight, padded_len, pair_tiled,
                       pair_untiled, unpack_planes, vf_alloc, xp_alloc)
 from .pair import (EE_CLASS_R, edge_embed, edge_embed_class_of_row, edge_embed_class_row, edge_embed_class_rows, edge_embed_classes_eligible,
@@ -30,7 +30,7 @@ from .torch_ops import register_torch_ops
 __all__ = [
     "ABI_VERSION", "EXPORTS", "LIB_PATH", "HipLibraryError", "KernelTimer", "WeightRangeError", "load_library",
     "RANGE_BITS", "RANGE_FAMILIES", "range_families", "range_flag", "range_flag_names", "range_flag_read", "range_flag_reset", "range_headroom",
-    "NODE_TG", "LazyDict", "PairTiled", "act_alloc", "column_blocked", "fragment_order", "node_tiles", "pack_f16x2_layer", "pack_f16x3_embed_stream",
+    "NODE_TG", "LazyDict", "PairByClass", "PairTiled", "act_alloc", "column_blocked", "fragment_order", "node_tiles", "pack_f16x2_layer", "pack_f16x3_embed_stream",
     "pack_f16x3_stream", "pack_node_layer", "pack_node_weight", "pack_node_weight_f32", "pack_weight", "padded_len", "pair_tiled", "pair_untiled",
     "unpack_planes", "vf_alloc", "xp_alloc",
     "edge_embed", "edge_embed_f16x3", "edge_transition", "edge_transition_f16x3", "pair_project",

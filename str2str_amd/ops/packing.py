@@ -109,6 +109,38 @@ class PairTiled:
         return self
 
 
+class PairByClass:
+    """The edge embedding's [B,N,N,128] pair tensor BY CLASS (include/str2str_hip.h, "Pair-tensor layouts"): not materialised, but one
+    flat fp32 buffer  [M32 int32 words: each pair's class row, -1 where the edge mask is zero | a zero record | the class table's records
+    of ``rec`` floats, z[128] first],  M32 = B N N rounded up to 32.  ``ops.edge_embed_classes_f16x3(out_layout="by_class")`` makes one
+    and the first ``edge_transition_f16x3`` reads it; ``expand`` (set by the producer) materialises the row-major tensor through the
+    expansion kernel for every other reader (``pair_untiled``)."""
+    __slots__ = ("buf", "B", "N", "rec", "expand")
+
+    def __init__(self, B: int, N: int, buf: torch.Tensor, rec: int, expand=None):
+        self.B, self.N, self.rec, self.buf, self.expand = int(B), int(N), int(rec), buf, expand
+        if self.rec not in (128, 168) or buf.dtype != torch.float32 or buf.ndim != 1 or not buf.is_contiguous() or (buf.numel() - self.M32) % self.rec:
+            raise HipLibraryError("PairByClass: buffer must be a flat contiguous fp32 tensor of M32 index words and records of 128 or 168 floats")
+
+    @staticmethod
+    def index_words(B: int, N: int) -> int:
+        """M32: the words in front of the records (one per pair, rounded up to 32: the records start 16-byte aligned)."""
+        return -(-(int(B) * int(N) * int(N)) // 32) * 32
+
+    M32 = property(lambda self: self.index_words(self.B, self.N))
+    shape = property(lambda self: (self.B, self.N, self.N, 128))
+    device = property(lambda self: self.buf.device)
+    is_cuda = property(lambda self: self.buf.is_cuda)
+    index = property(lambda self: self.buf[:self.B * self.N * self.N].view(torch.int32).view(self.B, self.N, self.N))   # class row or -1
+    records = property(lambda self: self.buf[self.M32:].view(-1, self.rec))                                             # record 0 = zeros, class r = record r + 1
+
+    def data_ptr(self):
+        return self.buf.data_ptr()
+
+    def contiguous(self):
+        return self
+
+
 def pair_tiled(z: torch.Tensor) -> PairTiled:
     """Row-major [B,N,N,128] -> tiled (plain torch; conversion is for callers and tests, the kernels produce the layout themselves)."""
     B, N = z.shape[0], z.shape[1]
@@ -120,7 +152,12 @@ def pair_tiled(z: torch.Tensor) -> PairTiled:
     return t
 
 
-def pair_untiled(t: PairTiled) -> torch.Tensor:
+def pair_untiled(t) -> torch.Tensor:
+    """``PairTiled`` -> row-major (plain torch), ``PairByClass`` -> row-major through the expansion kernel of its producer."""
+    if isinstance(t, PairByClass):
+        if t.expand is None:
+            raise HipLibraryError("pair_untiled: this PairByClass does not come from edge_embed_classes_f16x3 (no expansion to materialise it with)")
+        return t.expand()
     M = t.B * t.N * t.N
     return t.buf.view(-1, 16, 2, 32, 4).permute(0, 3, 1, 2, 4).reshape(-1, 128)[:M].reshape(t.B, t.N, t.N, 128).contiguous()
 

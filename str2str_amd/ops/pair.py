@@ -2,7 +2,7 @@
 import torch
 
 from .binding import HipLibraryError, _check, _p, _req, _req_all, _req_opt, _stream, _timed, load_library
-from .packing import PairTiled, column_blocked
+from .packing import PairByClass, PairTiled, column_blocked
 from .range_guard import range_flag
 
 
@@ -21,7 +21,8 @@ def edge_transition_f16x3(edge, node_ab, node_p, wstream, b2, gamma, beta, mask,
     """EdgeTransition on split-f16 MFMA (fp32-equivalent accuracy; csrc/pair_mlp_f16.hip); same contract as ``edge_transition``.
     ``proj`` = (31-stage stream = this layer's 30 stages (``pack_f16x3_stream``) + the next IPA block's projection stage
     (``pack_f16x2_layer``), bias64) also returns that block's (attn_bias [B,8,N,N], pair_z [B,N,N,32]).
-    ``edge`` may be a ``PairTiled``; ``out_layout``: "rowmajor" (the reference's tensor), "tiled" (-> ``PairTiled``) or "none" (the pair
+    ``edge`` may be a ``PairTiled``, or a ``PairByClass`` (the edge embedding's class table + one class index per pair: the kernel reads
+    each pair's row out of the table; only with ``proj``); ``out_layout``: "rowmajor" (the reference's tensor), "tiled" (-> ``PairTiled``) or "none" (the pair
     vectors are not written: only with ``proj``, for the last EdgeTransition of a trunk; returns None in their place).
     ``prescale_exp`` = e (0 .. 15): the kernel keeps its hidden activations as f16 planes of 2^-e x the value (a block exponent: exact,
     same speed) -- what the sampler sets when the range guard reports hidden activations of 2^15 and beyond.
@@ -33,7 +34,9 @@ def edge_transition_f16x3(edge, node_ab, node_p, wstream, b2, gamma, beta, mask,
     rounding); the kernel form must arrive centred, as ``EdgeTransition.node_layers`` produces it."""
     lib = load_library()
     B, N = edge.shape[0], edge.shape[1]
-    in_tiled = isinstance(edge, PairTiled)
+    in_tiled, in_cls = isinstance(edge, PairTiled), isinstance(edge, PairByClass)
+    if in_cls and proj is None:
+        raise HipLibraryError("edge_transition_f16x3: a PairByClass input needs the fused projection (proj); pair_untiled materialises it")
     if not 0 <= int(prescale_exp) <= 15:
         raise HipLibraryError(f"edge_transition_f16x3: prescale_exp {prescale_exp} outside 0 .. 15")
     # C ABI: node_ab = [2^-e (A_i + b1) | 2^5 B_j | 2^(5-e) G_j] -- the row half at the planes' scale, the column half and the final layer's
@@ -54,7 +57,7 @@ def edge_transition_f16x3(edge, node_ab, node_p, wstream, b2, gamma, beta, mask,
             node_ab[..., 768:] -= node_ab[..., 768:].mean(dim=-1, keepdim=True)
     if out_layout not in ("rowmajor", "tiled", "none") or (out_layout == "none" and proj is None):
         raise HipLibraryError(f"edge_transition_f16x3: out_layout {out_layout!r}" + (" needs proj" if out_layout == "none" else ""))
-    _req(edge.buf if in_tiled else edge, name="edge")
+    _req(edge.buf if in_tiled or in_cls else edge, name="edge")
     _req_all(node_ab=node_ab, node_p=node_p, b2=b2, gamma=gamma, beta=beta)
     pw, pb, pbias, ppz = _proj_outputs(proj, B, N, edge.device, torch.int16, "wstream")
     wstream = _req(wstream, torch.int16, "wstream") if proj is None else pw
@@ -69,9 +72,9 @@ def edge_transition_f16x3(edge, node_ab, node_p, wstream, b2, gamma, beta, mask,
         raise HipLibraryError("edge_transition: out may not alias edge")
     elif isinstance(out, PairTiled) != (out_layout == "tiled"):
         raise HipLibraryError("edge_transition_f16x3: out does not have the requested layout")
-    io = (1 if in_tiled else 0) | {"rowmajor": 0, "tiled": 2, "none": 4}[out_layout]
+    io = (1 if in_tiled else 0) | {"rowmajor": 0, "tiled": 2, "none": 4}[out_layout] | ((8 | (16 if edge.rec == 168 else 0)) if in_cls else 0)
     _check(_timed("s2s_edge_transition", lambda: lib.s2s_edge_transition_f16x3(
-        _p(edge.buf if in_tiled else edge), _p(node_ab), _p(node_p), _p(wstream), _p(b2), _p(gamma), _p(beta), _p(mask),
+        _p(edge.buf if in_tiled or in_cls else edge), _p(node_ab), _p(node_p), _p(wstream), _p(b2), _p(gamma), _p(beta), _p(mask),
         _p(out.buf if isinstance(out, PairTiled) else out), B, N, ln_eps, io, _p(pb), _p(pbias), _p(ppz), int(prescale_exp), _p(range_flag()),
         _stream())), "s2s_edge_transition_f16x3")
     return out if proj is None else (out, pbias, ppz)
@@ -192,6 +195,8 @@ def edge_embed_classes_f16x3(node_a2, node_b2, fixed_cls, rel_table, bin_table, 
                              mask, rel_offset: int, ln_eps=1e-5, out=None, proj=None, out_layout: str = "rowmajor"):
     """The edge embedding by class: ``edge_embed_f16x3``'s outputs (same return contract, bit for bit where the edge mask is non-zero)
     for a chunk that shares one timestep and has a 0/1 fixed mask and node mask -- the MLP once per class row, then a copy per pair.
+    ``out_layout`` "by_class": the pair tensor is NOT materialised -- a ``PairByClass`` (the table and one class index per pair) for
+    ``edge_transition_f16x3``; attn_bias and pair_z are written as in the other layouts.
     ``node_a2`` [n_fixed,128] / ``node_b2`` [32,n_fixed,4]: what ``embed_assemble`` gives for a pseudo-sample whose fixed mask runs over
     the n_fixed values present; ``fixed_cls`` [B,N] int32: each residue's index among them; tables column-blocked."""
     lib = load_library()
@@ -211,23 +216,42 @@ def edge_embed_classes_f16x3(node_a2, node_b2, fixed_cls, rel_table, bin_table, 
     if wstream.numel() * 2 != (5 if proj is not None else 4) * 32 * 1024:
         raise HipLibraryError("s2s_edge_embed_classes_f16x3: weight stream has the wrong number of stages")
     _req_opt(mask=mask)
-    if out_layout not in ("rowmajor", "tiled"):
-        raise HipLibraryError(f"edge_embed_classes_f16x3: out_layout {out_layout!r}")
-    tiled = out_layout == "tiled"
-    if out is None:
-        out = PairTiled(B, N, dev) if tiled else torch.empty(B, N, N, 128, device=dev, dtype=torch.float32)
-    elif isinstance(out, PairTiled) != tiled:
-        raise HipLibraryError("edge_embed_classes_f16x3: out does not have the requested layout")
-    table = torch.empty(rows, 168 if proj is not None else 128, device=dev, dtype=torch.float32)
+    if out_layout not in ("rowmajor", "tiled", "by_class") or (out_layout == "by_class" and out is not None):
+        raise HipLibraryError(f"edge_embed_classes_f16x3: out_layout {out_layout!r}" + (" takes no out" if out is not None else ""))
+    by_cls = out_layout == "by_class"
+
+    def pair_out(out, tiled):   # the materialised pair tensor of an expansion
+        if out is None:
+            out = PairTiled(B, N, dev) if tiled else torch.empty(B, N, N, 128, device=dev, dtype=torch.float32)
+        elif isinstance(out, PairTiled) != tiled:
+            raise HipLibraryError("edge_embed_classes_f16x3: out does not have the requested layout")
+        return out
+
+    def expand(z, mode, pbias, ppz):   # mode: s2s_edge_embed_expand's out_tiled (0 row-major, 1 tiled, 2 class indices)
+        return lib.s2s_edge_embed_expand(_p(table), _p(fixed_cls), _p(bin_lower), _p(residue_idx), _p(ca), _p(mask), _p(pb), _p(z), mode,
+                                         _p(pbias), _p(ppz), B, N, int(rel_offset), n_rel, n_bins, _stream())
+
+    if not by_cls:
+        out = pair_out(out, out_layout == "tiled")
+    # one buffer [M32 index words | zero record | table] by class (``PairByClass``), the table alone (M32 = 0, no zero record) otherwise
+    rec, m32 = 168 if proj is not None else 128, PairByClass.index_words(B, N) if by_cls else 0
+    buf = torch.empty(m32 + (rows + (1 if by_cls else 0)) * rec, device=dev, dtype=torch.float32)
+    table = buf[m32 + (rec if by_cls else 0):].view(rows, rec)
 
     def launch():   # both launches under one timer: the family's time is the table plus the expansion
         rc = lib.s2s_edge_embed_classes_f16x3(_p(node_a2), _p(node_b2), _p(rel_table), _p(bin_table), _p(wstream), _p(b2), _p(b3), _p(gamma),
                                               _p(beta), _p(table), n_fixed, n_rel, n_bins, ln_eps, _p(pb), _p(range_flag()), _stream())
-        return rc or lib.s2s_edge_embed_expand(_p(table), _p(fixed_cls), _p(bin_lower), _p(residue_idx), _p(ca), _p(mask), _p(pb),
-                                               _p(out.buf if tiled else out), 1 if tiled else 0, _p(pbias), _p(ppz), B, N, int(rel_offset),
-                                               n_rel, n_bins, _stream())
+        if by_cls:
+            buf[m32:m32 + rec].zero_()   # the zero record: what a masked pair's index + 1 points at
+        return rc or (expand(buf, 2, pbias, ppz) if by_cls else expand(out.buf if out_layout == "tiled" else out, 1 if out_layout == "tiled" else 0, pbias, ppz))
 
     _check(_timed("s2s_edge_embed", launch), "s2s_edge_embed_classes_f16x3 / s2s_edge_embed_expand")
+    if by_cls:
+        def materialise():   # the row-major tensor from the same table: z alone (the record size follows from the bias pointer)
+            z = pair_out(None, False)
+            _check(expand(z, 0, None, None), "s2s_edge_embed_expand")
+            return z
+        out = PairByClass(B, N, buf, rec, expand=materialise)
     return out if proj is None else (out, pbias, ppz)
 
 

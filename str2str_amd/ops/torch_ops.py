@@ -6,7 +6,7 @@ from .binding import _opt_int
 from .geometry import forward_marginal, frames_to_backbone, rigid_compose_update, rigid_scale_trans, se3_step, torsion_head
 from .node import (embed_assemble, ipa_projections, node_chain, node_linear, node_linear_f32, node_linear_multi, node_linear_vfrag, pack_planes,
                    row_layernorm)
-from .packing import PairTiled
+from .packing import PairByClass, PairTiled
 from .pair import edge_embed, edge_embed_classes_f16x3, edge_embed_f16x3, edge_transition, edge_transition_f16x3, pair_project
 
 _registered = False   # rebound by register_torch_ops: read it there only
@@ -33,11 +33,12 @@ def _op_node_linear_f32(x, wpk32, bias, n_rows, k_in, n_out, tiles, pre_scale=No
 
 
 def _op_edge_transition_f16x3_chain(edge, in_tiled, B, N, node_ab, node_p, wstream, b2, gamma, beta, mask, ln_eps, proj_bias64,
-                                    out_layout, prescale_exp=0, ab_kernel_form=False):
-    """The trunk's form of the edge transition: pair tensor in either layout (``edge`` = the flat tiled buffer when ``in_tiled``), the
+                                    out_layout, prescale_exp=0, ab_kernel_form=False, in_rec=0):
+    """The trunk's form of the edge transition: pair tensor in either layout (``edge`` = the flat tiled buffer when ``in_tiled``; the
+    flat buffer of a ``PairByClass`` with records of ``in_rec`` floats when that is not 0), the
     next IPA block's projections fused in when ``proj_bias64`` is given (``wstream`` is then the 31-stage stream).
     -> (pair tensor (row-major [B,N,N,128] | flat tiled buffer | None), attn_bias | None, pair_z | None)"""
-    e = PairTiled(B, N, buf=edge) if in_tiled else edge
+    e = PairByClass(B, N, edge, in_rec) if in_rec else (PairTiled(B, N, buf=edge) if in_tiled else edge)
     r = edge_transition_f16x3(e, node_ab, node_p, wstream, b2, gamma, beta, mask, ln_eps,
                               proj=None if proj_bias64 is None else (wstream, proj_bias64), out_layout=out_layout, prescale_exp=prescale_exp,
                               ab_kernel_form=ab_kernel_form)
@@ -54,7 +55,7 @@ _TORCH_OPS = {
         lambda e, nab, np_, ws, b2, g, b, m, eps, pe=0: edge_transition_f16x3(e, nab, np_, ws, b2, g, b, m, eps, prescale_exp=pe),
     "edge_transition_f16x3_chain(Tensor edge, bool in_tiled, int B, int N, Tensor node_ab, Tensor node_p, Tensor wstream, Tensor b2, "
     "Tensor gamma, Tensor beta, Tensor? mask, float ln_eps, Tensor? proj_bias64, str out_layout, int prescale_exp=0, "
-    "bool ab_kernel_form=False) -> (Tensor?, Tensor?, Tensor?)": _op_edge_transition_f16x3_chain,
+    "bool ab_kernel_form=False, int in_rec=0) -> (Tensor?, Tensor?, Tensor?)": _op_edge_transition_f16x3_chain,
     "edge_embed(Tensor node_a, Tensor node_b, Tensor rel_table, Tensor bin_table, Tensor bin_lower, Tensor residue_idx, Tensor ca, "
     "Tensor w2p, Tensor w3p, Tensor b2, Tensor b3, Tensor gamma, Tensor beta, Tensor? mask, int rel_offset, float ln_eps) -> Tensor":
         lambda *a: edge_embed(*a),
