@@ -25,7 +25,11 @@ the eigenproblem on the host) and writes ``dynamics_<tag>_<mmdd-HH-MM>.csv`` (th
 principal components, the RMSIP of the top ten, the mean absolute difference of the cross-correlation maps, the total variance of both)
 and the cross-correlations ``dynamics/<target>.csv``.
 ``+tica_backend=device`` computes the ``js_tica`` column with the time-lagged covariances and the projections on the device
-(metrics.js_tica(backend="device")); absent, the column is the reference's path.  Column name and file layout do not change."""
+(metrics.js_tica(backend="device")); absent, the column is the reference's path.  Column name and file layout do not change.
+``+msm=true`` (optional ``+msm_states=<k>``, default 100, and ``+msm_lag=<frames>``, default 20) also builds a Markov state model of the
+target ensemble (TICA, k-means microstates and transition counts on the device; the estimators on the host) and writes
+``msm_<tag>_<mmdd-HH-MM>.csv`` (the JS distance of the sampled ensemble's state populations from the target's, the number of active states,
+the three slowest implied timescales of the target) and the per-state populations ``msm/<target>.csv``."""
 import logging
 import os
 import sys
@@ -118,6 +122,31 @@ def tica_backend_switch(value) -> str:
     if isinstance(value, str) and value.strip().lower() in ("host", "device"):
         return value.strip().lower()
     raise ValueError(f"tica_backend {value!r}: expected host or device")
+
+
+MSM_COLUMNS = ("js_msm", "n_active", "timescale_1", "timescale_2", "timescale_3")
+MSM_STATES, MSM_LAG = 100, 20
+msm_switch = partial(_switch, "msm")
+
+
+def msm_row(ca, n_states=MSM_STATES, lagtime=MSM_LAG):
+    """-> (row {MSM_COLUMNS}, table {per state: the target's and the samples' populations and the target's stationary distribution, NaN
+    outside the active set}).  Fewer target frames than the lag time (or than the states): warned about, the row stays NaN."""
+    row, table = dict.fromkeys(MSM_COLUMNS, float("nan")), {}
+    try:
+        labels = metrics.msm_states(ca, ref_key="target", lagtime=lagtime, n_states=n_states)
+    except ValueError as e:
+        log.warning(f"msm: {e}")
+        return row, table
+    model = metrics.msm(labels["target"], n_states, lagtime)
+    slowest = list(model.timescales[:3]) + [float("nan")] * 3
+    row.update(js_msm=metrics.js_of_states(labels, n_states, "target")["pred"], n_active=int(len(model.active)),
+               timescale_1=slowest[0], timescale_2=slowest[1], timescale_3=slowest[2])
+    pi = np.full(n_states, np.nan)
+    pi[model.active] = model.stationary
+    table = {"state": np.arange(n_states), "population_target": metrics.state_populations(labels["target"], n_states),
+             "population_pred": metrics.state_populations(labels["pred"], n_states), "stationary_target": pi}
+    return row, table
 
 
 def _backbones(what, pred_file, target_file):
@@ -248,7 +277,8 @@ def _write_summary(output_dir, prefix, tag, rows, columns, mean_row):
 
 
 def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, extra_metrics=None, cluster_cutoff=None,
-                        secondary_structure=None, contacts=None, sasa=None, saxs=None, saxs_data=None, dynamics=None, tica_backend=None):
+                        secondary_structure=None, contacts=None, sasa=None, saxs=None, saxs_data=None, dynamics=None, tica_backend=None,
+                        msm=None, msm_states=None, msm_lag=None):
     """reference src/eval.py:47-99: one row per target, one column per metric, plus the mean row.  ``extra_metrics``: names out of
     EXTRA_METRICS, appended as columns after the reference's five (none by default: the file is then the reference's).
     ``cluster_cutoff`` (A; None: nothing of this happens): the ``pred`` ensemble of every target is clustered by ``metrics.cluster_rmsd``;
@@ -261,7 +291,10 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     surface and mean relative accessibility; ``saxs_...csv`` (SAXS_COLUMNS, and ``saxs_chi2`` against ``<saxs_data>/<target>.dat`` when
     the directory ``saxs_data`` is given) and ``saxs/<target>.csv`` the scattering summaries and the curves; ``dynamics_...csv``
     (DYNAMICS_COLUMNS) and ``dynamics/<target>.csv`` the essential-dynamics summaries and the cross-correlations.  All but the ss csv end
-    with the mean row.  ``tica_backend`` ("device"; None or "host": the reference's path) selects how the ``js_tica`` column is computed."""
+    with the mean row.  ``tica_backend`` ("device"; None or "host": the reference's path) selects how the ``js_tica`` column is computed.
+    ``msm`` (true; otherwise nothing of it happens): ``msm_row`` on every target with ``msm_states`` microstates (default MSM_STATES) at the
+    lag time ``msm_lag`` (default MSM_LAG); ``msm_...csv`` (MSM_COLUMNS, no mean row) and ``msm/<target>.csv`` receive the summaries and the
+    per-state populations."""
     columns = metric_columns(extra_metrics)
     tica_backend = tica_backend_switch(tica_backend)
     switches = dict(secondary_structure=secondary_structure, contacts=contacts, sasa=sasa, saxs=saxs, dynamics=dynamics)
@@ -270,6 +303,15 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
         raise ValueError(f"saxs_data {saxs_data}: needs saxs=true")
     if cluster_cutoff is not None and not 0.0 < float(cluster_cutoff) < float("inf"):
         raise ValueError(f"cluster_cutoff {cluster_cutoff}: expected a positive finite RMSD in Angstrom")
+    msm = msm_switch(msm)
+    msm_size = {"msm_states": MSM_STATES, "msm_lag": MSM_LAG}
+    for name, value in (("msm_states", msm_states), ("msm_lag", msm_lag)):
+        if value is not None:
+            if not msm:
+                raise ValueError(f"{name} {value}: needs msm=true")
+            if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+                raise ValueError(f"{name} {value!r}: expected an integer >= 1")
+            msm_size[name] = value
     from time import strftime
     from types import SimpleNamespace
 
@@ -290,7 +332,7 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
            "div_rmsd": metrics.diversity_rmsd, "div_tm": metrics.diversity_tm, "div_lddt": metrics.diversity_lddt}
     coverage = {"rmsd": metrics.coverage_rmsd, "tm": metrics.coverage_tm, "lddt": metrics.coverage_lddt}
     eval_res = {k: {} for k in columns}
-    clusters, rows = {}, {r.name: {} for r in reports}
+    clusters, rows, msm_rows = {}, {r.name: {} for r in reports}, {}
     for target in targets:
         pred_file, target_file = os.path.join(pred_dir, f"{target}.pdb"), os.path.join(target_dir, f"{target}.pdb")
         if not os.path.isfile(pred_file):
@@ -320,6 +362,10 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
             res = metrics.cluster_rmsd(ca["pred"], float(cluster_cutoff))
             select_pdb_models(pred_file, res.centres, os.path.join(output_dir, "clusters", f"{target}.pdb"))
             clusters[target] = cluster_summary(res.sizes)
+        if msm:
+            msm_rows[target], table = msm_row(ca, msm_size["msm_states"], msm_size["msm_lag"])
+            os.makedirs(os.path.join(output_dir, "msm"), exist_ok=True)
+            pd.DataFrame(table).to_csv(os.path.join(output_dir, "msm", f"{target}.csv"), index=False, sep="\t")
         files = SimpleNamespace(ca=ca, pred_file=pred_file, target_file=target_file,
                                 saxs_file=None if saxs_data is None else os.path.join(str(saxs_data), f"{target}.dat"))
         for r in reports:
@@ -331,6 +377,8 @@ def evaluate_prediction(pred_dir: str, target_dir: str = None, tag: str = None, 
     df.to_csv(os.path.join(output_dir, f"metrics_{tag}_{strftime('%m%d-%H-%M')}.csv"), index=True, sep="\t")
     if cluster_cutoff is not None:
         _write_summary(output_dir, "clusters", tag, clusters, CLUSTER_COLUMNS, False)
+    if msm:
+        _write_summary(output_dir, "msm", tag, msm_rows, MSM_COLUMNS, False)
     for r in reports:
         _write_summary(output_dir, r.prefix, tag, rows[r.name], r.columns + (("saxs_chi2",) if r.name == "saxs" and saxs_data is not None else ()), r.mean_row)
     return df.loc["mean"]
@@ -341,7 +389,7 @@ def evaluate(cfg):
     scoring = dict(target_dir=cfg.get("target_dir"), tag=cfg.get("task_name"), extra_metrics=cfg.get("extra_metrics"),
                    cluster_cutoff=cfg.get("cluster_cutoff"), secondary_structure=cfg.get("secondary_structure"),
                    contacts=cfg.get("contacts"), sasa=cfg.get("sasa"), saxs=cfg.get("saxs"), saxs_data=cfg.get("saxs_data"), dynamics=cfg.get("dynamics"),
-                   tica_backend=cfg.get("tica_backend"))
+                   tica_backend=cfg.get("tica_backend"), msm=cfg.get("msm"), msm_states=cfg.get("msm_states"), msm_lag=cfg.get("msm_lag"))
     if pred_dir and os.path.isdir(pred_dir):
         log.info(f"Found pre-computed prediction directory {pred_dir}.")
         return evaluate_prediction(pred_dir, **scoring)

@@ -35,6 +35,8 @@ UNITS = {
     "ensemble_tm.hip": [],     # (as above)
     "ensemble_pca.hip": [],    # (as above)
     "ensemble_tica.hip": [],   # (as above)
+    # k-means and transition counts (include/str2str_kinetics.h); contraction off: every squared distance is bit for bit the numpy yardstick's
+    "ensemble_kinetics.hip": ["-ffp-contract=off"],
     "ensemble_cluster.hip": [],   # integer and float64 comparisons only
     "ensemble_lddt.hip": [],      # float64 distances against squared bounds, integer sums
     # contraction off: the argument of the soft Q's exponential is then bit for bit the numpy yardstick's, so the a-priori bound of its
@@ -82,7 +84,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     cc = hipcc()
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
-        os.path.join(ROOT, "include", "str2str_hip.h"), os.path.abspath(__file__)]
+        os.path.join(ROOT, "include", "str2str_hip.h"), os.path.join(ROOT, "include", "str2str_kinetics.h"), os.path.abspath(__file__)]
 
     def compile_one(item):
         src, extra = item

@@ -38,7 +38,10 @@ eigenproblem stays on the host), with ``js_pca``, ``rmsip``, ``dccm_mae`` and ``
 global superposition, CA only, no quasi-harmonic entropy.  Which coordinates are slow: ``tica`` and ``tica_project``
 (csrc/ensemble_tica.hip: the reversible mean and the time-lagged covariances of any feature trajectory and the projections in float64 on
 the device; the two eigenproblems stay on the host) give the components, eigenvalues and implied timescales behind ``js_tica``, whose
-``backend="device"`` runs on them -- no weights in the fit, no VAMP score.
+``backend="device"`` runs on them -- no weights in the fit, no VAMP score.  Which states, and how fast between them: ``kmeans``,
+``assign_states``, ``msm``, ``state_populations`` and ``js_msm`` (csrc/ensemble_kinetics.hip: nearest centre, Lloyd update, farthest-point
+seeding and transition counts on the device; the k x k estimators stay on the host) -- no PCCA+, no Bayesian errors, no k-means++ or
+mini-batches, no relocation of empty clusters, no weights in the fit, at most 64 dimensions.
 """
 from __future__ import annotations
 
@@ -289,6 +292,220 @@ def _js_tica_tail(ca_dr2d, ref_key, n_bins, w, return_tic):
     if return_tic:
         return results, ca_dr2d
     return results
+
+
+# ---- Markov state models: k-means microstates of the slow coordinates, transition counts, populations and timescales ------------------
+class EnsembleKMeans(NamedTuple):
+    """Microstates of a feature space [T, d]: ``centres`` [k, d] float64, ``labels`` [T] int32 (the nearest centre of every row, the
+    lowest index on ties), ``counts`` [k] (the rows of every state), ``inertia`` (the sum of the squared distances to the nearest
+    centre), ``n_iter`` (the assignments that were run) and ``converged`` (the last assignment changed no label).  The labels are those
+    of the last assignment and the centres the ones they were assigned against."""
+    centres: np.ndarray
+    labels: np.ndarray
+    counts: np.ndarray
+    inertia: float
+    n_iter: int
+    converged: bool
+
+
+class EnsembleMSM(NamedTuple):
+    """A Markov state model at ``lagtime``: ``counts`` [k, k] int64 (all states), ``active`` (the states of the largest strongly
+    connected set, ascending), and on the active set ``transition_matrix`` [n, n], ``stationary`` [n], ``eigenvalues`` [n] (real, by
+    descending magnitude; the first is 1) and ``timescales`` [n - 1] (-lagtime / ln |eigenvalue| of the second eigenvalue on, in frames;
+    inf for |eigenvalue| >= 1).  ``converged``: the reversible estimate met its tolerance (always True for the row-normalised one)."""
+    counts: np.ndarray
+    active: np.ndarray
+    transition_matrix: np.ndarray
+    stationary: np.ndarray
+    eigenvalues: np.ndarray
+    timescales: np.ndarray
+    lagtime: int
+    converged: bool
+
+
+def _count(fn, name, v, lo=1) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+        raise ValueError(f"{fn}: {name} must be an integer >= {lo}, got {v!r}")
+    return int(v)
+
+
+def _feature_rows(fn, x) -> torch.Tensor:
+    """Feature rows [T, d] (array or tensor, any device) -> float64 device tensor."""
+    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{fn}: expected features [T, d], got {tuple(t.shape)}")
+    if t.shape[1] > ops.KINETICS_MAX_DIM:
+        raise ValueError(f"{fn}: at most {ops.KINETICS_MAX_DIM} dimensions, got {t.shape[1]}: reduce first (tica_project, pca_project)")
+    return t.to("cuda", torch.float64).contiguous()
+
+
+def kmeans(features, n_states, init="farthest", first=0, max_iter=100, max_centres=None) -> EnsembleKMeans:
+    """Which microstates does an ensemble visit?  Lloyd's k-means of feature rows [T, d <= 64] (``tica_project`` or ``pca_project`` output,
+    typically) on the device (csrc/ensemble_kinetics.hip).  ``init``: "farthest" (row ``first``, then repeatedly the row farthest from the
+    chosen ones: deterministic, no random numbers) or an array [n_states, d] of centres.  The loop is assign, then update, until an
+    assignment changes no label (an integer criterion: the device's counter of changed labels, no float tolerance) or ``max_iter``
+    assignments have run.  Squared float64 distances, the lowest index on ties; the update sums in a fixed order, so a run is
+    reproducible bit for bit; a state that loses all its rows keeps its centre (no relocation).  ``max_centres`` bounds the centres
+    per LDS tile and changes no bit.  No k-means++, no mini-batches, no weights."""
+    fn = "kmeans"
+    k, max_iter = _count(fn, "n_states", n_states), _count(fn, "max_iter", max_iter)
+    if k > ops.KINETICS_MAX_CENTRES:
+        raise ValueError(f"{fn}: at most {ops.KINETICS_MAX_CENTRES} states, got {k}")
+    if isinstance(init, str) and init != "farthest":
+        raise ValueError(f"{fn}: init must be 'farthest' or an array of centres, got {init!r}")
+    x = _feature_rows(fn, features)
+    T, d = x.shape
+    if isinstance(init, str):
+        if k > T:
+            raise ValueError(f"{fn}: {k} states out of {T} frames")
+        centres = ops.farthest_points(x, k, _count(fn, "first", first, 0))[1]
+    else:
+        centres = (init if torch.is_tensor(init) else torch.as_tensor(np.asarray(init))).to("cuda", torch.float64).contiguous().clone()
+        if centres.shape != (k, d):
+            raise ValueError(f"{fn}: init {tuple(centres.shape)}, expected [{k}, {d}]")
+    prev, converged = None, False
+    for n_iter in range(1, max_iter + 1):
+        labels, dist2, changed = ops.kmeans_assign(x, centres, prev, max_centres)
+        if changed is not None and int(changed.item()) == 0:
+            converged = True
+            break
+        if n_iter < max_iter:
+            ops.kmeans_update(x, labels, centres)
+            prev = labels
+    lab = labels.cpu().numpy()
+    return EnsembleKMeans(centres.cpu().numpy(), lab, np.bincount(lab, minlength=k), float(dist2.cpu().numpy().sum()), n_iter, converged)
+
+
+def assign_states(features, model_or_centres) -> np.ndarray:
+    """The state of every feature row [R, d] of any ensemble: the nearest centre of an ``EnsembleKMeans`` (or of an array [k, d]), the
+    rule of ``kmeans`` -> int32 [R]."""
+    x = _feature_rows("assign_states", features)
+    c = model_or_centres.centres if isinstance(model_or_centres, EnsembleKMeans) else model_or_centres
+    c = (c if torch.is_tensor(c) else torch.as_tensor(np.asarray(c))).to("cuda", torch.float64).contiguous()
+    if c.ndim != 2 or c.shape[1] != x.shape[1]:
+        raise ValueError(f"assign_states: centres {tuple(c.shape)} for features {tuple(x.shape)}")
+    return ops.kmeans_assign(x, c)[0].cpu().numpy()
+
+
+def state_populations(labels, n_states, weights=None) -> np.ndarray:
+    """The (weighted) fraction of an ensemble in every state -> float64 [n_states]; a negative label is unassigned."""
+    lab = np.asarray(labels)
+    w = np.ones(len(lab)) if weights is None else np.asarray(weights, dtype=np.float64)
+    if w.shape != lab.shape:
+        raise ValueError(f"state_populations: weights {w.shape} for {lab.shape} labels")
+    keep = (lab >= 0) & (lab < n_states)
+    hist = np.bincount(lab[keep], weights=w[keep], minlength=int(n_states))
+    return hist / hist.sum()
+
+
+def _active_set(counts: np.ndarray) -> np.ndarray:
+    """The largest strongly connected set of the graph counts > 0; on a size tie the set that holds the lowest state."""
+    from scipy.sparse import csr_matrix
+    from scipy.sparse.csgraph import connected_components
+
+    _, comp = connected_components(csr_matrix(counts > 0), directed=True, connection="strong")
+    sizes = np.bincount(comp)
+    lowest = np.array([np.flatnonzero(comp == c)[0] for c in range(len(sizes))])
+    best = min(range(len(sizes)), key=lambda c: (-sizes[c], lowest[c]))
+    return np.flatnonzero(comp == best)
+
+
+def _reversible_mle(c: np.ndarray, tol: float, max_iter: int):
+    """The reversible maximum-likelihood estimate of a count matrix on a strongly connected set: the fixed point of
+    x_ij <- (c_ij + c_ji) / (c_i / x_i + c_j / x_j) (c_i, x_i: row sums) from x = C + C^T, until the relative residual
+    |x_ij (c_i / x_i + c_j / x_j) - (c_ij + c_ji)| / (c_ij + c_ji) is at most ``tol`` wherever c_ij + c_ji > 0.
+    -> (transition matrix x_ij / x_i, stationary x_i / sum x, converged)."""
+    c = np.asarray(c, dtype=np.float64)
+    s, ci = c + c.T, c.sum(1)
+    x, pair = s.copy(), s > 0
+    converged = False
+    for _ in range(int(max_iter)):
+        q = ci / x.sum(1)
+        denom = q[:, None] + q[None, :]
+        if (np.abs(x * denom - s)[pair] <= tol * s[pair]).all():
+            converged = True
+            break
+        x = np.where(pair, s / np.where(pair, denom, 1.0), 0.0)
+    xi = x.sum(1)
+    return x / xi[:, None], xi / xi.sum(), converged
+
+
+def _msm_tail(counts: np.ndarray, lagtime: int, reversible: bool, tol: float, max_iter: int) -> EnsembleMSM:
+    """The k x k host tail of ``msm`` on the count matrix."""
+    active = _active_set(counts)
+    c = counts[np.ix_(active, active)].astype(np.float64)
+    if len(active) == 1 and c[0, 0] == 0:      # no transition was counted at all
+        t, pi, converged = np.ones((1, 1)), np.ones(1), True
+    elif reversible:
+        t, pi, converged = _reversible_mle(c, tol, max_iter)
+    else:
+        t, converged = c / c.sum(1)[:, None], True
+        w, v = np.linalg.eig(t.T)
+        pi = np.abs(np.real(v[:, np.argmin(np.abs(w - 1.0))]))
+        pi = pi / pi.sum()
+    root = np.sqrt(pi)
+    sym = root[:, None] * t / root[None, :]
+    lam = np.linalg.eigvalsh(0.5 * (sym + sym.T))
+    lam = lam[np.argsort(-np.abs(lam), kind="stable")]
+    mag = np.abs(lam[1:])
+    timescales = np.full(mag.shape, np.inf)
+    with np.errstate(divide="ignore"):
+        timescales[mag < 1.0] = np.abs(-float(lagtime) / np.log(mag[mag < 1.0]))     # (an eigenvalue 0: timescale 0)
+    return EnsembleMSM(counts, active, t, pi, lam, timescales, int(lagtime), bool(converged))
+
+
+def msm(labels, n_states, lagtime, lengths=None, reversible=True, tol=1e-12, max_iter=100000) -> EnsembleMSM:
+    """A Markov state model of labelled trajectories: ``labels`` [T] (states 0 .. n_states - 1 in time order, a negative label is
+    unassigned; several trajectories laid end to end with their ``lengths``).  The sliding-window counts of the pairs (t, t + lagtime)
+    run on the device; the n_states x n_states tail runs on the host: the largest strongly connected set (the set with the lowest state
+    on a size tie), then the row-normalised counts or (``reversible``) the reversible maximum-likelihood estimate (``_reversible_mle``:
+    its fixed-point iteration to the relative residual ``tol``, at most ``max_iter`` rounds), the stationary distribution, the real
+    spectrum of the symmetrised matrix and the implied timescales.  No coarse-graining (PCCA+), no Bayesian errors."""
+    fn = "msm"
+    k, lag = _count(fn, "n_states", n_states), _count(fn, "lagtime", lagtime)
+    lab = torch.as_tensor(np.asarray(labels.cpu() if torch.is_tensor(labels) else labels))
+    if lab.ndim != 1 or lab.shape[0] < 1:
+        raise ValueError(f"{fn}: expected labels [T], got {tuple(lab.shape)}")
+    lens = None
+    if lengths is not None:
+        lens = np.asarray(lengths, dtype=np.int64)
+        if lens.ndim != 1 or len(lens) < 1 or (lens < 0).any() or lens.sum() != lab.shape[0]:
+            raise ValueError(f"{fn}: lengths {lens.tolist()} do not sum to the {lab.shape[0]} labels")
+        lens = torch.as_tensor(lens).to("cuda", torch.int32)
+    counts = ops.transition_counts(lab.to("cuda", torch.int32).contiguous(), k, lag, lens).cpu().numpy()
+    return _msm_tail(counts, lag, bool(reversible), float(tol), int(max_iter))
+
+
+def js_msm(ca_coords_dict, ref_key="target", lagtime=20, n_states=100, dim=4, weights=None, return_model=False):
+    """Does a sampled ensemble populate the metastable states of the reference?  ``tica(reference, lagtime, dim)`` on the time-ordered
+    reference, ``kmeans`` with ``n_states`` microstates on its projection; every ensemble, the reference included, then goes through
+    ``tica_project`` and ``assign_states``, and its state histogram (per-sample ``weights`` by key, PSEUDO_C added) is compared with the
+    reference's by the Jensen-Shannon distance -> {key: distance rounded to 4 decimals, the reference 0.0}; with ``return_model`` also the
+    ``EnsembleMSM`` of the reference's labels at ``lagtime``.  Only the reference needs time order.  Where the marginals of ``js_tica``
+    cannot tell two basins that overlap in every coordinate from one, the states can."""
+    labels = msm_states(ca_coords_dict, ref_key, lagtime, n_states, dim)
+    results = js_of_states(labels, n_states, ref_key, weights)
+    if return_model:
+        return results, msm(labels[ref_key], n_states, lagtime)
+    return results
+
+
+def msm_states(ca_coords_dict, ref_key="target", lagtime=20, n_states=100, dim=4):
+    """The first half of ``js_msm``: {key: coordinates or features} -> {key: int32 [R_k], the microstate of every structure}, the states
+    being the k-means states of the reference's TICA projection."""
+    k = _count("js_msm", "n_states", n_states)
+    model = tica(ca_coords_dict[ref_key], lagtime, dim=dim)
+    proj = {key: tica_project(v, model) for key, v in ca_coords_dict.items()}
+    if k > len(proj[ref_key]):
+        raise ValueError(f"js_msm: {k} states out of {len(proj[ref_key])} reference frames")
+    states = kmeans(proj[ref_key], k)
+    return {key: assign_states(p, states) for key, p in proj.items()}
+
+
+def js_of_states(labels, n_states, ref_key="target", weights=None):
+    """The second half of ``js_msm``: {key: state labels} -> {key: JS distance of the (weighted) state histogram from the reference's}."""
+    w = _weights(weights, labels)
+    return js_of_histograms({key: np.bincount(lab, weights=w[key], minlength=int(n_states)) + PSEUDO_C for key, lab in labels.items()}, ref_key)
 
 
 # ---- pair scores: RMSD, TM-score and lDDT as one family ------------------------------------------------------------------------------

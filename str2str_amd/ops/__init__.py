@@ -6,12 +6,14 @@ op raises.  The ops are also registered as ``torch.ops.str2str_amd.*`` custom op
 The names below are the objects of the submodules themselves; module state that is rebound (the library handle, the host-RNG
 verdict, the registration flag) stays in its module and is reached through that module's functions."""
 from .attention import encoder_attention, ipa_attention, ipa_attention_f16, ipa_prep_points, ipa_prep_points_f16
-from .binding import ABI_VERSION, EXPORTS, LIB_PATH, HipLibraryError, KernelTimer, WeightRangeError, load_library
+from .binding import (ABI_VERSION, EXPORTS, KINETICS_ABI_VERSION, KINETICS_EXPORTS, LIB_PATH, HipLibraryError, KernelTimer, WeightRangeError,
+                      load_library)
 from .ensemble import (CLUSTER_MAX_N, CONTACT_MAX_RES, LDDT_MAX_RES, PCA_MAX_RES, RMSD_LAUNCH_PAIRS, SASA_MAX_POINTS, SASA_MAX_RES, SAXS_MAX_Q, SAXS_MAX_RES,
                        SAXS_MAX_TYPES, SS_MAX_RES, TM_MAX_RES, VIOL_MAX_RES, apply_xform, backbone_sasa, backbone_violations, ca_aligned_mean, ca_contact_map, ca_covariance, ca_fit_transforms, ca_project, ca_contact_stats, ca_lddt_matrix, ca_native_contacts, ca_native_q, ca_lddt_per_residue, ca_pairwise_distances, ca_pwd_js, ca_rmsd_matrix,
                        ca_sample_stats, ca_scattering, ca_superpose, ca_tm_matrix, ca_tm_superpose, cluster_adjacency, cluster_gromos,
                        lddt_workspace_bytes, rmsd_row_chunk, secondary_structure, sphere_points,
                        TICA_MAX_FEATURES, feature_project, lagged_covariances, lagged_mean, tica_groups)
+from .kinetics import KINETICS_MAX_CENTRES, KINETICS_MAX_DIM, farthest_points, kmeans_assign, kmeans_update, transition_counts
 from .geometry import forward_marginal, frames_to_backbone, rigid_compose_update, rigid_scale_trans, se3_step, torsion_head
 from .hostio import (float64_normal_outputs, format_pdb_models, host_rng_can_discard, host_rng_discard_float64_normals,
                      host_rng_fast_forward_ok, merge_pdb_files, write_pdb_models)
@@ -51,6 +53,8 @@ __all__ = [
     "PCA_MAX_RES", "ca_aligned_mean", "ca_covariance", "ca_fit_transforms", "ca_project",
     "TICA_MAX_FEATURES", "feature_project", "lagged_covariances", "lagged_mean", "tica_groups",
     "CLUSTER_MAX_N", "cluster_adjacency", "cluster_gromos",
+    "KINETICS_ABI_VERSION", "KINETICS_EXPORTS", "KINETICS_MAX_CENTRES", "KINETICS_MAX_DIM", "farthest_points", "kmeans_assign", "kmeans_update",
+    "transition_counts",
     "float64_normal_outputs", "format_pdb_models", "host_rng_can_discard", "host_rng_discard_float64_normals", "host_rng_fast_forward_ok",
     "merge_pdb_files", "write_pdb_models",
     "register_torch_ops",

@@ -78,6 +78,17 @@ _SIGNATURES = {
 _LL_RETURN = ("s2s_format_pdb_models", "s2s_write_pdb_models", "s2s_merge_pdb_files")
 EXPORTS = tuple(_SIGNATURES)
 
+# The kinetics family (include/str2str_kinetics.h): the same library, a prefix, a table and a version of its own.
+KINETICS_ABI_VERSION = 1
+_KINETICS_SIGNATURES = {
+    "s2k_abi_version": [],
+    "s2k_assign": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "s2k_centre_update": [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _ll, _vp],
+    "s2k_farthest_point": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp],
+    "s2k_transition_counts": [_vp, _i, _vp, _i, _i, _i, _vp, _vp],
+}
+KINETICS_EXPORTS = tuple(_KINETICS_SIGNATURES)
+
 
 class HipLibraryError(RuntimeError):
     pass
@@ -143,9 +154,16 @@ def load_library(path: Optional[str] = None):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.argtypes = args
         fn.restype = ctypes.c_longlong if name in _LL_RETURN else ctypes.c_int
+    for name, args in _KINETICS_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = ctypes.c_int
     v = lib.s2s_abi_version()
     if v != ABI_VERSION:
         raise HipLibraryError(f"libstr2str_hip.so ABI {v} != expected {ABI_VERSION}; rebuild")
+    v = lib.s2k_abi_version()
+    if v != KINETICS_ABI_VERSION:
+        raise HipLibraryError(f"libstr2str_hip.so kinetics ABI {v} != expected {KINETICS_ABI_VERSION}; rebuild")
     if path is None:
         _lib = lib
     return lib
