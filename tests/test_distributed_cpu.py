@@ -274,7 +274,9 @@ def test_entry_points_start_their_own_ranks(tmp_path):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "who.py"
-    script.write_text("import os, sys\nprint('rank', os.environ['RANK'], 'of', os.environ['WORLD_SIZE'], 'addr', os.environ['MASTER_ADDR'], sys.argv[1:], flush=True)\n"
+    # (one write per rank: the ranks share a pipe, and the pieces of a several-argument print of an unbuffered stdout interleave)
+    script.write_text("import os, sys\nsys.stdout.write('rank %s of %s addr %s %s\\n' % (os.environ['RANK'], os.environ['WORLD_SIZE'], os.environ['MASTER_ADDR'], sys.argv[1:]))\n"
+                      "sys.stdout.flush()\n"
                       "sys.exit(3 if '--fail' in sys.argv and os.environ['RANK'] == '1' else 0)\n")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     code = "import sys; from str2str_amd.utils.launch import relaunch; sys.exit(relaunch(2, sys.argv[1], sys.argv[2:]))"

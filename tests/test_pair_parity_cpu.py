@@ -5,10 +5,17 @@
   * the families of tests/pair_cases.py have the properties they are named for, the shapes the tile arithmetic they were chosen for;
   * D32 -- the float32 chain's distance from float64 under the per-pair measure -- for every (family, level), recorded; below the
     cap for flat and offset, so the reference alone stays within it;
-  * the CPU emulation of the f16 planes meets 3 x D32 + F on every family at the shapes up to (2, 37), and on the small family
-    exceeds 3 x D32 alone: F is needed;
-  * every planted mistake exceeds the bound on some case.
+  * r16 -- the share of the a-priori floor F that the CPU emulation of the f16 planes uses -- for every (family, level), recorded and
+    at most 1 (F does bound the format);
+  * the emulation meets 3 x D32 + min(1, 3 x r16) x F on every family at the shapes up to (2, 37), and on the small family exceeds
+    3 x D32 alone: the F term is needed;
+  * every planted mistake exceeds the bound on some case; a low plane dropped (x_l, W_l) or its subnormals flushed in ANY ONE of the
+    eight layers of a module-level evaluation (n', A, B, G, layer 1, layer 2, final, projection) or of the four of a parts-level one
+    exceeds it at that level.  (Under 3 x D32 + F, the rule before r16, every one of them passed at the module level: the weakest
+    stage's error / bound under both rules is recorded.)
 """
+import functools
+
 import pytest
 import torch
 
@@ -114,9 +121,24 @@ def test_d32_is_recorded_and_below_the_cap_where_capped(family):
                 assert d[o] < NC.CAP, (family, level, o, d[o])
 
 
-def _emulation(c, flags=()):
-    kw = {k: True for k in flags}
-    return dict(L=RN.f16x3_layer(**kw), L_hidden=RP.scaled_planes_layer(c["exp"], **kw) if c["exp"] else None)
+@pytest.mark.parametrize("family", PC.FAMILIES)
+def test_r16_is_recorded_and_at_most_one(family):
+    """r16 = the largest error / F of the plane emulation (three plane products accumulated in float64: the format's loss alone):
+    F is an a-priori bound of exactly that, so r16 <= 1; the bound rule takes min(1, 3 x r16) of F."""
+    for level in PC.levels(family):
+        r = PC.r16(family, level)
+        for o in PC.OUTPUTS:
+            print(f"pair r16 {family} {level} {o}: {r[o]:.3e} (share of F in the bound: {PC.floor_share(family, level, o):.3e})")
+            record_margin(f"pair r16 (plane emulation's error / F): {family} {level} {o}", r[o], 1.0)
+            assert 0.0 < r[o] <= 1.0, (family, level, o, r[o])
+
+
+def test_embed_r16_is_recorded_and_at_most_one():
+    """The same share for the edge embedding's last two layers (pair_cases.embed_r16), whose bound takes min(1, 3 x r16) of their F."""
+    r = PC.embed_r16()
+    print(f"pair r16 edge embedding, offset rows: {r:.3e}")
+    record_margin("pair r16 (plane emulation's error / F): edge embedding, offset rows", r, 1.0)
+    assert 0.0 < r <= 1.0, r
 
 
 @pytest.mark.parametrize("family", PC.FAMILIES)
@@ -125,8 +147,7 @@ def test_emulated_planes_meet_the_bound(family):
     for level in PC.levels(family):
         d = PC.d32(family, level)
         for shape in PC.SMALL_SHAPES:
-            c = PC.case(family, shape)
-            out, proj, _ = PC.run(c, level, **_emulation(c))
+            out, proj = PC.emulated(family, shape, level)
             traces = PC.ref(family, shape, level)[2]
             for o, got in (("out", out), ("proj", proj)):
                 a, b, r, exact = PC.check(got, traces, o, family, d[o])
@@ -167,29 +188,82 @@ MISTAKES = {"ij_swapped": (("flat",), dict(wrong="ij_swapped")),
             "plain_mean_float32": (("offset-G", "offset-W"), dict(dtype=torch.float32, L=_plain_mean_layer)),
             "attn_bias_pair_major": (("flat",), dict(wrong="attn_bias_pair_major")),
             "projection_of_unmasked_row": (("masked",), dict(wrong="projection_of_unmasked_row")),
+            "x_l_dropped": (("flat", "trained-like"), "drop_xl"),
             "w_l_dropped": (("flat", "trained-like"), "drop_wl"),
             "low_plane_subnormals_flushed": (("small",), "flush_subnormals"),
             "ragged_last_pair_from_neighbour": (("flat",), dict(wrong="ragged_last_pair_from_neighbour"))}
+PLANE_MISTAKES = tuple(m for m, (_, how) in MISTAKES.items() if isinstance(how, str))
+MISTAKE_SHAPES = ((3, 7), (2, 37))
 
 
 @pytest.mark.parametrize("mistake", list(MISTAKES))
 def test_planted_mistake_exceeds_the_bound(mistake):
+    """The mistake in every layer it can be made in.  A plane mistake must show in every family it is looked for in at BOTH levels (a
+    hit at the parts level says nothing about the module level, whose F starts four layers earlier)."""
     families, how = MISTAKES[mistake]
     hits = []
     for family in families:
         for level in PC.levels(family):
             d = PC.d32(family, level)
-            for shape in ((3, 7), (2, 37)):
+            n0 = len(hits)
+            for shape in MISTAKE_SHAPES:
                 c = PC.case(family, shape)
-                kw = _emulation(c, (how,)) if isinstance(how, str) else how
+                kw = PC.emulation(c, level, (how,)) if isinstance(how, str) else how
                 out, proj, _ = PC.run(c, level, **kw)
                 traces = PC.ref(family, shape, level)[2]
                 for o, got in (("out", out), ("proj", proj)):
                     a, b, r, exact = PC.check(got, traces, o, family, d[o], arith="f16x3" if isinstance(how, str) else "f32")
                     if not (a < b and exact):
                         hits.append((family, level, shape, o, a, b))
+            assert len(hits) > n0 or not isinstance(how, str), (mistake, family, level, "passes the bound")
     print(mistake, len(hits), hits[:3])
     assert hits
+
+
+@functools.lru_cache(maxsize=None)
+def _one_layer_ratio(mistake, family, level, stage):
+    """{rule: the largest error / bound over MISTAKE_SHAPES and both outputs} of the plane emulation with ``mistake`` in layer ``stage``
+    alone, judged as the GPU tests judge a kernel ("measured"), and with the whole a-priori F as before r16 ("a-priori")."""
+    d, best = PC.d32(family, level), {"measured": 0.0, "a-priori": 0.0}
+    for shape in MISTAKE_SHAPES:
+        c = PC.case(family, shape)
+        out, proj, _ = PC.run(c, level, **PC.emulation(c, level, (MISTAKES[mistake][1],), stage))
+        traces = PC.ref(family, shape, level)[2]
+        for o, got in (("out", out), ("proj", proj)):
+            for rule in best:
+                j = PC.judged(got, traces, o, family, d[o], rule=rule)
+                best[rule] = max(best[rule], j["achieved"] / j["bound"])
+    return best
+
+
+@pytest.mark.parametrize("mistake, level, stage", [(m, lv, st) for m in PLANE_MISTAKES for lv in PC.LEVELS for st in PC.stages(lv)])
+def test_plane_mistake_in_one_layer_exceeds_the_bound(mistake, level, stage):
+    """A low plane lost in ONE layer (the realistic kernel mistake: one MFMA of one stage without its x_l or W_l operand, one
+    conversion that flushes) must leave the bound at the level it is made at, in every family it is looked for in, on (3, 7) or
+    (2, 37), in at least one output.  (exp10 is not among the families: its hidden activations of 2^23 dwarf what two of the per-node
+    layers lose; that family is there for the block exponent.)"""
+    for family in MISTAKES[mistake][0]:
+        r = _one_layer_ratio(mistake, family, level, stage)
+        print(f"{mistake} in {stage}, {family} {level}: error / bound {r['measured']:.3g} (with the whole F: {r['a-priori']:.3g})")
+        assert r["measured"] > 1.0, (mistake, family, level, stage, r)
+
+
+@pytest.mark.parametrize("mistake, level", [(m, lv) for m in PLANE_MISTAKES for lv in PC.LEVELS])
+def test_weakest_stage_of_a_plane_mistake_is_recorded(mistake, level):
+    """error / bound of the stage at which the mistake shows least, per family: under the bound rule, and under 3 x D32 + F.  A dropped
+    plane is recorded for offset-W and masked as well (not asserted: the per-layer requirement is on flat and trained-like)."""
+    required = MISTAKES[mistake][0]
+    extra = tuple(f for f in ("offset-W", "masked") if mistake != "low_plane_subnormals_flushed" and level in PC.levels(f))
+    for family in required + extra:
+        per = {st: _one_layer_ratio(mistake, family, level, st) for st in PC.stages(level)}
+        for rule in ("measured", "a-priori"):
+            st = min(per, key=lambda s: per[s][rule])
+            n_pass = sum(per[s][rule] <= 1.0 for s in per)
+            print(f"{mistake} {family} {level}, {rule} F: weakest stage {st} at {per[st][rule]:.3g}; {n_pass} of {len(per)} stages pass")
+            # (a mistake: "achieved" above the "bound" of 1 is what is wanted here)
+            record_margin(f"pair plane mistake in one layer, weakest stage [error / bound, {rule} F]: {mistake} {family} {level}",
+                          per[st][rule], 1.0)
+        assert family in extra or min(per[s]["measured"] for s in per) > 1.0
 
 
 def test_ln_eps_must_follow_the_block_exponent_on_ordinary_magnitudes():
