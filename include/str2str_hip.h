@@ -59,7 +59,7 @@ int s2s_edge_transition(const float* edge, const float* node_ab, const float* no
                         int n_res, float ln_eps, const float* proj_w_packed, const float* proj_bias_cat64,
                         float* proj_attn_bias, float* proj_pair_z, void* stream);
 
-/* The same operator on split-f16 MFMA ("f16x3", csrc/pair_mlp_f16.hip; the default): every fp32 operand as two f16 numbers (11 + 11
+/* The same operator on split-f16 MFMA ("f16x3", csrc/edge_transition_f16.h; the default): every fp32 operand as two f16 numbers (11 + 11
  * bits + the residue's sign = fp32's 24), products w_h x_h + w_h x_l + w_l x_h with the weights stored as the split of 2^5 w (2^-5
  * back in the epilogues), fp32 accumulation -- three matrix instructions per block, the dropped w_l x_l below one fp32 rounding.
  * Activations must stay below f16's 65504 (range guard above).  weight_stream: 30 (+1 with the fused projection) stages x 32 KiB

@@ -28,7 +28,7 @@ def default_arith() -> str:
 # their kernels.  The families are independent: any subset may run on the exact kernels while the rest stays on f16x3 (the pair tensor
 # changes layout at the boundary, the node stream's format follows the trunk) -- which is how the sampler answers a raised flag: only
 # the family that overflowed pays the fp32 price.
-#   "edge_transition"  EdgeTransition.arith                  (csrc/pair_mlp_f16.hip | pair_mlp.hip; 73 % of the cfg2 step)
+#   "edge_transition"  EdgeTransition.arith                  (csrc/edge_transition_f16.h | pair_mlp.hip; 73 % of the cfg2 step)
 #   "edge_embed"       EmbeddingModule.arith                 (edge embedding kernels)
 #   "ipa"              InvariantPointAttention.arith         (point preparation + attention core)
 #   "node"             TranslationIPA.arith, EmbeddingModule.node_arith   (node GEMMs, pack_planes, encoder attention: the activation

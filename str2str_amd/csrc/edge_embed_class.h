@@ -1,5 +1,5 @@
 // The per-pair CLASS of the edge embedding's first layer: which distogram row and which relative-position row a pair (i, j) gathers.
-// One definition for the kernels that need it -- edge_embed_f16_kernel (csrc/pair_mlp_f16.hip, setup_b) and the class expansion
+// One definition for the kernels that need it -- edge_embed_f16_kernel (csrc/edge_embed_f16.h, setup_b) and the class expansion
 // (csrc/pair_embed_expand.hip) -- because the bin rule's strict comparisons and the unfused distance are pinned by the parity tests.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,21 +1,4 @@
-// EdgeTransition / edge embedding on split-f16 MFMA ("f16x3"): fp32-equivalent accuracy on the 16-bit matrix cores, the DEFAULT
-// arithmetic of the pair stream.  Same operators and contracts as s2s_edge_transition / s2s_edge_embed (csrc/pair_mlp.hip, the
-// exact fp32-MFMA kernels; reference EdgeTransition.forward, src/models/net/layers.py:170-185 + mask ipa.py:372, and
-// EmbeddingModule.forward, denoising_ipa.py:137-158).
-//
-// Arithmetic.  Every fp32 operand is split into two f16 numbers  x = x_h + x_l (+ <= 2^-24 |x|),  x_h = rn16(x), x_l = rn16(x - x_h)
-// -- 11 + 11 significant bits plus the sign of the residue, i.e. fp32's 24 -- and a product keeps  w_h x_h + w_h x_l + w_l x_h  (the
-// dropped w_l x_l is below one fp32 rounding of the product) on v_mfma_f32_32x32x16_f16 with fp32 accumulation: 3 MFMAs per
-// (k-step, tile).  f16's narrow exponent is handled by one exact power-of-two scaling: the weight side stores the split of 2^5 w,
-// W_h = rn16(32 w), W_l = rn16(32 w - W_h)  (so that the small part stays in f16's normal range; 2 A fragments per (k-step, tile),
-// 4 KiB per slot, 32 KiB stages, 0.94 MB stream), the activation side two plane registers x_h, x_l, and the accumulators carry
-// 32 x the layer output: the factor 2^-5 rides in the multiply-add that adds the bias / seeds in every epilogue (LayerNorm, scale
-// invariant, runs on the scaled values with 1024 eps).  A value of x_l below f16's normal range (|x| < 0.25) is rounded to 2^-25
-// absolute -- 1.7e-8 rms on an O(1) output, under fp32's own rounding.
-// RANGE: activations must stay below f16's 65504.  Every activation that is split here feeds a running maximum; a tile whose
-// maximum reaches 2^15 (or is not finite) raises the caller's range flag (range_flag.h), and the sampler re-runs that chunk on the
-// exact fp32 kernels (str2str_amd/sampler.py) -- an overflow is neither silent nor an error.  Weights with |32 w| >= 65504 are
-// refused at pack time (ops.pack_f16x2_layer).
+// EdgeTransition on split-f16 MFMA: the kernel template and its launcher (arithmetic and range guard: pair_f16.h).
 //
 // Schedule.  One wave owns 32 pairs; the 4 waves of a workgroup share the weight stream (30 stages of 32 KiB through a ring of
 // LDS buffers, see s_w).  A stage is 8 SLOTS of 6 MFMAs / 4 A fragments.  Per pair tile (240 slots):
@@ -46,36 +29,32 @@
 // Pair-tensor layouts: row-major [B,N,N,128] (the reference's) or TILED on either side (include/str2str_hip.h): a lane owns one pair,
 //   so on row-major rows every load / store instruction touches 32 B in each of 32 cache lines; tiled, 8 whole lines.  The last
 //   EdgeTransition of a trunk writes no pair tensor at all (io_layout bit 2).
-#include <hip/hip_runtime.h>
+#pragma once
+#include "pair_f16.h"
+#include "pair_launch.h"
 
-#include <cstdlib>
+namespace s2s {
 
-#include "edge_embed_class.h"
-#include "f16x3.h"
-#include "range_flag.h"
-#include "str2str_hip.h"
+// the arguments of s2s_edge_transition_f16x3 (include/str2str_hip.h) in its order, filled once by the public entry point
+struct EtArgs {
+    const float *edge, *node_ab, *node_p;  const void* weight_stream;
+    const float *b2, *ln_gamma, *ln_beta, *mask;  float* out;
+    int n_samples, n_res;  float ln_eps;  int io_layout;
+    const float* proj_bias_cat64;  float *proj_attn_bias, *proj_pair_z;
+    int prescale_exp;  int* range_words;  void* stream;
+};
+// Inside the library only, each in its own translation unit (two instantiations of the kernel per unit):
+// chains below 32 residues: a 32-pair tile spans more than two rows, the row seeds stay per-lane loads
+__attribute__((visibility("hidden"))) int et_f16x3_short_chains(const EtArgs& a);
+// the first EdgeTransition behind the class path of the edge embedding: edge rows read by class (io_layout bit 3)
+__attribute__((visibility("hidden"))) int et_f16x3_by_class(const EtArgs& a);
 
-// Three translation units from this one source (the four edge-transition instantiations + the two of the edge embedding took 7.5 minutes
-// of a forced build as one unit): S2S_PM_PART 1 (this file compiled directly) = the edge transition for chains of 32+ residues and the
-// public entry point, 2 (pair_mlp_f16_b.hip) = its per-lane-seed form for shorter chains, 3 (pair_mlp_f16_c.hip) = the edge embedding,
-// 4 (pair_mlp_f16_d.hip) = the edge embedding's class-table form, 5 (pair_mlp_f16_e.hip) = the edge transition reading its edge rows BY CLASS.
-#ifndef S2S_PM_PART
-#define S2S_PM_PART 1
-#endif
+}  // namespace s2s
 
 namespace {
 
-constexpr int kStageBytes = 32 * 1024;  // 8 slots x 4 fragments x 1 KiB
 constexpr int kStagesBase = 30;         // + 1 stage (8 slots) for the fused pair projection of the next IPA block
-
-// max(x, 0) as ONE instruction.  fmaxf() of a value the compiler cannot see through (a pinned register, an MFMA result) is preceded by
-// a canonicalising v_max_f32 x, x (IEEE quieting of a signalling NaN): 128 of the edge embedding's ~1500 VALU instructions per tile.
-// v_max_f32 itself returns the other operand for any NaN input, which is what the two-instruction form computes as well.
-__device__ __forceinline__ float relu1(float x) {
-    float r;
-    asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
+constexpr int kClsSlot = 200;           // BYCLS: the schedule slot that requests the next tile's class indices (one HBM round trip ahead of slot kXv0 + 1)
 
 // slot s of the schedule: phase 0 = A (layer 1), 1 = B (layer 2), 2 = F (final layer)
 struct SlotDesc { int phase, t, a, b; };  // A: tile t, a = k-step pair 0..3;  B: tile t, a = u (k-step 2t+u), b = tile pair 0..5 (B_11: pair-major);
@@ -100,9 +79,7 @@ constexpr SlotDesc slot_desc(int s) {
 constexpr int sched_slot(bool proj, int ns) { return !proj ? ns : (ns < 8 ? ns : (ns < 16 ? 240 + (ns - 8) : ns - 8)); }
 constexpr int blob_stage(bool proj, int st) { return !proj ? st : (st == 0 ? 0 : (st == 1 ? 30 : st - 1)); }
 
-#define S2S_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 __device__ float s2s_one[1] = {1.0f};   // stands in for an absent node mask (read with stride 0)
-
 
 // PROJ: also emit the NEXT IPA block's linear_b / down_z (ipa.py:177,253) of the pair vector just produced -- one more
 // weight stage (64 x 128 Wcat, chain-packed), 8 more slots on the LayerNorm output while it is still in registers,
@@ -255,12 +232,7 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
     // BYCLS: a pair's row as ONE 32-bit byte offset into the records (below 4 GB by the CALLER's rule, see the header: the row count is
     // not known here): record cls + 1, this lane's
     // half.  The loads are base (scalar) + offset (one register) + immediate; the class index itself lives from its load to the offset.
-#ifndef S2S_ET_CLS_NT
-#define S2S_ET_CLS_NT 0      // table rows as plain loads (they are re-read from the L2 by every tile that meets the class; profiles/r08_et_by_class_stop_rule.md)
-#endif
-#ifndef S2S_ET_CLS_SLOT
-#define S2S_ET_CLS_SLOT 200  // the schedule slot that requests the next tile's class indices (one HBM round trip ahead of slot kXv0 + 1)
-#endif
+    // Table rows are plain loads: they are re-read from the L2 by every tile that meets the class (nt measured, profiles/r08_et_by_class_stop_rule.md).
     const unsigned cls_rec = (io_layout & 16) ? s2s::kEeRecProj : s2s::kEeRecPlain;
     auto cls_pair = [&](long long wg_tile) -> unsigned {   // flat pair of this lane in tile wg_tile, clamped like setup()
         const unsigned p = ((unsigned)wg_tile * 4u + (unsigned)wave) * 32u + ((unsigned)lane & 31u);
@@ -269,11 +241,7 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
     auto cls_off = [&](int cls) -> unsigned { return ((unsigned)(cls + 1) * cls_rec + 4u * (unsigned)h) * 4u; };
     auto ldrow_cls = [&](unsigned off, int g) -> float4 {
         const f32x4* q = reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(edge) + off + 32 * g);
-#if S2S_ET_CLS_NT
-        const f32x4 v = __builtin_nontemporal_load(q);
-#else
         const f32x4 v = *q;
-#endif
         return make_float4(v.x, v.y, v.z, v.w);
     };
     const long long n_wt = (M + 127) / 128;
@@ -496,7 +464,7 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
     bool has_next = false;
     PairCtx nxt = cur;  // next tile's context, edge row and planes: produced under the last 16 slots of this tile
     float4 xv[16];
-    unsigned ncls = 0;   // BYCLS: the next tile's class index (from slot S2S_ET_CLS_SLOT), then its row offset (from slot kXv0 + 1)
+    unsigned ncls = 0;   // BYCLS: the next tile's class index (from slot kClsSlot), then its row offset (from slot kXv0 + 1)
     f16x8 xpn[8][2];
     f16x8 xq[8][2];   // final-layer input planes of k-steps 8..15 (block 1 of the layer-2 epilogue)
     auto slot = [&](auto sc) {
@@ -523,7 +491,7 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
         //  address unit -- and whatever waits next on the in-order counter waits for all of it.  Two loads per slot, in slots whose
         //  next counter wait (the weight store 4+ slots later) is at least 6 slots away: HBM latency fits in between.)
         constexpr int kXv0 = 208;
-        if constexpr (BYCLS && s == S2S_ET_CLS_SLOT) ncls = (unsigned)cls_idx[cls_pair(has_next ? wt_next : wt)];
+        if constexpr (BYCLS && s == kClsSlot) ncls = (unsigned)cls_idx[cls_pair(has_next ? wt_next : wt)];
         if constexpr (BYCLS && s == kXv0 + 1) ncls = cls_off((int)ncls);
         if constexpr (s == kXv0) nxt = setup(has_next ? wt_next : wt);
         if constexpr (s == kXv0 + 3) stage_load(nxt);     // (slots ss = 3, 0 of the next stage: none of the edge row's loads)
@@ -708,599 +676,48 @@ __global__ void __launch_bounds__(256) edge_transition_f16_kernel(
     s2s::range_report(range_flag, amax, s2s::kRangeEdgeTransition);
 }
 
-
-// ------------------------------------------------------------------------------------------------------------------
-// Edge embedding on split-f16 MFMA: same operator and contract as s2s_edge_embed (csrc/pair_mlp.hip; reference
-// EmbeddingModule.forward edge branch, denoising_ipa.py:137-158).  The first Linear(120 -> 128) is a sum of four gathered
-// rows (+ ReLU); the two 128 x 128 layers, LayerNorm and (PROJ) the first IPA block's linear_b / down_z run as f16x3 slots
-// exactly like the edge transition above: 5 weight stages of 32 KiB (W2 | W3 | [linear_b; down_z]), 40 slots of 6 MFMAs per
-// 32-pair tile, persistent workgroups; the NEXT tile's rows are gathered and split under the current tile's MFMAs.
-// TABLE (s2s_edge_embed_classes_f16x3): the same body on the rows of the CLASS TABLE instead of on pairs.  "Pair" r is the class
-//   r = ((fa 2 + fb) n_rel + d) (n_bins + 1) + (bin + 1)   (s2s::ee_class_row)
-// and gathers node_a[fa], node_b[fb] (N = the number of rows of these two operands), rel_tab[d], bin_tab[bin] (kb = 0 for bin = -1):
-// no CA, residue index or mask is read, the edge mask is 1, and a row's outputs go to one contiguous record of `out`
-// (z[128] | attn_bias[8] | pair_z[32] with PROJ, z alone without).  Only the per-pair setup and the output addresses differ: the
-// weight pipe, the slots, the split, LayerNorm, the projection and the range tracking are the statements below, shared.
-template <bool PROJ, bool TABLE = false>
-__global__ void __launch_bounds__(256) edge_embed_f16_kernel(
-    const float* __restrict__ node_a, const float* __restrict__ node_b, const float* __restrict__ rel_tab,
-    const float* __restrict__ bin_tab, const float* __restrict__ bin_lower, const long long* __restrict__ residue_idx,
-    const float* __restrict__ ca, const char* __restrict__ wblob, const float* __restrict__ b2, const float* __restrict__ b3,
-    const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mask, float* __restrict__ out,
-    long long M, int N, int rel_off, int n_rel, int n_bins, float ln_eps, int out_tiled, const float* __restrict__ proj_b,
-    float* __restrict__ proj_bias_out, float* __restrict__ proj_pz_out, int* __restrict__ range_flag) {
-    constexpr int kStages = PROJ ? 5 : 4;
-    constexpr int kSlots = 8 * kStages;
-    __shared__ __attribute__((aligned(16))) char s_w[2][kStageBytes];
-    __shared__ __attribute__((aligned(16))) float s_vec[512 + 64];  // b2 | b3 | gamma | beta | projection bias
-    __shared__ __attribute__((aligned(16))) float s_bins[s2s::kEeBinSlots];    // distogram bin lower edges (ascending), padded with 3e38
-    const int lane = threadIdx.x & 63, h = lane >> 5, wave = threadIdx.x >> 6;
-
-    // ---- weight pipe (identical to the edge transition's)
-    const unsigned voff = wave * 8192 + lane * 16;
-    typedef __attribute__((address_space(3))) char lds_char;
-    lds_char* lds_image[2] = {(lds_char*)&s_w[0][lane * 16], (lds_char*)&s_w[1][lane * 16]};
-    asm volatile("" : "+v"(lds_image[0]), "+v"(lds_image[1]));
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wblob, 0, kStages * kStageBytes, 0x00020000);
-    auto ldw = [&](unsigned vo, int so) -> f32x4 {
-        const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, vo, so, 0);
-        return f32x4{__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w)};
-    };
-    f32x4 c0, c1, c2, c3, e0, e1, e2, e3;
-    typedef __attribute__((address_space(3))) f32x4 lds_f4;
-    auto cp_load_a = [&](int stage) {
-        const int so = stage * kStageBytes;
-        c0 = ldw(voff, so); c1 = ldw(voff + 1024, so); c2 = ldw(voff + 2048, so); c3 = ldw(voff + 3072, so);
-    };
-    auto cp_load_b = [&](int stage) {
-        const int so = stage * kStageBytes + 4096;
-        e0 = ldw(voff, so); e1 = ldw(voff + 1024, so); e2 = ldw(voff + 2048, so); e3 = ldw(voff + 3072, so);
-    };
-    auto cp_store_a = [&](int par) {
-        lds_char* d = lds_image[par] + wave * 8192;   // (last-loaded piece first: its counter wait covers the group)
-        *(lds_f4*)(d + 3072) = c3; *(lds_f4*)(d + 2048) = c2; *(lds_f4*)(d + 1024) = c1; *(lds_f4*)(d) = c0;
-    };
-    auto cp_store_b = [&](int par) {
-        lds_char* d = lds_image[par] + (wave * 8192 + 4096);
-        *(lds_f4*)(d + 3072) = e3; *(lds_f4*)(d + 2048) = e2; *(lds_f4*)(d + 1024) = e1; *(lds_f4*)(d) = e0;
-    };
-    cp_load_a(0);
-    cp_load_b(0);
-
-    // ---- per-tile context: the four first-layer rows of this lane's pair
-    // node_b / rel_tab / bin_tab come COLUMN-BLOCKED: [32 chunks of 4 channels][rows][4], so that the 16 B a lane wants of
-    // its pair's row sit next to the neighbouring pairs' (consecutive j -> consecutive rows): one load instruction touches
-    // 8 cache lines instead of 32.  Lane part of the address in voffset, chunk pair (2G, 2G+1) in the scalar offset.
-    struct Ctx {
-        const float* ra;
-        unsigned vb, vr, vk;   // byte offsets of (row, chunk h) in node_b / rel_tab / bin_tab
-        float kb;
-        long long p, boff;
-        float em;
-        bool valid;
-    };
-    const long long NN = (long long)N * N;
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)node_b, 0, (unsigned)((TABLE ? (long long)N : M / N) * 512), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc((void*)rel_tab, 0, n_rel * 512, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc((void*)bin_tab, 0, n_bins * 512, 0x00020000);
-    // setup in two halves so that the per-pair loads (CA coordinates, residue indices, masks) are in flight for a few slots
-    // before they are consumed; the distogram edges sit in LDS (s_bins)
-    struct Raw {
-        long long p, bi, bj, bb;
-        float ax, ay, az, bx, by, bz;
-        long long ii, ij;
-        float mi, mj;
-        bool valid;
-    };
-    // The launcher keeps the pair count of one launch below 2^31: 32-bit index arithmetic, division by N through
-    // floor(2^32 / N) (quotient short by at most one for x < 2^31; a 64-bit division is ~100 VALU instructions).
-    const unsigned n_magic = N >= 2 ? (unsigned)((1ull << 32) / (unsigned)N) : 0u;
-    auto div_n = [&](unsigned x, unsigned& q, unsigned& r) {
-        q = N >= 2 ? __umulhi(x, n_magic) : x;
-        r = x - q * (unsigned)N;
-        const bool fix = r >= (unsigned)N;
-        q = fix ? q + 1 : q;
-        r = fix ? r - (unsigned)N : r;
-    };
-    const float* mask_or_any = mask ? mask : ca;  // always a readable [B N] float array: no branch around the mask loads
-    auto setup_a = [&](long long wg_tile) -> Raw {
-        long long p = (wg_tile * 4 + wave) * 32 + (lane & 31);
-        Raw r;
-        r.valid = p < M;
-        p = r.valid ? p : M - 1;
-        r.p = p;
-        if constexpr (TABLE) {   // class row p -> (fa, fb, d, bin + 1), carried in the fields of the row / column node, the two indices
-            const unsigned nb1 = (unsigned)n_bins + 1u, q = (unsigned)p / nb1, cls = q / (unsigned)n_rel;
-            r.bi = cls >> 1; r.bj = cls & 1u; r.bb = 0;
-            r.ii = q - cls * (unsigned)n_rel; r.ij = (unsigned)p - q * nb1;
-            r.ax = r.ay = r.az = r.bx = r.by = r.bz = 0.f;
-            r.mi = r.mj = 1.f;
-            return r;
-        }
-        // p = (bb N + i) N + j:  global row bi = p / N,  j = p - bi N,  bb = bi / N
-        unsigned bi, j, bb, i;
-        div_n((unsigned)p, bi, j);
-        div_n(bi, bb, i);
-        r.bi = bi; r.bb = bb; r.bj = bb * (unsigned)N + j;
-        r.ax = ca[r.bi * 3 + 0]; r.ay = ca[r.bi * 3 + 1]; r.az = ca[r.bi * 3 + 2];
-        r.bx = ca[r.bj * 3 + 0]; r.by = ca[r.bj * 3 + 1]; r.bz = ca[r.bj * 3 + 2];
-        r.ii = residue_idx[r.bi];
-        r.ij = residue_idx[r.bj];
-        r.mi = mask_or_any[r.bi];
-        r.mj = mask_or_any[r.bj];
-        return r;
-    };
-    auto setup_b = [&](const Raw& r) -> Ctx {
-        Ctx c;
-        c.valid = r.valid;
-        // distogram bin and relative-position row of this pair (edge_embed_class.h); TABLE: the class row names them
-        const int bin = TABLE ? (int)r.ij - 1 : s2s::ee_pair_bin(s_bins, n_bins, r.ax, r.ay, r.az, r.bx, r.by, r.bz);
-        const long long d = TABLE ? r.ii : s2s::ee_rel_row(r.ii, r.ij, rel_off, n_rel);
-        c.ra = node_a + r.bi * 128;
-        const unsigned jj = (unsigned)(r.bj - r.bb * N);
-        c.vb = ((unsigned)r.bb * 32u * (unsigned)N + (unsigned)h * (unsigned)N + jj) * 16u;
-        c.vr = ((unsigned)h * (unsigned)n_rel + (unsigned)d) * 16u;
-        c.vk = ((unsigned)h * (unsigned)n_bins + (unsigned)(bin < 0 ? 0 : bin)) * 16u;
-        c.kb = bin < 0 ? 0.f : 1.f;
-        c.p = r.p;
-        c.boff = r.p + 7 * r.bb * NN;
-        c.em = (!TABLE && mask) ? r.mi * r.mj : 1.0f;
-        return c;
-    };
-    float amax = 0.f;   // range guard (range_flag.h)
-    auto split4 = [&](const float (&x)[4], f16x8& ph, f16x8& pm, int at) {  // planes (x_h, x_l)
-        split4_f16(x, ph, pm, at, amax);
-    };
-    // first-layer sum in accumulator layout: g1[4G + q] = channel 8G + 4h + q, built row by row (same association as the
-    // fp32 kernel: ((a + b) + r) + kb*k)
-    float g1[64];
-    auto row_set = [&](const float* r) {
-#pragma unroll
-        for (int G = 0; G < 16; ++G) {
-            const float4 v = ldg4(r, G, h);
-            g1[4 * G + 0] = v.x; g1[4 * G + 1] = v.y; g1[4 * G + 2] = v.z; g1[4 * G + 3] = v.w;
-        }
-    };
-    float tmp[64];
-    auto row_cb = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned vo, int rows, float (&dst)[64], int G0, int G1) {
-#pragma unroll
-        for (int G = G0; G < G1; ++G) {  // chunk 2G + h of the row: scalar offset 2G rows-blocks of 16 B
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, G * 32 * rows, 0);
-            dst[4 * G + 0] = __uint_as_float(v.x); dst[4 * G + 1] = __uint_as_float(v.y);
-            dst[4 * G + 2] = __uint_as_float(v.z); dst[4 * G + 3] = __uint_as_float(v.w);
-        }
-    };
-    auto row_add = [&](float scale) {  // pinned: left alone, the compiler sinks these adds to the splits 20 slots later and keeps
-#pragma unroll                         // (spills) all four loaded rows until then
-        for (int i = 63; i >= 0; --i) {   // (last-loaded values first: one counter wait for the whole row instead of one per load)
-            g1[i] = __fmaf_rn(scale, tmp[i], g1[i]);  // (explicit: both template variants must round alike)
-            asm volatile("" : "+v"(g1[i]));
-        }
-    };
-    // ReLU + split of first-layer k-step ks (registers 8ks .. 8ks+7 of g1: chain order) into planes
-    auto g1_split = [&](f16x8 (&dst)[2], int ks) {
-        const float x0[4] = {relu1(g1[8 * ks + 0]), relu1(g1[8 * ks + 1]), relu1(g1[8 * ks + 2]), relu1(g1[8 * ks + 3])};
-        const float x1[4] = {relu1(g1[8 * ks + 4]), relu1(g1[8 * ks + 5]), relu1(g1[8 * ks + 6]), relu1(g1[8 * ks + 7])};
-        split4(x0, dst[0], dst[1], 0);
-        split4(x1, dst[0], dst[1], 4);
-    };
-
-    const long long n_wt = (M + 127) / 128;
-    long long wt = blockIdx.x;
-    if constexpr (!TABLE) s2s::ee_fill_bins(s_bins, bin_lower, n_bins);
-    __syncthreads();
-    Ctx cur = setup_b(setup_a(wt));
-    f16x8 xp[8][2];  // planes of the current layer's input (8 k-steps of 16)
-    {
-        row_set(cur.ra);
-        for (int i = threadIdx.x; i < 512; i += 256)
-            s_vec[i] = i < 128 ? kWS * b2[i] : (i < 256 ? kWS * b3[i - 128] : (i < 384 ? gamma[i - 256] : beta[i - 384]));   // biases x 32 (accumulator scale)
-        if (PROJ && threadIdx.x < 64) s_vec[512 + threadIdx.x] = proj_b[threadIdx.x];
-        cp_store_a(0);
-        cp_load_a(1);
-        cp_store_b(0);
-        row_cb(rs_b, cur.vb, N, tmp, 0, 16); row_add(1.0f);
-        row_cb(rs_r, cur.vr, n_rel, tmp, 0, 16); row_add(1.0f);
-        row_cb(rs_k, cur.vk, n_bins, tmp, 0, 16); row_add(cur.kb);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) g1_split(xp[ks], ks);
-    }
-    f32x16 a2[4], a3[4], pq[2];
-    f16x8 fr[2][4];
-    auto fetch = [&](int par, int slot_in_stage, f16x8 (&f)[4]) {
-        typedef __attribute__((address_space(3))) f16x8 lds_frag;
-        const lds_frag* s = (const lds_frag*)lds_image[par] + slot_in_stage * 4 * 64;
-        f[0] = s[0]; f[2] = s[128]; f[3] = s[192]; f[1] = s[64];   // (the slot's first MFMA reads f[1]: one counter wait per slot, as in the edge transition)
-    };
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // The VALU work of a tile is cut into per-k-step pieces, each pinned (empty asm on its inputs / outputs: otherwise the
-    // compiler sinks a piece to its first use, i.e. in FRONT of the MFMAs that wait for it) into a slot whose MFMAs do not depend
-    // on it, and interleaved with them by sched_group_barrier.
-    auto pin_frag = [&](f16x8 (&x)[2]) { asm volatile("" : "+v"(x[0]), "+v"(x[1])); };
-    // accumulator start = bias (registers 4 rq + q of tile t <-> channel 32 t + 8 rq + 4 h + q)
-    auto bias16 = [&](const float* vec, int t) -> f32x16 {   // (s_vec holds 32 x bias: the accumulators carry 32 x the layer output)
-        const float4 b0 = ldg4(vec, 4 * t, h), b1 = ldg4(vec, 4 * t + 1, h), b2v = ldg4(vec, 4 * t + 2, h), b3v = ldg4(vec, 4 * t + 3, h);
-        return f32x16{b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2v.x, b2v.y, b2v.z, b2v.w, b3v.x, b3v.y, b3v.z, b3v.w};
-    };
-    // layer-2 output (bias already in the accumulator): ReLU + split of k-step k -> layer-3 input planes xp[k]
-    auto l2_piece = [&](auto kc) {
-        constexpr int k = decltype(kc)::value, t = k / 2;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int rq = 2 * (k & 1) + u;
-            const float xx[4] = {relu1(a2[t][4 * rq + 0]) * kInvWS, relu1(a2[t][4 * rq + 1]) * kInvWS,
-                                 relu1(a2[t][4 * rq + 2]) * kInvWS, relu1(a2[t][4 * rq + 3]) * kInvWS};
-            split4(xx, xp[k][0], xp[k][1], 4 * u);
-        }
-        pin_frag(xp[k]);
-    };
-    float ln_mean = 0.f, ln_rstd = 0.f;
-    // output block of the wave (16 KiB): row-major  n 512 + g 32 + h 16,  tiled  g 1024 + lane 16  (edge transition, "Pair-tensor layouts")
-    // (TABLE: row-major records of kRec floats)
-    constexpr unsigned kRec = TABLE ? (PROJ ? s2s::kEeRecProj : s2s::kEeRecPlain) : 128u;
-    const unsigned out_lane = out_tiled ? lane * 16u : (unsigned)((lane & 31) * (kRec * 4) + h * 16), out_step = out_tiled ? 1024u : 32u;
-    f16x8 xq[2][2];  // LayerNorm output planes of the projection's current / next k-step
-    // LayerNorm output of k-step k (16 channels): scale, shift, edge mask, store (+ planes for the projection)
-    __amdgpu_buffer_rsrc_t rs_out;  // this tile's 32 output rows; rows past M are outside num_records: their stores are dropped
-    auto out_rsrc = [&](long long wg_tile) {
-        const long long p0 = (wg_tile * 4 + __builtin_amdgcn_readfirstlane(wave)) * 32;
-        const long long left = M - p0;
-        // (tiled layout: the pairs of a partial last tile are interleaved with its padding, which the buffer holds: whole block)
-        rs_out = __builtin_amdgcn_make_buffer_rsrc((void*)(out + (p0 < M ? p0 : 0) * kRec), 0,
-                                                   (unsigned)(left <= 0 ? 0 : (left < 32 && !out_tiled ? left : 32)) * (kRec * 4u), 0x00020000);
-    };
-    float4 lga[2], lbe[2];  // gamma / beta of the next LayerNorm piece, read at the top of its slot
-    auto ln_load = [&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int g = 4 * (k / 2) + 2 * (k & 1) + u;
-            lga[u] = ldg4(s_vec + 256, g, h);
-            lbe[u] = ldg4(s_vec + 384, g, h);
-        }
-    };
-    auto ln_piece = [&](auto kc, const Ctx& c) {
-        constexpr int k = decltype(kc)::value, t = k / 2;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int rq = 2 * (k & 1) + u, g = 4 * t + rq;
-            const float4 ga = lga[u], be = lbe[u];
-            float4 o;
-            // (the channel offset goes into the store's immediate field, not into an SGPR soffset: a 128-bit buffer store with an
-            // SGPR offset followed by VALU writes of its data registers lost the last lanes' data in the plain variant)
-            // explicit roundings: the fused-projection and the plain variant of this kernel must agree bit for bit
-            o.x = __fmul_rn(__fmaf_rn(__fmul_rn(a3[t][4 * rq + 0] - ln_mean, ln_rstd), ga.x, be.x), c.em);
-            o.y = __fmul_rn(__fmaf_rn(__fmul_rn(a3[t][4 * rq + 1] - ln_mean, ln_rstd), ga.y, be.y), c.em);
-            o.z = __fmul_rn(__fmaf_rn(__fmul_rn(a3[t][4 * rq + 2] - ln_mean, ln_rstd), ga.z, be.z), c.em);
-            o.w = __fmul_rn(__fmaf_rn(__fmul_rn(a3[t][4 * rq + 3] - ln_mean, ln_rstd), ga.w, be.w), c.em);
-            // (plain stores: with the nt bit, no change beyond the noise; profiles/r06_et_nt_ab.txt)
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(o.w)},
-                                                   rs_out, out_lane + (unsigned)g * out_step, 0, 0);
-            if constexpr (PROJ) {
-                const float xx[4] = {o.x, o.y, o.z, o.w};
-                split4(xx, xq[k & 1][0], xq[k & 1][1], 4 * u);
-            }
-        }
-        if constexpr (PROJ) pin_frag(xq[k & 1]);
-    };
-    // rows of the next tile's first layer, eight 16 B loads per slot (a burst of 32 per wave backs up the vector memory
-    // pipe and with it the wave's MFMA issue)
-    auto row_load8 = [&](const float* r, float (&dst)[64], int half) {
-#pragma unroll
-        for (int G = 8 * half; G < 8 * half + 8; ++G) {
-            const float4 v = ldg4(r, G, h);
-            dst[4 * G + 0] = v.x; dst[4 * G + 1] = v.y; dst[4 * G + 2] = v.z; dst[4 * G + 3] = v.w;
-        }
-    };
-    S2S_LDS_BARRIER();
-    fetch(0, 0, fr[0]);
-    f32x16 initA0 = bias16(s_vec, 0), initA1 = bias16(s_vec, 1), initB0, initB1;
-    // per-pair scalars (CA coordinates, residue indices, masks) of the tile after this one: requested a whole tile ahead -- used four
-    // slots after the request they cost the tile ~1.2 k cycles of waiting (profiles/r03f_ee_phase_probe.txt)
-    Raw nraw = setup_a(wt + gridDim.x < n_wt ? wt + gridDim.x : wt);
-
-    for (;;) {
-    const long long wt_next = wt + gridDim.x;
-    const bool has_next = wt_next < n_wt;
-    Ctx nxt = cur;
-    f16x8 xl[2];  // the next tile's last k-step (xp[7] is read by the final layer's last slot)
-    static_for<0, kSlots>([&](auto sc) {
-        constexpr int s = decltype(sc)::value;
-        constexpr int stage = s / 8, ss = s % 8, par = stage & 1;
-        constexpr int layer = s / 16;             // 0: layer 2, 1: layer 3, 2: projection
-        constexpr int ks = layer < 2 ? (s % 16) / 2 : s - 32;
-        constexpr int pr = layer < 2 ? s % 2 : 0;
-        // ---------------- top of the slot: LDS / global loads whose results are used under later MFMAs
-        // the accumulators of a layer's first two slots start from the bias, read one slot ahead (A: slots 0 / 16, B: 1 / 17)
-        if constexpr (s == kSlots - 1) { initA0 = bias16(s_vec, 0); initA1 = bias16(s_vec, 1); }
-        if constexpr (s == 0) { initB0 = bias16(s_vec, 2); initB1 = bias16(s_vec, 3); }
-        if constexpr (s == 15) { initA0 = bias16(s_vec + 128, 0); initA1 = bias16(s_vec + 128, 1); }
-        if constexpr (s == 16) { initB0 = bias16(s_vec + 128, 2); initB1 = bias16(s_vec + 128, 3); }
-        if constexpr (PROJ && s >= 31 && s < 39) ln_load(IC<s - 31>{});
-        if constexpr (ss < 7) {
-            fetch(par, ss + 1, fr[(s + 1) & 1]);
-        } else {
-            S2S_LDS_BARRIER();
-            fetch(par ^ 1, 0, fr[(s + 1) & 1]);
-        }
-        // next tile: per-pair loads under slot 0, context under slot 4, then its four first-layer rows
-        if constexpr (s == 30) out_rsrc(wt);
-        if constexpr (s == 5) row_load8(nxt.ra, g1, 0);
-        if constexpr (s == 6) row_load8(nxt.ra, g1, 1);
-        if constexpr (s == 7) row_cb(rs_b, nxt.vb, N, tmp, 0, 8);
-        if constexpr (s == 8) row_cb(rs_b, nxt.vb, N, tmp, 8, 16);
-        if constexpr (s == 13) row_cb(rs_r, nxt.vr, n_rel, tmp, 0, 8);
-        if constexpr (s == 14) row_cb(rs_r, nxt.vr, n_rel, tmp, 8, 16);
-        if constexpr (s == 18) row_cb(rs_k, nxt.vk, n_bins, tmp, 0, 8);
-        if constexpr (s == 19) row_cb(rs_k, nxt.vk, n_bins, tmp, 8, 16);
-        __builtin_amdgcn_sched_barrier(0);
-
-        // ---------------- the 12 MFMAs and the VALU pieces that run under them
-        const f16x8 (&f)[4] = fr[s & 1];
-        const f16x8 (&x)[2] = layer < 2 ? xp[ks] : xq[ks & 1];
-        f32x16& t0 = layer == 0 ? a2[2 * pr] : (layer == 1 ? a3[2 * pr] : pq[0]);
-        f32x16& t1 = layer == 0 ? a2[2 * pr + 1] : (layer == 1 ? a3[2 * pr + 1] : pq[1]);
-        if constexpr (ks == 0) {
-            if constexpr (layer < 2) {
-                t0 = mfma_f16(f[1], x[0], pr == 0 ? initA0 : initB0); t1 = mfma_f16(f[3], x[0], pr == 0 ? initA1 : initB1);
-            } else {
-                t0 = mfma_f16(f[1], x[0], zero16); t1 = mfma_f16(f[3], x[0], zero16);
-            }
-        } else {
-            t0 = mfma_f16(f[1], x[0], t0); t1 = mfma_f16(f[3], x[0], t1);  // W_l x_h
-        }
-        t0 = mfma_f16(f[0], x[1], t0); t1 = mfma_f16(f[2], x[1], t1);      // W_h x_l
-        t0 = mfma_f16(f[0], x[0], t0); t1 = mfma_f16(f[2], x[0], t1);      // W_h x_h
-        if constexpr (s == 1) nxt = setup_b(nraw);                                                        // the next tile's context
-        if constexpr (s == 26) nraw = setup_a(wt_next + gridDim.x < n_wt ? wt_next + gridDim.x : wt_next);   // requests for the tile after it
-        if constexpr (s == 12) row_add(1.0f);     // a + b   (same association as the fp32 kernel: ((a + b) + r) + kb k)
-        if constexpr (s == 17) row_add(1.0f);     // + relative-position row
-        if constexpr (s == 22) row_add(nxt.kb);   // + distogram row
-        // layer-2 output, k-step k (read by slots 16 + 2k, 17 + 2k) under slot 14 + 2k, k-step 0 under slot 15
-        if constexpr (s >= 16 && s <= 28 && s % 2 == 0) l2_piece(IC<(s - 14) / 2>{});
-        if constexpr (s == 15) l2_piece(IC<0>{});   // tiles 0, 1 of the layer-2 output are complete after slot 14
-        // next tile's first layer: k-step k of xp is last read by slot 17 + 2k, so k = 0..6 go under slots 24..30 and the
-        // last one (under slot 23) into xl
-        if constexpr (s >= 24 && s < 31) { g1_split(xp[s - 24], s - 24); pin_frag(xp[s - 24]); }
-        if constexpr (s == 23) { g1_split(xl, 7); pin_frag(xl); }
-        // LayerNorm output k-step k + 1 under projection slot 32 + k
-        if constexpr (PROJ && s >= 32 && s < 39) ln_piece(IC<s - 31>{}, cur);
-        // weight pipe: one load / LDS store behind each of the first four MFMAs (edge transition, same slots)
-        if constexpr (ss == 0) cp_load_b((stage + 1) % kStages);
-        if constexpr (ss == 4) cp_load_a((stage + 2) % kStages);
-        if constexpr (ss == 1) cp_store_a(par ^ 1);
-        if constexpr (ss == 5) cp_store_b(par ^ 1);
-        constexpr int copy_kind = (ss == 0 || ss == 4) ? 0x020 : ((ss == 1 || ss == 5) ? 0x200 : 0);   // VMEM read | DS write | none
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA,
-            if (copy_kind != 0 && i < 4) __builtin_amdgcn_sched_group_barrier(copy_kind, 1, 0);   // one piece of the weight pipe,
-            __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);  // up to eight VALU instructions behind it
-        }
-        __builtin_amdgcn_sched_barrier(0);
-
-        // ---------------- exposed steps
-        if constexpr (s == 31) {  // layer-3 output (bias included): LayerNorm statistics
-            float sum = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sum += a3[t][r];
-            ln_mean = __fmul_rn(xhalf_sum(sum), 1.0f / 128);
-            float var = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float dd = a3[t][r] - ln_mean;
-                    var = __fmaf_rn(dd, dd, var);
-                }
-            ln_rstd = 1.0f / sqrtf(__fmaf_rn(xhalf_sum(var), 1.0f / 128, ln_eps * (kWS * kWS)));   // (scaled accumulator: 1024 eps)
-            if constexpr (PROJ) {
-                ln_piece(IC<0>{}, cur);
-            } else {
-                static_for<0, 8>([&](auto kc) { ln_load(kc); ln_piece(kc, cur); });
-            }
-        }
-    });
-    if constexpr (PROJ) {
-        if (cur.valid) {
-            const float4 b0 = ldg4(s_vec + 512, 0, h);
-            // (TABLE: both projections follow z in the class row's record)
-            float* o = TABLE ? out + cur.p * kRec + 128 + 4 * h : proj_bias_out + cur.boff + 4 * h * NN;
-            const long long hs = TABLE ? 1 : NN;
-            float* pz = TABLE ? out + cur.p * kRec + 136 : proj_pz_out + cur.p * 32;
-            o[0] = __builtin_fmaf(pq[0][0], kInvWS, b0.x);
-            o[hs] = __builtin_fmaf(pq[0][1], kInvWS, b0.y);
-            o[2 * hs] = __builtin_fmaf(pq[0][2], kInvWS, b0.z);
-            o[3 * hs] = __builtin_fmaf(pq[0][3], kInvWS, b0.w);
-#pragma unroll
-            for (int g = 1; g <= 4; ++g) {
-                const int t = g >> 2, rq = g & 3;
-                const float4 bq = ldg4(s_vec + 512, g, h);
-                *reinterpret_cast<float4*>(pz + 8 * (g - 1) + 4 * h) =
-                    make_float4(__builtin_fmaf(pq[t][4 * rq + 0], kInvWS, bq.x), __builtin_fmaf(pq[t][4 * rq + 1], kInvWS, bq.y),
-                                __builtin_fmaf(pq[t][4 * rq + 2], kInvWS, bq.z), __builtin_fmaf(pq[t][4 * rq + 3], kInvWS, bq.w));
-            }
-        }
-    }
-    if (!has_next) break;
-    cur = nxt;
-    wt = wt_next;
-    xp[7][0] = xl[0]; xp[7][1] = xl[1];
-    if constexpr (kStages % 2 == 1) {  // odd stage count: the next tile's stage 0 sits in the other buffer
-        lds_char* sw = lds_image[0];
-        lds_image[0] = lds_image[1];
-        lds_image[1] = sw;
-    }
-    }  // persistent tile loop
-    s2s::range_report(range_flag, amax, s2s::kRangeEdgeEmbed);
-}
-
-
-// smallest number of samples whose pairs fill whole 32-pair blocks (launch boundaries of a tiled pair tensor)
-long long tile_aligned_samples(long long NN) {
-    long long q = 32;
-    while (q > 1 && (NN * (32 / q)) % 32 != 0) q /= 2;   // 32 / q samples suffice when NN (32 / q) is a multiple of 32
-    return 32 / q;
-}
-
-// persistent workgroups: one per CU of the current device
-int cu_count() {
-    int dev = 0, n_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-        return 256;
-    return n_cu;
-}
-
 template <bool STAGE, bool BYCLS = false>
-int et_launch(const float* edge, const float* node_ab, const float* node_p, const void* weight_stream, const float* b2,
-              const float* ln_gamma, const float* ln_beta, const float* mask, float* out, int n_samples, int n_res, float ln_eps,
-              int io_layout, const float* proj_bias_cat64, float* proj_attn_bias, float* proj_pair_z, int prescale_exp, int* range_words,
-              void* stream) {
-    if (n_samples <= 0 || n_res <= 0) return 0;
-    if ((io_layout & ~31) || ((io_layout & 4) && !proj_attn_bias) || (!(io_layout & 4) && !out)) return (int)hipErrorInvalidValue;
+int et_launch(const s2s::EtArgs& a) {
+    if (a.n_samples <= 0 || a.n_res <= 0) return 0;
+    const int io_layout = a.io_layout;
+    if ((io_layout & ~31) || ((io_layout & 4) && !a.proj_attn_bias) || (!(io_layout & 4) && !a.out)) return (int)hipErrorInvalidValue;
     // by class (bit 3): not with a tiled input, only with the fused projection; bit 4 (the record size) only with bit 3
-    if (BYCLS != ((io_layout & 8) != 0) || (BYCLS ? ((io_layout & 1) || !proj_attn_bias) : (io_layout & 16) != 0)) return (int)hipErrorInvalidValue;
-    if (prescale_exp < 0 || prescale_exp > 15) return (int)hipErrorInvalidValue;
-    const float sk = ldexpf(1.0f, -prescale_exp);
-    const long long NN = (long long)n_res * n_res;
+    if (BYCLS != ((io_layout & 8) != 0) || (BYCLS ? ((io_layout & 1) || !a.proj_attn_bias) : (io_layout & 16) != 0)) return (int)hipErrorInvalidValue;
+    if (a.prescale_exp < 0 || a.prescale_exp > 15) return (int)hipErrorInvalidValue;
+    const float sk = ldexpf(1.0f, -a.prescale_exp);
+    const long long NN = (long long)a.n_res * a.n_res;
     // 32-bit pair / head-major indices inside a launch (8 M < 2^32): split the samples over several launches when needed
-    const char* cap_env = getenv("S2S_ET_MAX_PAIRS");   // test hook: a smaller per-launch pair budget exercises the split
-    long long cap = cap_env ? atoll(cap_env) : 0;
-    if (cap <= 0 || cap > (1ll << 29) - 1) cap = (1ll << 29) - 1;
-    long long chunk = cap / NN;
-    if ((io_layout & 3) && chunk < n_samples) chunk -= chunk % tile_aligned_samples(NN);   // launches of a tiled tensor start on a 32-pair block
+    const long long chunk = s2s::samples_per_launch("S2S_ET_MAX_PAIRS", (1ll << 29) - 1, NN, a.n_samples, (io_layout & 3) != 0);
     if (chunk < 1) return (int)hipErrorInvalidValue;
     const float* one = nullptr;   // s2s_one of the current device
     if (hipGetSymbolAddress((void**)&one, HIP_SYMBOL(s2s_one)) != hipSuccess) return (int)hipErrorInvalidValue;
-    const int n_cu = cu_count();
-    for (long long b0 = 0; b0 < n_samples; b0 += chunk) {
-        const long long nb = n_samples - b0 < chunk ? n_samples - b0 : chunk;
-        const long long M = nb * NN, rows0 = b0 * n_res;
-        const long long wg_tiles = (M + 127) / 128;
-        const long long grid = wg_tiles < n_cu ? wg_tiles : n_cu;
+    const int n_cu = s2s::cu_count();
+    for (long long b0 = 0; b0 < a.n_samples; b0 += chunk) {
+        const long long nb = a.n_samples - b0 < chunk ? a.n_samples - b0 : chunk;
+        const long long M = nb * NN, rows0 = b0 * a.n_res;
+        const dim3 grid(s2s::persistent_grid(M, n_cu));
         // BYCLS: words [0, M32) of `edge` are the pairs' class indices, the records follow and do not move with the launch
-        const long long m32 = ((long long)n_samples * NN + 31) / 32 * 32;
-        const float* e = BYCLS ? edge + m32 : edge + b0 * NN * 128;
-        const int* ci = BYCLS ? reinterpret_cast<const int*>(edge) + b0 * NN : nullptr;
-        const float* nab = node_ab + rows0 * 896;
-        const float* np = node_p + rows0 * 128;
-        const float* mk = mask ? mask + rows0 : one;
-        const unsigned mks = mask ? 1u : 0u;
-        float* o = out ? out + b0 * NN * 128 : nullptr;
+        const long long m32 = ((long long)a.n_samples * NN + 31) / 32 * 32;
+        const float* e = BYCLS ? a.edge + m32 : a.edge + b0 * NN * 128;
+        const int* ci = BYCLS ? reinterpret_cast<const int*>(a.edge) + b0 * NN : nullptr;
+        const float* nab = a.node_ab + rows0 * 896;
+        const float* np = a.node_p + rows0 * 128;
+        const float* mk = a.mask ? a.mask + rows0 : one;
+        const unsigned mks = a.mask ? 1u : 0u;
+        float* o = a.out ? a.out + b0 * NN * 128 : nullptr;
         auto k_proj = &edge_transition_f16_kernel<true, STAGE, BYCLS>;
-        if (proj_attn_bias) {
-            hipLaunchKernelGGL(k_proj, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, e, nab, np,
-                               (const char*)weight_stream, b2, ln_gamma, ln_beta, mk, o, M, n_res, ln_eps, io_layout, mks, proj_bias_cat64,
-                               proj_attn_bias + b0 * 8 * NN, proj_pair_z + b0 * NN * 32, range_words, sk, ci);
+        if (a.proj_attn_bias) {
+            hipLaunchKernelGGL(k_proj, grid, dim3(256), 0, (hipStream_t)a.stream, e, nab, np,
+                               (const char*)a.weight_stream, a.b2, a.ln_gamma, a.ln_beta, mk, o, M, a.n_res, a.ln_eps, io_layout, mks,
+                               a.proj_bias_cat64, a.proj_attn_bias + b0 * 8 * NN, a.proj_pair_z + b0 * NN * 32, a.range_words, sk, ci);
         } else if constexpr (!BYCLS) {
             auto k_plain = &edge_transition_f16_kernel<false, STAGE>;
-            hipLaunchKernelGGL(k_plain, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, e, nab, np,
-                               (const char*)weight_stream, b2, ln_gamma, ln_beta, mk, o, M, n_res, ln_eps, io_layout, mks,
-                               (const float*)nullptr, (float*)nullptr, (float*)nullptr, range_words, sk, (const int*)nullptr);
+            hipLaunchKernelGGL(k_plain, grid, dim3(256), 0, (hipStream_t)a.stream, e, nab, np,
+                               (const char*)a.weight_stream, a.b2, a.ln_gamma, a.ln_beta, mk, o, M, a.n_res, a.ln_eps, io_layout, mks,
+                               (const float*)nullptr, (float*)nullptr, (float*)nullptr, a.range_words, sk, (const int*)nullptr);
         }
     }
     return (int)hipGetLastError();
 }
 
 }  // namespace
-
-#define S2S_ET_ARGS const float* edge, const float* node_ab, const float* node_p, const void* weight_stream, const float* b2, \
-                    const float* ln_gamma, const float* ln_beta, const float* mask, float* out, int n_samples, int n_res, float ln_eps, \
-                    int io_layout, const float* proj_bias_cat64, float* proj_attn_bias, float* proj_pair_z, int prescale_exp, \
-                    int* range_words, void* stream
-#define S2S_ET_PASS edge, node_ab, node_p, weight_stream, b2, ln_gamma, ln_beta, mask, out, n_samples, n_res, ln_eps, io_layout, \
-                    proj_bias_cat64, proj_attn_bias, proj_pair_z, prescale_exp, range_words, stream
-// chains below 32 residues: a 32-pair tile spans more than two rows, the row seeds stay per-lane loads (its own translation unit)
-extern "C" __attribute__((visibility("hidden"))) int s2s_et_f16x3_short_chains(S2S_ET_ARGS);   // (inside the library only)
-#if S2S_PM_PART == 2
-extern "C" int s2s_et_f16x3_short_chains(S2S_ET_ARGS) { return et_launch<false>(S2S_ET_PASS); }
-#endif
-// the first EdgeTransition behind the class path of the edge embedding: edge rows read by class (io_layout bit 3; its own translation unit)
-extern "C" __attribute__((visibility("hidden"))) int s2s_et_f16x3_by_class(S2S_ET_ARGS);   // (inside the library only)
-#if S2S_PM_PART == 5
-extern "C" int s2s_et_f16x3_by_class(S2S_ET_ARGS) {
-    // the records (zero record + class rows) are addressed with 32-bit byte offsets: below 4 GB is the caller's contract (header), it
-    // cannot be checked here -- the row count is no argument of this entry point
-    return n_res >= 32 ? et_launch<true, true>(S2S_ET_PASS) : et_launch<false, true>(S2S_ET_PASS);
-}
-#endif
-#if S2S_PM_PART == 1
-extern "C" int s2s_edge_transition_f16x3(S2S_ET_ARGS) {
-    if (io_layout & 8) return s2s_et_f16x3_by_class(S2S_ET_PASS);
-    return n_res >= 32 ? et_launch<true>(S2S_ET_PASS) : s2s_et_f16x3_short_chains(S2S_ET_PASS);
-}
-#endif
-
-#if S2S_PM_PART == 3
-extern "C" int s2s_edge_embed_f16x3(const float* node_a, const float* node_b, const float* rel_table, const float* bin_table,
-                                     const float* bin_lower, const long long* residue_idx, const float* ca_xyz,
-                                     const void* weight_stream, const float* b2, const float* b3, const float* ln_gamma,
-                                     const float* ln_beta, const float* mask, float* out, int n_samples, int n_res,
-                                     int rel_offset, int n_rel, int n_bins, float ln_eps, int out_tiled, const float* proj_bias_cat64,
-                                     float* proj_attn_bias, float* proj_pair_z, int* range_words, void* stream) {
-    if (n_samples <= 0 || n_res <= 0) return 0;
-    if (n_bins > 32 || (out_tiled & ~1)) return (int)hipErrorInvalidValue;  // the distogram edges are counted from a 32-entry LDS table
-    // 32-bit pair indices and buffer offsets inside a launch: split the samples over several launches when needed
-    const long long NN = (long long)n_res * n_res;
-    if (NN >= (1ll << 31) || (long long)n_rel * 512 >= (1ll << 32)) return (int)hipErrorInvalidValue;
-    const char* cap_env = getenv("S2S_EE_MAX_PAIRS");   // test hook: a smaller per-launch pair budget exercises the split
-    long long cap = cap_env ? atoll(cap_env) : 0;
-    if (cap <= 0 || cap > (1ll << 31) - 1) cap = (1ll << 31) - 1;
-    long long chunk = cap / NN;
-    const long long rows_cap = ((1ll << 32) - 1) / ((long long)n_res * 512);  // node_b descriptor
-    if (rows_cap < chunk) chunk = rows_cap;
-    if (out_tiled && chunk < n_samples) chunk -= chunk % tile_aligned_samples(NN);
-    if (chunk < 1) return (int)hipErrorInvalidValue;
-    const int n_cu = cu_count();
-    for (long long b0 = 0; b0 < n_samples; b0 += chunk) {
-        const long long nb = n_samples - b0 < chunk ? n_samples - b0 : chunk;
-        const long long M = nb * NN, rows0 = b0 * n_res;
-        const long long wg_tiles = (M + 127) / 128;
-        const long long grid = wg_tiles < n_cu ? wg_tiles : n_cu;
-        const float* na = node_a + rows0 * 128;
-        const float* nbp = node_b + rows0 * 128;
-        const long long* ridx = residue_idx + rows0;
-        const float* cap = ca_xyz + rows0 * 3;
-        const float* mk = mask ? mask + rows0 : nullptr;
-        float* o = out + b0 * NN * 128;
-        if (proj_attn_bias)
-            hipLaunchKernelGGL(edge_embed_f16_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, na, nbp,
-                               rel_table, bin_table, bin_lower, ridx, cap, (const char*)weight_stream, b2, b3, ln_gamma, ln_beta,
-                               mk, o, M, n_res, rel_offset, n_rel, n_bins, ln_eps, out_tiled, proj_bias_cat64,
-                               proj_attn_bias + b0 * 8 * NN, proj_pair_z + b0 * NN * 32, range_words);
-        else
-            hipLaunchKernelGGL(edge_embed_f16_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, na, nbp,
-                               rel_table, bin_table, bin_lower, ridx, cap, (const char*)weight_stream, b2, b3, ln_gamma, ln_beta,
-                               mk, o, M, n_res, rel_offset, n_rel, n_bins, ln_eps, out_tiled, (const float*)nullptr, (float*)nullptr,
-                               (float*)nullptr, range_words);
-    }
-    return (int)hipGetLastError();
-}
-#endif   // S2S_PM_PART == 3
-
-#if S2S_PM_PART == 4
-extern "C" int s2s_edge_embed_classes_f16x3(const float* node_a2, const float* node_b2, const float* rel_table, const float* bin_table,
-                                             const void* weight_stream, const float* b2, const float* b3, const float* ln_gamma,
-                                             const float* ln_beta, float* table, int n_fixed, int n_rel, int n_bins, float ln_eps,
-                                             const float* proj_bias_cat64, int* range_words, void* stream) {
-    if (n_fixed < 1 || n_fixed > 2 || n_rel < 1 || n_bins < 1 || n_bins > 32) return (int)hipErrorInvalidValue;
-    const long long M = (long long)(n_fixed == 2 ? 4 : 1) * n_rel * (n_bins + 1);   // class rows: every (fa, fb) of the fixed classes present
-    if (M * s2s::kEeRecProj * 4 >= (1ll << 32) || (long long)n_rel * 512 >= (1ll << 32)) return (int)hipErrorInvalidValue;   // 32-bit offsets
-    const long long wg_tiles = (M + 127) / 128;
-    const int n_cu = cu_count();
-    const long long grid = wg_tiles < n_cu ? wg_tiles : n_cu;
-    if (proj_bias_cat64)
-        hipLaunchKernelGGL((edge_embed_f16_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, node_a2, node_b2,
-                           rel_table, bin_table, (const float*)nullptr, (const long long*)nullptr, (const float*)nullptr,
-                           (const char*)weight_stream, b2, b3, ln_gamma, ln_beta, (const float*)nullptr, table, M, n_fixed, 0, n_rel, n_bins,
-                           ln_eps, 0, proj_bias_cat64, (float*)nullptr, (float*)nullptr, range_words);
-    else
-        hipLaunchKernelGGL((edge_embed_f16_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, node_a2, node_b2,
-                           rel_table, bin_table, (const float*)nullptr, (const long long*)nullptr, (const float*)nullptr,
-                           (const char*)weight_stream, b2, b3, ln_gamma, ln_beta, (const float*)nullptr, table, M, n_fixed, 0, n_rel, n_bins,
-                           ln_eps, 0, (const float*)nullptr, (float*)nullptr, (float*)nullptr, range_words);
-    return (int)hipGetLastError();
-}
-#endif   // S2S_PM_PART == 4

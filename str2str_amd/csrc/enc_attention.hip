@@ -190,7 +190,7 @@ __global__ void __launch_bounds__(256) enc_attention_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// The same operator on split-f16 MFMA ("f16x3", the default arithmetic; see csrc/pair_mlp_f16.hip): every operand as two f16 numbers
+// The same operator on split-f16 MFMA ("f16x3", the default arithmetic; see csrc/pair_f16.h): every operand as two f16 numbers
 // x = x_h + x_l, three v_mfma_f32_32x32x16_f16 per (k-step, tile) instead of eight v_mfma_f32_32x32x2_f32 at 1/16 of their rate
 // -- 33 matrix instructions of 32 cycles per key tile and wave instead of 88 of 64.  Same workgroup shape, same online softmax in
 // fp32; what changes is the operand plumbing:

@@ -2,7 +2,7 @@
 // the split-f16 ("f16x3") primitive.
 //
 // Split.  An fp32 value x becomes two f16 numbers  x = x_h + x_l (+ <= 2^-24 |x|),  x_h = rn16(x),  x_l = rn16(x - x_h), and a
-// product keeps  W_h x_h + W_h x_l + W_l x_h  on v_mfma_f32_32x32x16_f16 (csrc/pair_mlp_f16.hip, header).  The split is written as
+// product keeps  W_h x_h + W_h x_l + W_l x_h  on v_mfma_f32_32x32x16_f16 (csrc/pair_f16.h, header).  The split is written as
 // ONE opaque inline-asm block per 2 or 4 values:
 //   x_h = rn16(x):            v_cvt_pk_f16_f32, two values per instruction
 //   x_l = rn16(x - x_h):      the difference is exact in fp32, so ONE fused multiply-add that reads x_h as f16 and rounds to f16

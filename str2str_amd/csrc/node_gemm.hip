@@ -1,4 +1,4 @@
-// Per-node dense layers on split-f16 MFMA ("f16x3", fp32-equivalent; the formulation of pair_mlp_f16.hip): every nn.Linear of the
+// Per-node dense layers on split-f16 MFMA ("f16x3", fp32-equivalent; the formulation of pair_f16.h): every nn.Linear of the
 // trunk that acts on the [B*N, c] node stream -- linear_q / linear_kv / point projections, linear_out, skip_embed, the transformer's
 // in/out projections and feed-forward, trunk.linear_b, NodeTransition, BackboneUpdate, EdgeTransition.initial_embed and the
 // per-node halves of its first layer, TorsionAngleHead (reference src/models/net/ipa.py:131-171,259-266,312-317,357-366;

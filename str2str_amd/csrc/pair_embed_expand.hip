@@ -1,7 +1,7 @@
 // Edge embedding, second half of the CLASS path: expand the class table of s2s_edge_embed_classes_f16x3 to the pair tensors.
 //
 // With one timestep per chunk and a 0/1 fixed mask, a pair's whole MLP input -- and with it z, attn_bias and pair_z before the edge
-// mask -- depends only on its class (fixed_i, fixed_j, d, bin): csrc/pair_mlp_f16.hip ("TABLE") runs the MLP once per class row, and
+// mask -- depends only on its class (fixed_i, fixed_j, d, bin): csrc/edge_embed_f16.h ("TABLE") runs the MLP once per class row, and
 // this kernel computes every pair's class exactly as the edge embedding does (edge_embed_class.h: the same device functions) and
 // copies the row.  No matrix work, no weights: a wave owns a 32-pair block (16 KiB of z), reads its rows out of the cache -- the
 // table is a few MB to a few tens of MB -- and writes 672 B per pair.
@@ -19,9 +19,8 @@
 // table that was built with the fused projection), else 128.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "edge_embed_class.h"
+#include "pair_launch.h"
 #include "str2str_hip.h"
 
 namespace {
@@ -109,13 +108,6 @@ __global__ void __launch_bounds__(256) edge_embed_expand_kernel(
     }
 }
 
-// smallest number of samples whose pairs fill whole 32-pair blocks (launch boundaries of a tiled pair tensor)
-long long tile_aligned_samples(long long NN) {
-    long long q = 32;
-    while (q > 1 && (NN * (32 / q)) % 32 != 0) q /= 2;
-    return 32 / q;
-}
-
 }  // namespace
 
 extern "C" int s2s_edge_embed_expand(const float* table, const int* fixed_cls, const float* bin_lower, const long long* residue_idx,
@@ -128,11 +120,7 @@ extern "C" int s2s_edge_embed_expand(const float* table, const int* fixed_cls, c
     // 32-bit pair indices inside a launch: the split of s2s_edge_embed_f16x3 (and its test hook)
     const long long NN = (long long)n_res * n_res;
     if (NN >= (1ll << 31)) return (int)hipErrorInvalidValue;
-    const char* cap_env = getenv("S2S_EE_MAX_PAIRS");
-    long long cap = cap_env ? atoll(cap_env) : 0;
-    if (cap <= 0 || cap > (1ll << 31) - 1) cap = (1ll << 31) - 1;
-    long long chunk = cap / NN;
-    if (out_tiled == 1 && chunk < n_samples) chunk -= chunk % tile_aligned_samples(NN);
+    const long long chunk = s2s::samples_per_launch("S2S_EE_MAX_PAIRS", (1ll << 31) - 1, NN, n_samples, out_tiled == 1);   // (mode 2 is the index tensor)
     if (chunk < 1) return (int)hipErrorInvalidValue;
     for (long long b0 = 0; b0 < n_samples; b0 += chunk) {
         const long long nb = n_samples - b0 < chunk ? n_samples - b0 : chunk;

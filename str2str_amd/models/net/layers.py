@@ -139,7 +139,7 @@ class EdgeTransition(nn.Module):
         self.layer_norm = nn.LayerNorm(edge_embed_out)
         self._shape = (edge_embed_in, bias_embed_size, hidden, edge_embed_out, num_layers)
         self._cache, self._cache32, self._proj_cache, self._node_cache, self._c32, self._bf_cache = (DerivedCache() for _ in range(6))
-        self.arith = default_arith()      # "f16x3" (csrc/pair_mlp_f16.hip) | "f32" (csrc/pair_mlp.hip): see str2str_amd/arith.py
+        self.arith = default_arith()      # "f16x3" (csrc/edge_transition_f16.h) | "f32" (csrc/pair_mlp.hip): see str2str_amd/arith.py
         self.prescale_exp = 0             # f16x3: block exponent of the hidden activations (planes hold 2^-e x the value; the sampler raises
         #                                   it when the range guard reports activations of 2^15 and beyond: sampler.denoise_loop)
 

@@ -52,7 +52,7 @@ def fragment_order(w: torch.Tensor, kind: str) -> torch.Tensor:
 def pack_f16x2_layer(w: torch.Tensor, kind: str = "chain") -> torch.Tensor:
     """[Mout, K] fp32 -> f16 fragments [K/16][Mout/32][2 planes (W_h, W_l)][64][8] for v_mfma_f32_32x32x16_f16 A operands
     (lane / element order of ``fragment_order``): the f16 pair split of 2^5 w,  W_h = rn16(32 w),  W_l = rn16(32 w - W_h)  --
-    the power of two keeps W_l in f16's normal range; the kernels take 2^-5 back in their epilogues (csrc/pair_mlp_f16.hip).
+    the power of two keeps W_l in f16's normal range; the kernels take 2^-5 back in their epilogues (csrc/pair_f16.h).
     A weight with |32 w| beyond f16's range cannot be packed: ``WeightRangeError`` (the modules then run on the fp32 kernels)."""
     wmax = float(w.detach().abs().max()) if w.numel() else 0.0
     if not (32.0 * wmax < 65504.0):
@@ -65,7 +65,7 @@ def pack_f16x2_layer(w: torch.Tensor, kind: str = "chain") -> torch.Tensor:
 
 def pack_f16x3_stream(w1_edge: torch.Tensor, w2: torch.Tensor, wf: torch.Tensor) -> torch.Tensor:
     """The weight stream of s2s_edge_transition_f16x3 as int16: 240 slots of 4 fragments ((W_h, W_l) of two (k-step, tile) units;
-    8 slots = one 32 KiB stage, 30 stages) in the kernel's consumption order (csrc/pair_mlp_f16.hip):
+    8 slots = one 32 KiB stage, 30 stages) in the kernel's consumption order (csrc/edge_transition_f16.h):
       A_t (4 slots): layer-1 output tile t, k-step pairs (2s, 2s+1), fragments [k-step][plane];
       B_t (12 slots): layer-2 k-steps 2t + u (u = 0, 1) x output tile pairs 0..5, fragments [tile][plane]; B_11 pair-major
                       (pair b, then u): its first output tiles are complete early and their epilogue runs under the rest;

@@ -18,7 +18,7 @@ def _proj_outputs(proj, B, N, dev, dtype=torch.float32, name="proj.wp"):
 
 def edge_transition_f16x3(edge, node_ab, node_p, wstream, b2, gamma, beta, mask, ln_eps=1e-5, out=None, proj=None,
                           out_layout: str = "rowmajor", prescale_exp: int = 0, ab_kernel_form: bool = False):
-    """EdgeTransition on split-f16 MFMA (fp32-equivalent accuracy; csrc/pair_mlp_f16.hip); same contract as ``edge_transition``.
+    """EdgeTransition on split-f16 MFMA (fp32-equivalent accuracy; csrc/edge_transition_f16.h); same contract as ``edge_transition``.
     ``proj`` = (31-stage stream = this layer's 30 stages (``pack_f16x3_stream``) + the next IPA block's projection stage
     (``pack_f16x2_layer``), bias64) also returns that block's (attn_bias [B,8,N,N], pair_z [B,N,N,32]).
     ``edge`` may be a ``PairTiled``, or a ``PairByClass`` (the edge embedding's class table + one class index per pair: the kernel reads
@@ -120,7 +120,7 @@ def edge_embed(node_a, node_b, rel_table, bin_table, bin_lower, residue_idx, ca,
 
 def edge_embed_f16x3(node_a, node_b, rel_table, bin_table, bin_lower, residue_idx, ca, wstream, b2, b3, gamma, beta, mask,
                      rel_offset: int, ln_eps=1e-5, out=None, proj=None, column_blocked_tables=False, out_layout: str = "rowmajor"):
-    """Edge embedding on split-f16 MFMA (csrc/pair_mlp_f16.hip); ``proj`` = (5-stage stream, bias64) also returns (attn_bias, pair_z).
+    """Edge embedding on split-f16 MFMA (csrc/edge_embed_f16.h); ``proj`` = (5-stage stream, bias64) also returns (attn_bias, pair_z).
     node_b / rel_table / bin_table: [.., rows, 128], or already ``column_blocked`` ([.., 32, rows, 4]) with the flag set.
     ``out_layout`` "tiled" -> a ``PairTiled`` for ``edge_transition_f16x3``."""
     lib = load_library()

@@ -1,7 +1,7 @@
 """Seeded case table of the pair-stream parity suite (tests/test_pair_parity.py, tests/test_pair_parity_cpu.py), its measure and its
 bound rule.  Nothing here looks at a kernel.
 
-Shapes (B, N), each the smallest that reaches its path of s2s_edge_transition_f16x3 (csrc/pair_mlp_f16.hip):
+Shapes (B, N), each the smallest that reaches its path of s2s_edge_transition_f16x3 (csrc/edge_transition_f16.h):
   N < 32 (the short-chain instantiation)   (1, 1), (1, 2), (3, 7) = 147 pairs: a partial second 128-pair tile, a partial 32-pair block, (2, 31)
   N >= 32                                  (1, 32), (1, 33), (2, 37)
   launch splits under S2S_ET_MAX_PAIRS     (5, 24) in launches of 2 + 2 + 1 samples, (20, 6) with a budget of 10 samples lowered to 8

@@ -110,10 +110,10 @@ def test_pack_weight_layout():
 
 
 def test_f16x3_weight_split_and_stream_layout():
-    """Host side of the split-f16 kernels (csrc/pair_mlp_f16.hip, node_gemm.hip): fragments sit where the kernels' lanes read them,
+    """Host side of the split-f16 kernels (csrc/pair_f16.h, node_gemm.hip): fragments sit where the kernels' lanes read them,
     the weight pair (W_h, W_l) of 2^5 w recovers w to fp32 rounding over the weights' range (the factor keeps W_l out of f16's
     subnormals for |w| >= 2^-14), a weight beyond the packing's range is refused, the stream follows the slot schedule documented
-    in csrc/pair_mlp_f16.hip (A_0 A_1 | B_0 A_2 | ... | B_10 B_11 | F), the fp32 node packing follows pack_weight's lane order, and
+    in csrc/edge_transition_f16.h (A_0 A_1 | B_0 A_2 | ... | B_10 B_11 | F), the fp32 node packing follows pack_weight's lane order, and
     the gather tables' column blocking is a pure permutation."""
     import pytest
 

@@ -1,4 +1,4 @@
-"""The pair stream on the HIP kernels (csrc/pair_mlp_f16.hip, csrc/pair_mlp.hip behind EdgeTransition / EmbeddingModule) against the
+"""The pair stream on the HIP kernels (csrc/edge_transition_f16.h, csrc/edge_embed_f16.h, csrc/pair_mlp.hip behind EdgeTransition / EmbeddingModule) against the
 float64 statement of its formulas (tests/ref_pair.py, evaluated with torch on the device), per pair, at the cases of
 tests/pair_cases.py: N below and from 32 (both STAGE instantiations), with and without the fused projection (both PROJ
 instantiations), launch splits, more tiles than persistent workgroups with a ragged end; the families flat, trained-like (x 150),

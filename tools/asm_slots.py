@@ -1,5 +1,5 @@
-"""Per-slot instruction mix of a slot-scheduled kernel from hipcc's -S output (tools/asm_stats.sh):
-    python tools/asm_slots.py gpurun_out/asm/pair_mlp_f16.s edge_transition_f16_kernelILb1E [mfmas_per_slot]
+"""Per-slot instruction mix of a slot-scheduled kernel from hipcc's -S output (tools/asm_stats.sh edge_transition_f16 OUT.s):
+    python tools/asm_slots.py OUT.s edge_transition_f16_kernelILb1E [mfmas_per_slot]
 Prints the class counts between every n-th MFMA (a "slot") and the totals; v_accvgpr moves and s_nop are listed on their own."""
 import collections
 import re

@@ -7,7 +7,8 @@ computes for a noised synthetic chain; the two paths' outputs compared as int32.
 
 Times are HIP events on the launch stream around the library calls (ops.KernelTimer): "embed" = table kernel + expansion (the table
 kernel is the same launch in both), "et" = the transition; 5 launches after a warm-up each, two interleaved series.  A library variant
-(tools/build_variant.sh with UNIT=pair_mlp_f16_e and -DS2S_ET_CLS_NT=1 or -DS2S_ET_CLS_SLOT=n) is measured by a second run of this script.
+is measured by a second run of this script; the variants of the profile (non-temporal table loads, another slot for the class-index request)
+were built from the source at commit 2f5af7f, which had a build-time switch for each.
 """
 import json
 import os

@@ -1,5 +1,5 @@
 // What can the edge-transition kernel's instruction mix sustain on this part?  One wave per SIMD, every CU busy, random operand bits
-// (power depends on toggling), runs long enough for the power cap to act.  Per "slot" (the unit of csrc/pair_mlp_f16.hip): 6
+// (power depends on toggling), runs long enough for the power cap to act.  Per "slot" (the unit of csrc/edge_transition_f16.h): 6
 // v_mfma_f32_32x32x16_f16 on two alternating accumulators.  Variants add, one at a time, what the real kernel needs around them:
 //   0  MFMAs only, operands in registers                         -> the power-limited matrix rate of this shape
 //   1  + the slot's 4 weight fragments from LDS (ds_read_b128, one slot ahead)

@@ -6,7 +6,7 @@
 // (B fragments: 8 x 1 KiB per k-step for 36 MFMAs; each wave writes the planes of the 32-channel tile it produced: 16 KiB per 8
 // k-steps), two barriers per round of 8 k-steps.  This file times the steady state of layer 2 of both forms, same random operand
 // bits, same VALU filler per MFMA, long enough for the power cap to act:
-//   kA  the slot skeleton of csrc/pair_mlp_f16.hip (et_roof.hip level 3)
+//   kA  the slot skeleton of csrc/edge_transition_f16.h (et_roof.hip level 3)
 //   kB  the width-split skeleton
 //   hipcc --offload-arch=gfx950 -O3 et_roof4.hip -o et_roof4 && ./et_roof4
 #include <hip/hip_runtime.h>
